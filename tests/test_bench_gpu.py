@@ -41,8 +41,28 @@ def _bench(*args, env=None, timeout=600, detail=False):
     return line, json.load(open(dfile))
 
 
+def test_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """without --full: one timed call of exactly --steps steps, the headline keys, nothing measured after the timed region;
+    --dump-outputs writes what that call returned"""
+    import numpy as np
+    dump = tmp_path / "out"
+    line, d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--dump-outputs", str(dump), detail=True)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "shapes/s" and line["config"]["full"] is False
+    assert len(d["config"]["ms_per_step_all_runs"]) == 1
+    assert line["roofline"]["achieved"] is None and line["cpu_baseline"]["value"] is None
+    assert "value_full_chain_1000" not in line and "roofline_voxelize" not in d
+    pts = np.load(dump / "points.npy")
+    assert pts.shape == (2, 2048, 3) and pts.dtype == np.float32 and np.isfinite(pts).all()
+    for name in ("sample_mean_global", "sample_var_global"):
+        assert np.load(dump / (name + ".npy")).dtype == np.float32
+
+
 def test_sample_line_contract_single_rank():
-    line, d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--repeats", "2", "--side-lines",
+    line, d = _bench("--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--batch", "2", "--repeats", "2", "--side-lines",
                      "--side-steps", "2", "--forced-steps", "8", "--small-batches", "1", detail=True)
     # the compact line: the contract's keys + the round-6 scalars (forced clouds, small batch, fractions, census)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
