@@ -262,13 +262,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_split_kernel(const float 
   // barrier that was there anyway; when a later tile raises a maximum the accumulators are multiplied by the exact power-of-two
   // ratio first.  Finer than one scale per tensor (every product carries >= 22 bits relative to the largest operand the
   // WORKGROUP has seen), deterministic (no cross-workgroup state), and no launch besides the kernel and its reduction.
-  __shared__ unsigned s_m[2][2];   // [parity][x, gy] bits of the tile's max |.| (finite values)
+  __shared__ unsigned s_m[2][3];   // [parity][x, gy] bits of the tile's max |.| (finite values); [parity][2]: x holds inf / NaN (all-zero maximum only)
   int Ex = 127, Eg = 127;          // 127 = not chosen yet (scale 1)
   float sxs = 1.f, sgs = 1.f;
-  if (tid < 4) s_m[tid >> 1][tid & 1] = 0u;
+  if (tid < 6) s_m[tid / 3][tid % 3] = 0u;
   auto tile_max = [&](int par) {   // this thread's staged registers -> s_m[par]
-    // v_max_f32 with the |.| source modifier: one instruction per staged value (max ignores NaN operands; an infinite maximum
-    // is not taken as a scale, below)
+    // v_max_f32 with the |.| source modifier: one instruction per staged value.  max ignores NaN operands but not inf: a
+    // thread whose maximum came out infinite takes the max over its finite values again (rare), so that an inf next to the
+    // tile's largest finite value cannot hide it from the scale (the cut of that value would overflow fp16)
     float fg = 0.f, fx = 0.f;
 #pragma unroll
     for (int c = 0; c < 32; ++c) fg = fmaxf(fg, fabsf(rgy[c]));
@@ -277,8 +278,20 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_split_kernel(const float 
 #pragma unroll
       for (int c = 0; c < CIT; ++c) fx = fmaxf(fx, fabsf(rx[i][c]));
     unsigned mg = __float_as_uint(fg), mx = __float_as_uint(fx);
-    mg = mg <= 0x7f7fffffu ? mg : 0u;
-    mx = mx <= 0x7f7fffffu ? mx : 0u;
+    if (mg > 0x7f7fffffu || mx > 0x7f7fffffu) {   // rare, one branch off the common path
+      if (mg > 0x7f7fffffu) {
+        mg = 0u;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) { const unsigned u = __float_as_uint(rgy[c]) & 0x7fffffffu; mg = u <= 0x7f7fffffu && u > mg ? u : mg; }
+      }
+      if (mx > 0x7f7fffffu) {
+        mx = 0u;
+#pragma unroll
+        for (int i = 0; i < NXI; ++i)
+#pragma unroll
+          for (int c = 0; c < CIT; ++c) { const unsigned u = __float_as_uint(rx[i][c]) & 0x7fffffffu; mx = u <= 0x7f7fffffu && u > mx ? u : mx; }
+      }
+    }
     mg = wave_max_u32_lane63(mg);
     mx = wave_max_u32_lane63(mx);
     if (lane == 63) { if (mx) atomicMax(&s_m[par][0], mx); if (mg) atomicMax(&s_m[par][1], mg); }
@@ -323,8 +336,19 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_split_kernel(const float 
     __syncthreads();               // the tile's maxima are complete; the previous tile's LDS reads are done
     // A tile whose input window (halo included) is all zero adds nothing: no cut, no LDS stores, no MFMAs -- only its loads,
     // which were in flight already.  The first convolution of every PVConv reads a freshly voxelized grid (2048 points in 32^3
-    // voxels: most 256-voxel tiles are empty); the tile's maximum is known here anyway.
-    const bool empty = s_m[par][0] == 0u;   // uniform over the workgroup
+    // voxels: most 256-voxel tiles are empty); the tile's maximum is known here anyway.  A window of zeros and inf / NaN (a
+    // voxelised grid after training diverged) is not empty: its non-finite products reach the gradient as in the fp32 kernel.
+    bool empty = s_m[par][0] == 0u;   // uniform over the workgroup
+    if (empty) {   // no finite non-zero value in the window: is it all +-0 (sign bit masked), or does it hold inf / NaN?
+      unsigned any = 0u;
+#pragma unroll
+      for (int i = 0; i < NXI; ++i)
+#pragma unroll
+        for (int c = 0; c < CIT; ++c) any |= __float_as_uint(rx[i][c]);
+      if (any & 0x7fffffffu) s_m[par][2] = 1u;   // (benign race: every writer stores 1); flagged apart from the maximum,
+      __syncthreads();                           // which sets no scale
+      empty = s_m[par][2] == 0u;
+    }
     if (!empty) {
       const unsigned bx = s_m[par][0], bg = s_m[par][1];
       float f = 1.f;               // what the accumulated sums have to be multiplied by (<= 1, exact)
@@ -338,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_split_kernel(const float 
       }
     }
     if (!empty) store_tile();
-    if (tid < 2) s_m[par ^ 1][tid] = 0u;   // the other parity: its last readers passed the barrier above
+    if (tid < 3) s_m[par ^ 1][tid] = 0u;   // the other parity: its last readers passed the barrier above
     __syncthreads();
     if (tn < ntiles) load_tile(tn);
     // 4 k-steps of 16 voxels over this wave's 64 voxels; a lane's fragment = voxels v0 .. v0 + 7 of one row

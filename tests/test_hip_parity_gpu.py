@@ -941,8 +941,9 @@ def test_conv3d_wgrad_matches_fp64_reference(cin, cout, r):
     e32 = (gw.double() - wd.grad).abs().max().item() / wd.grad.abs().max().item()
     assert e32 < 2e-5
     if cin % 8 == 0:
-        # round 4: the same gradient on the 16-bit pipe (fp16 pairs cut in registers, per-tensor scales): held to the fp32
-        # kernel's own error (both accumulate ~10^5 products in fp32), also with operands 1e-6 / 1e4 away from unit scale
+        # the same gradient on the 16-bit pipe (fp16 pairs, a running power-of-two scale per workgroup and operand): held to
+        # the fp32 kernel's own error (both accumulate ~10^5 products in fp32), also with operands 1e-6 / 1e4 away from unit
+        # scale (adversarial ranges: test_conv_grad_numerics_gpu.py)
         gs = conv3d_k3_wgrad(x, gy, w.shape, split=True)
         es = (gs.double() - wd.grad).abs().max().item() / wd.grad.abs().max().item()
         assert es < max(2 * e32, 4e-6), (es, e32)
