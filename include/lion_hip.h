@@ -550,6 +550,47 @@ int lion_adam_row(void);
 int lion_adam_step(const uint64_t *table, const int32_t *numel, const int32_t *blockmap, int blocks, int tensors, const float *lr,
                    float beta1, float beta2, float eps, float weight_decay, float ema_decay, lionStream_t stream);
 
+/* ---- probability-flow ODE of the VPSDE: scipy's RK45 on the device (csrc/ode.hip) --------------------------------------
+ * utils/diffusion_continuous.py:90-255 (compute_ode_nll / sample_model_ode) hand the PF-ODE of the whole batch -- ONE system
+ * of n = B*D unknowns -- to scipy.integrate.solve_ivp(method='RK45') (rk.py RK45._step_impl, common.py select_initial_step)
+ * through torchdiffeq's scipy wrapper.  Here its state stays on the device:
+ *   Y f64[2][n]  (y and y_new; row ctrl->yslot is y), K f64[7][n] (stage derivatives; rows 0 / 6 swap roles via ctrl->fslot),
+ *   x32 f32[n] (the model's input: fp32 of the stage state), t_model f32[B] (the model's time, sign-applied),
+ *   partials f64[lion_ode_partials_bytes(n) / 8], ctrl (below; device memory, written by the host once per solve).
+ * One evaluation: lion_ode_stage (stage ctrl->stage: 1..6 a step's stages, 7 = f0 at t0, 8 = the initial-step probe)
+ *   -> the denoiser reads x32 / t_model -> lion_ode_drift writes row `stage` of K:
+ *   dx/dt = f(t) x + 0.5 g2(t) params / sqrt(var(t)) in fp32 (diffusion_continuous.py:205-226, :599-622), negated when
+ *   ctrl->sign < 0 (torchdiffeq misc.py:152-159, _ReverseFunc), widened to f64.  eps is the model output, [n] or, with
+ *   cm_points = N != 0, the local prior's channel-major [B][4][N] for a point-major [B][N][4] latent.  mix_a / mix_b
+ *   (f32[mix_len], n % mix_len == 0, both NULL without mixing): 1 - sigmoid(mixing_logit), sigmoid(mixing_logit).
+ *   The schedule scalars are the fp32 roundings of beta_start, beta_end - beta_start, -beta_start,
+ *   0.5 * (beta_end - beta_start) and 1 - sigma2_0, as torch applies them to a float32 t.
+ * One attempted step ends with lion_ode_error_partials -> lion_ode_control: the RMS norm of the error estimate (or of the
+ *   initial-step quantities d0, d1 / d2), reduced in a fixed order (no float atomics), and scipy's controller: accept /
+ *   reject, SAFETY 0.9, factor in [0.2, 10], exponent -1/5, factor <= 1 after a rejection, the last step clipped to t_bound,
+ *   TOO_SMALL_STEP below 10 x the spacing of doubles at t; the next attempt's h and t_new are prepared and stage = 1.
+ *   The host reads ctrl once per attempted step. */
+#define LION_ODE_RUNNING 0
+#define LION_ODE_FINISHED 1
+#define LION_ODE_TOO_SMALL_STEP (-1)
+typedef struct lion_ode_ctrl {
+  double t, h_abs, t_bound, direction, rtol, atol;
+  double h, t_new, err_norm, h0, d1, sign;  /* attempt's step and end time; last norm; initial-step h0, d1; time sign */
+  int32_t stage, cur, status, step_rejected; /* next stage; stage of the running evaluation; LION_ODE_*; this step */
+  int32_t yslot, fslot, nfe, n_accepted;
+  int32_t n_rejected, accepted, pad0, pad1;  /* accepted: the last attempt was */
+} lion_ode_ctrl;
+size_t lion_ode_partials_bytes(size_t n);
+int lion_ode_stage(double *Y, const double *K, size_t n, lion_ode_ctrl *ctrl, float *x32, float *t_model, int B,
+                   lionStream_t stream);
+int lion_ode_drift(const float *eps, int cm_points, const float *x32, size_t n, const float *t_model, float beta_start,
+                   float beta_delta, float neg_beta_start, float half_beta_delta, float one_minus_sigma2_0,
+                   const float *mix_a, const float *mix_b, int mix_len, double *K, lion_ode_ctrl *ctrl,
+                   lionStream_t stream);
+int lion_ode_error_partials(const double *Y, const double *K, size_t n, const lion_ode_ctrl *ctrl, double *partials,
+                            lionStream_t stream);
+int lion_ode_control(const double *partials, size_t n, lion_ode_ctrl *ctrl, lionStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,11 @@ SIGNATURES = {
     "lion_latent_unpack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_concat_broadcast": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lion_three_nn_interpolate_cat_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "lion_ode_partials_bytes": (_sz, [_sz]),
+    "lion_ode_stage": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp]),
+    "lion_ode_drift": (_i, [_vp, _i, _vp, _sz, _vp, _f, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _vp]),
+    "lion_ode_error_partials": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "lion_ode_control": (_i, [_vp, _sz, _vp, _vp]),
 }
 
 

@@ -42,7 +42,10 @@ def policy_key() -> tuple:
 
 class GraphedChain:
     def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
-                 record_noise=False):
+                 record_noise=False, step_fn=None):
+        """step_fn(chain), if given, replaces the chain's step: another driver's kernels around the same forward, captured
+        with the same machinery (lion_amd/ode.py: [ODE stage -> forward -> drift]); it reads chain.x / chain.t / chain.cond /
+        chain.clip as the model's inputs."""
         self.model, self.mode, self.capacity = model, mode, int(capacity)
         self.fingerprint = _wcache.fingerprint(model)
         dev = torch.device(device)
@@ -65,7 +68,7 @@ class GraphedChain:
         # per run() (model.time_embedding over the schedule) and a replayed step picks its row by the device-resident step
         # index -- instead of 7 (global prior) / 3 (local prior) launches per step that recompute it for every sample.
         self.temb_table = None
-        self.use_temb_table = TEMB_TABLE and hasattr(model, "time_embedding") and not getattr(model, "embed_dim", 1) == 0
+        self.use_temb_table = step_fn is None and TEMB_TABLE and hasattr(model, "time_embedding") and not getattr(model, "embed_dim", 1) == 0
         self.policy = policy_key()
         self.pinned = []         # strong references to every packed / mirrored weight the captured launches point at
         lib = _lib.load()
@@ -77,6 +80,9 @@ class GraphedChain:
                        and int(np.prod(shape)) == n_pts * n_cls and not getattr(model, "mixed_prediction", False))
 
         def step():
+            if step_fn is not None:
+                step_fn(self)
+                return
             st = _lib.stream_ptr(dev)
             extra = {}
             if self.temb_table is not None:   # the step's time-embedding row, copied by the prologue kernel itself

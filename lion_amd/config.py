@@ -54,7 +54,10 @@ _RELEASED_PRIOR = {
                 learning_rate_dae=2e-4, weight_decay=3e-4,
                 prior_model="models.latent_points_ada_localprior.PVCNN2Prior",
                 kl_anneal_portion_vada=0.5, kl_const_portion_vada=0.0, kl_const_coeff_vada=1e-7,
-                kl_max_coeff_vada=0.5),
+                kl_max_coeff_vada=0.5,
+                # continuous-time diffusion (lion_amd/diffusion_continuous.py; ode_sample = 1), default_config.py:99-130
+                sde_type="vpsde", beta_start=0.1, beta_end=20.0, sigma2_0=0.0, time_eps=1e-2, ode_eps=1e-5,
+                iw_sample_p="ll_iw", iw_subvp_like_vp_sde=False, time_emb_scales=1.0),
     "shapelatent": dict(latent_dim=1, kl_weight=0.5, log_sigma_offset=6.0,
                         decoder_type="models.latent_points_ada.LatentPointDecPVC",
                         encoder_type="models.latent_points_ada.PointTransPVC", model="models.vae_adain"),

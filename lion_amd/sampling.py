@@ -12,18 +12,30 @@ import torch
 def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable_autocast=False,
                                  temp=1.0, ddim_step=0, clip_feat=None, ddim_skip_type='uniform',
                                  ddim_kappa=1.0, noise='device', step_callback=None, graph=True, given_noise=None,
-                                 state_hook=None):
+                                 state_hook=None, ode_sample=0, ode_eps=1e-5, ode_solver_tol=1e-5, start_noise=None):
     """shape: vae.latent_shape(); dae: [global prior, local prior].  Returns (points [B,N,3], info).
     graph=True (default): every chain is replayed from one captured hipGraph per prior (lion_amd/chain.py);
     graph=False: the eager per-step loop; noise='cpu' draws the start and every step's noise from torch's CPU generator
     (one seed = one chain on any device: what the sampler-level parity test runs on the GPU and on the host);
     given_noise = [(start, [z per step]) per prior] replays recorded draws through the eager loop (DDIM only).
     state_hook(prior_index, step_index, x): may overwrite a chain's latent in place before a model evaluation (DDIM only;
-    device-side launches, no host synchronisation)."""
+    device-side launches, no host synchronisation).
+    ode_sample=1 (train_2prior.py:58-75): each prior integrates the probability-flow ODE of a continuous diffusion
+    (diffusion_continuous.DiffusionVPSDE) from t = 1 to ode_eps at tolerance ode_solver_tol, starting from
+    start_noise[i] if given (else fresh N(0, I) draws); info['nfe'] lists the evaluations per prior."""
     condition_input = None
     all_eps = []
+    nfes = []
     for i in range(len(dae)):
-        if ddim_step > 0:
+        if ode_sample == 1:
+            if not hasattr(diffusion, 'sample_model_ode'):
+                raise TypeError('ODE-based sampling requires a continuous diffusion (diffusion_continuous.make_diffusion)')
+            eps, nfe, _ = diffusion.sample_model_ode(dae[i], num_samples, shape[i], ode_eps, ode_solver_tol,
+                                                     enable_autocast, temp,
+                                                     None if start_noise is None else start_noise[i],
+                                                     condition_input=condition_input, clip_feat=clip_feat, graph=graph)
+            nfes.append(nfe)
+        elif ddim_step > 0:
             eps, _ = diffusion.run_ddim(dae[i], num_samples, shape[i], temp, enable_autocast,
                                         is_image=False, ddim_step=ddim_step,
                                         condition_input=condition_input, clip_feat=clip_feat,
@@ -46,6 +58,8 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
     eps = vae.compose_eps(all_eps)
     info = {'print/sample_mean_global': eps.view(num_samples, -1).mean(-1).mean(),
             'print/sample_var_global': eps.view(num_samples, -1).var(-1).mean()}
+    if ode_sample == 1:
+        info['nfe'] = nfes
     points = vae.sample(num_samples=num_samples, decomposed_eps=vae.decompose_eps(eps))
     return points, info
 
