@@ -177,6 +177,36 @@ def check(code: int, what: str) -> None:
         raise RuntimeError(f"lion_amd: {what} failed: {msg}")
 
 
+def call(name: str, *args, unsupported_ok: bool = False) -> bool:
+    """Launch the C entry point `name` (an `int f(..., lionStream_t stream)` of include/lion_hip.h) on the current stream.
+
+    `args` are its parameters in header order without the stream: a tensor stands for its data_ptr(), None for NULL, numbers
+    pass as they are.  Layout and dtype stay the caller's business (strided views are passed on purpose).  Every tensor must be
+    a CUDA(HIP) tensor and all on one device -- checked before the library is entered -- and, being arguments of this call, they
+    are alive until it returns.  A non-zero return raises; with unsupported_ok, LION_EUNSUPPORTED returns False instead.
+    This runs once per launch of an eager step: one isinstance and one get_device() (-1 for a CPU tensor) per argument."""
+    import torch
+    if len(args) + 1 != len(SIGNATURES[name][1]):
+        raise TypeError(f"lion_amd: {name} takes {len(SIGNATURES[name][1]) - 1} arguments before the stream, got {len(args)}")
+    dev, argv = None, list(args)
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            d = a.get_device()
+            if d != dev:
+                if d < 0:
+                    raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
+                if dev is not None:
+                    raise RuntimeError(f"lion_amd: {name}: operands on different devices (cuda:{dev} and cuda:{d})")
+                dev = d
+            argv[i] = a.data_ptr()
+    # the handle of torch.cuda.current_stream(dev) without building the Stream object (what torch.compile's own wrappers call)
+    rc = getattr(load(), name)(*argv, torch._C._cuda_getCurrentRawStream(torch.cuda.current_device() if dev is None else dev))
+    if rc == -2 and unsupported_ok:
+        return False
+    check(rc, name)
+    return True
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())

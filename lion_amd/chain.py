@@ -71,7 +71,6 @@ class GraphedChain:
         self.use_temb_table = step_fn is None and TEMB_TABLE and hasattr(model, "time_embedding") and not getattr(model, "embed_dim", 1) == 0
         self.policy = policy_key()
         self.pinned = []         # strong references to every packed / mirrored weight the captured launches point at
-        lib = _lib.load()
 
         # the local prior hands back its channel-major [B, 4, N] output; the update reads it in that layout (round 6: no
         # transposing ATen copy at the end of a step)
@@ -83,32 +82,24 @@ class GraphedChain:
             if step_fn is not None:
                 step_fn(self)
                 return
-            st = _lib.stream_ptr(dev)
             extra = {}
             if self.temb_table is not None:   # the step's time-embedding row, copied by the prologue kernel itself
-                _lib.check(lib.lion_chain_begin_step_temb(_lib.ptr(self.table), self.capacity, _lib.ptr(self.counter),
-                                                          _lib.ptr(self.t), num_samples, _lib.ptr(self.cur),
-                                                          _lib.ptr(self.temb_table), self.temb_row.numel(),
-                                                          _lib.ptr(self.temb_row), st), "chain_begin_step_temb")
+                _lib.call("lion_chain_begin_step_temb", self.table, self.capacity, self.counter, self.t, num_samples, self.cur,
+                          self.temb_table, self.temb_row.numel(), self.temb_row)
                 extra["temb"] = self.temb_row
             else:
-                _lib.check(lib.lion_chain_begin_step(_lib.ptr(self.table), self.capacity, _lib.ptr(self.counter),
-                                                     _lib.ptr(self.t), num_samples, _lib.ptr(self.cur), st),
-                           "chain_begin_step")
+                _lib.call("lion_chain_begin_step", self.table, self.capacity, self.counter, self.t, num_samples, self.cur)
             if self.cm_out:
                 pred = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, channel_major_out=True,
                              **extra)
                 eps = pred.float().contiguous()
                 assert tuple(eps.shape) == (num_samples, n_cls, n_pts)
-                _lib.check(lib.lion_chain_update_noise_cm(mode, _lib.ptr(self.x), _lib.ptr(eps), num_samples, n_pts,
-                                                          _lib.ptr(self.cur), _lib.ptr(self.seed), 0, _lib.ptr(self.x),
-                                                          _lib.ptr(self.z), _lib.stream_ptr(dev)), "chain_update_noise_cm")
+                _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
+                          self.z)
                 return
             pred = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **extra)
             eps = pred.float().contiguous()
-            _lib.check(lib.lion_chain_update_noise(mode, _lib.ptr(self.x), _lib.ptr(eps), self.x.numel(),
-                                                   _lib.ptr(self.cur), _lib.ptr(self.seed), 0, _lib.ptr(self.x),
-                                                   _lib.ptr(self.z), _lib.stream_ptr(dev)), "chain_update_noise")
+            _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
 
         # Split-graph geometry overlap (geometry.SPLIT_GRAPH, models with a geometry_source()): the FPS / ball-query chain of
         # a step depends on the coordinates of x alone, is latency bound (0.7 ms on 32 CUs) and, on one stream, serial.

@@ -23,9 +23,7 @@ class _Chamfer3DModule:
         _lib.require_cuda(xyz1, xyz2, dist1, dist2, idx1, idx2)
         b, n, _ = xyz1.shape
         m = xyz2.shape[1]
-        _lib.check(_lib.load().lion_chamfer_forward(
-            _lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(dist1), _lib.ptr(dist2),
-            _lib.ptr(idx1), _lib.ptr(idx2), _lib.stream_ptr(xyz1.device)), "chamfer forward")
+        _lib.call("lion_chamfer_forward", xyz1, xyz2, b, n, m, dist1, dist2, idx1, idx2)
         return 1
 
     @staticmethod
@@ -33,10 +31,7 @@ class _Chamfer3DModule:
         _lib.require_cuda(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2)
         b, n, _ = xyz1.shape
         m = xyz2.shape[1]
-        _lib.check(_lib.load().lion_chamfer_backward(
-            _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(graddist1), _lib.ptr(graddist2),
-            _lib.ptr(idx1), _lib.ptr(idx2), b, n, m, _lib.ptr(gradxyz1), _lib.ptr(gradxyz2),
-            _lib.stream_ptr(xyz1.device)), "chamfer backward")
+        _lib.call("lion_chamfer_backward", xyz1, xyz2, graddist1, graddist2, idx1, idx2, b, n, m, gradxyz1, gradxyz2)
         return 1
 
 

@@ -35,14 +35,18 @@ def use_split(split, cin, cout, r):
     return bool(split) and split_supported(cin, cout, r)
 
 
-def _split_pack(weight):
+def pack_with(weight, size_query, pack, dtype, as_matrix=False):
+    """the packed copy of a [Cout, Cin, ...] weight every packer here and in fused_ops makes: `size_query`(Cout, Cin) elements
+    of `dtype`, filled by the launch `pack`; as_matrix: the kernel-size-1 weights are handed over as [Cout, Cin]"""
     cout, cin = weight.shape[:2]
-    lib = _lib.load()
-    wp = torch.empty((lib.lion_conv3d_split_packed_halfs(cout, cin),), device=weight.device, dtype=torch.int16)
-    w_c = weight.detach().contiguous()
-    _lib.check(lib.lion_conv3d_split_pack_weights(_lib.ptr(w_c), cout, cin, _lib.ptr(wp),
-                                                  _lib.stream_ptr(weight.device)), "conv3d_split_pack_weights")
+    wp = torch.empty((getattr(_lib.load(), size_query)(cout, cin),), device=weight.device, dtype=dtype)
+    w = weight.detach().reshape(cout, cin) if as_matrix else weight.detach()
+    _lib.call(pack, w.contiguous(), cout, cin, wp)
     return wp
+
+
+def _split_pack(weight):
+    return pack_with(weight, "lion_conv3d_split_packed_halfs", "lion_conv3d_split_pack_weights", torch.int16)
 
 
 _SPLIT_CACHE = WeightCache(_split_pack)
@@ -55,13 +59,7 @@ def split_packed_weight(weight):
 
 
 def _pack(weight):
-    cout, cin = weight.shape[:2]
-    lib = _lib.load()
-    wp = torch.empty((lib.lion_conv3d_packed_floats(cout, cin),), device=weight.device, dtype=torch.float32)
-    w_c = weight.detach().contiguous()  # local reference: see fused_ops.groupnorm_fold
-    _lib.check(lib.lion_conv3d_pack_weights(_lib.ptr(w_c), cout, cin, _lib.ptr(wp),
-                                            _lib.stream_ptr(weight.device)), "conv3d_pack_weights")
-    return wp
+    return pack_with(weight, "lion_conv3d_packed_floats", "lion_conv3d_pack_weights", torch.float32)
 
 
 _PACK_CACHE = WeightCache(_pack)
@@ -87,9 +85,8 @@ def conv3d_k3(x, weight, bias=None, split=None, packed=None, occ=None):
         y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
         bias_c = bias.detach().contiguous() if bias is not None else None
         wp = packed("split") if packed is not None else split_packed_weight(weight)
-        _lib.check(_lib.load().lion_conv3d_k3_split_forward(
-            _lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias_c), b, cin, cout, r, None, None, None, None, _lib.ptr(y), None,
-            _lib.ptr(occ) if (occ is not None and r >= 16) else None, _lib.stream_ptr(x.device)), "conv3d_k3_split_forward")
+        _lib.call("lion_conv3d_k3_split_forward", x, wp, bias_c, b, cin, cout, r, None, None, None, None, y, None,
+                  occ if r >= 16 else None)
         return y
     if cin % 4:
         pad = 4 - cin % 4
@@ -101,9 +98,7 @@ def conv3d_k3(x, weight, bias=None, split=None, packed=None, occ=None):
     wp = packed("f32") if packed is not None else packed_weight(weight)
     y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
     bias_c = bias.detach().contiguous() if bias is not None else None
-    _lib.check(_lib.load().lion_conv3d_k3_forward(
-        _lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias_c),
-        b, cin_p, cout, r, _lib.ptr(y), _lib.stream_ptr(x.device)), "conv3d_k3_forward")
+    _lib.call("lion_conv3d_k3_forward", x, wp, bias_c, b, cin_p, cout, r, y)
     return y
 
 
@@ -168,21 +163,14 @@ def conv3d_k3_wgrad(x, gy, weight_shape, split=None, counts=None):
     n = (lib.lion_conv3d_wgrad_sparse_workspace_floats if sparse else lib.lion_conv3d_wgrad_workspace_floats)(b, cin, cout, r)
     ws = torch.empty((n,), device=x.device, dtype=torch.float32)
     x_c, gy_c = x.contiguous(), gy.contiguous()
-    st = _lib.stream_ptr(x.device)
-    if sparse:
-        cnt_c = counts.contiguous()
-        rc = lib.lion_conv3d_k3_wgrad_split_sparse(_lib.ptr(x_c), _lib.ptr(gy_c), _lib.ptr(cnt_c), b, cin, cout, r, _lib.ptr(gw),
-                                                   _lib.ptr(ws), n, st)
-        if rc != -2:
-            _lib.check(rc, "conv3d_k3_wgrad_split_sparse")
-            return gw
-    if (WGRAD_SPLIT if split is None else split) and cin % 8 == 0:
-        rc = lib.lion_conv3d_k3_wgrad_split(_lib.ptr(x_c), _lib.ptr(gy_c), b, cin, cout, r, _lib.ptr(gw), _lib.ptr(ws), n, st)
-        if rc != -2:   # LION_EUNSUPPORTED (alignment): the fp32 kernel below
-            _lib.check(rc, "conv3d_k3_wgrad_split")
-            return gw
-    _lib.check(lib.lion_conv3d_k3_wgrad(_lib.ptr(x_c), _lib.ptr(gy_c), b, cin, cout, r, _lib.ptr(gw), _lib.ptr(ws), n, st),
-               "conv3d_k3_wgrad")
+    # each kernel that answers LION_EUNSUPPORTED (alignment) hands over to the next; the fp32 kernel takes every shape
+    if sparse and _lib.call("lion_conv3d_k3_wgrad_split_sparse", x_c, gy_c, counts.contiguous(), b, cin, cout, r, gw, ws, n,
+                            unsupported_ok=True):
+        return gw
+    if (WGRAD_SPLIT if split is None else split) and cin % 8 == 0 and _lib.call(
+            "lion_conv3d_k3_wgrad_split", x_c, gy_c, b, cin, cout, r, gw, ws, n, unsupported_ok=True):
+        return gw
+    _lib.call("lion_conv3d_k3_wgrad", x_c, gy_c, b, cin, cout, r, gw, ws, n)
     return gw
 
 

@@ -24,9 +24,7 @@ class _EmdModule:
         m = xyz2.shape[1]
         match = torch.empty((b, m, n), device=xyz1.device, dtype=torch.float32)
         ws, nbytes = _ws(b, n, m, xyz1.device)
-        _lib.check(_lib.load().lion_emd_approxmatch(
-            _lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(match), _lib.ptr(ws), nbytes,
-            _lib.stream_ptr(xyz1.device)), "approxmatch_forward")
+        _lib.call("lion_emd_approxmatch", xyz1, xyz2, b, n, m, match, ws, nbytes)
         return match
 
     @staticmethod
@@ -36,9 +34,7 @@ class _EmdModule:
         m = xyz2.shape[1]
         cost = torch.empty((b,), device=xyz1.device, dtype=torch.float32)
         ws, nbytes = _ws(b, n, m, xyz1.device)
-        _lib.check(_lib.load().lion_emd_matchcost(
-            _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(match), b, n, m, _lib.ptr(cost),
-            _lib.ptr(ws), nbytes, _lib.stream_ptr(xyz1.device)), "matchcost_forward")
+        _lib.call("lion_emd_matchcost", xyz1, xyz2, match, b, n, m, cost, ws, nbytes)
         return cost
 
     @staticmethod
@@ -48,9 +44,7 @@ class _EmdModule:
         m = xyz2.shape[1]
         g1 = torch.empty((b, n, 3), device=xyz1.device, dtype=torch.float32)
         g2 = torch.empty((b, m, 3), device=xyz1.device, dtype=torch.float32)
-        _lib.check(_lib.load().lion_emd_matchcost_backward(
-            _lib.ptr(grad_cost), _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(match), b, n, m,
-            _lib.ptr(g1), _lib.ptr(g2), _lib.stream_ptr(xyz1.device)), "matchcost_backward")
+        _lib.call("lion_emd_matchcost_backward", grad_cost, xyz1, xyz2, match, b, n, m, g1, g2)
         return [g1, g2]
 
 
@@ -88,8 +82,7 @@ class EarthMoverDistanceFunctionNoGrad(torch.autograd.Function):
         m = xyz2.shape[1]
         cost = torch.empty((b,), device=xyz1.device, dtype=torch.float32)
         ws, nbytes = _ws(b, n, m, xyz1.device)
-        _lib.check(_lib.load().lion_emd_cost(_lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(cost), _lib.ptr(ws),
-                                             nbytes, _lib.stream_ptr(xyz1.device)), "emd_cost")
+        _lib.call("lion_emd_cost", xyz1, xyz2, b, n, m, cost, ws, nbytes)
         return cost
 
 

@@ -31,14 +31,9 @@ def _i32(t, name):
 class _HipBackend:
     """The 12 operator entry points of the reference's ``_pvcnn_backend`` module."""
 
-    def __init__(self):
-        self._l = None
-
     @property
     def lib(self):
-        if self._l is None:
-            self._l = _lib.load()
-        return self._l
+        return _lib.load()
 
     # -- sampling/sampling.cpp:8-24 ------------------------------------------------------------
     def gather_features_forward(self, features, indices):
@@ -46,9 +41,7 @@ class _HipBackend:
         b, c, n = features.shape
         m = indices.shape[1]
         out = torch.empty((b, c, m), device=features.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_gather_features_forward(
-            _lib.ptr(features), _lib.ptr(indices), b, c, n, m, _lib.ptr(out),
-            _lib.stream_ptr(features.device)), "gather_features_forward")
+        _lib.call("lion_gather_features_forward", features, indices, b, c, n, m, out)
         return out
 
     # -- sampling/sampling.cpp:26-41 -----------------------------------------------------------
@@ -56,9 +49,7 @@ class _HipBackend:
         _lib.require_cuda(grad_y, indices); _f32(grad_y, "grad_y"); _i32(indices, "indices")
         b, c, m = grad_y.shape
         gx = torch.empty((b, c, n), device=grad_y.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_gather_features_backward(
-            _lib.ptr(grad_y), _lib.ptr(indices), b, c, n, m, _lib.ptr(gx),
-            _lib.stream_ptr(grad_y.device)), "gather_features_backward")
+        _lib.call("lion_gather_features_backward", grad_y, indices, b, c, n, m, gx)
         return gx
 
     # -- sampling/sampling.cpp:43-58 -----------------------------------------------------------
@@ -66,9 +57,7 @@ class _HipBackend:
         _lib.require_cuda(coords); _f32(coords, "coords")
         b, _, n = coords.shape
         idx = torch.empty((b, num_samples), device=coords.device, dtype=torch.int32)
-        _lib.check(self.lib.lion_furthest_point_sampling(
-            _lib.ptr(coords), b, n, num_samples, _lib.ptr(idx), _lib.stream_ptr(coords.device)),
-            "furthest_point_sampling")
+        _lib.call("lion_furthest_point_sampling", coords, b, n, num_samples, idx)
         return idx
 
     # -- ball_query/ball_query.cpp:7-33 --------------------------------------------------------
@@ -78,9 +67,7 @@ class _HipBackend:
         b, _, m = centers_coords.shape
         n = points_coords.shape[2]
         idx = torch.empty((b, m, num_neighbors), device=centers_coords.device, dtype=torch.int32)
-        _lib.check(self.lib.lion_ball_query(
-            _lib.ptr(centers_coords), _lib.ptr(points_coords), b, m, n, float(radius),
-            int(num_neighbors), _lib.ptr(idx), _lib.stream_ptr(idx.device)), "ball_query")
+        _lib.call("lion_ball_query", centers_coords, points_coords, b, m, n, float(radius), int(num_neighbors), idx)
         return idx
 
     # -- grouping/grouping.cpp ----------------------------------------------------------------
@@ -89,14 +76,13 @@ class _HipBackend:
         b, c, n = features.shape
         _, m, u = indices.shape
         out = torch.empty((b, c, m, u), device=features.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_grouping_forward(
-            _lib.ptr(features), _lib.ptr(indices), b, c, n, m, u, _lib.ptr(out),
-            _lib.stream_ptr(out.device)), "grouping_forward")
+        _lib.call("lion_grouping_forward", features, indices, b, c, n, m, u, out)
         return out
 
-    def _scatter_csr(self, grad_y, indices, weights, S, E, bins, what):
+    def _scatter_csr(self, grad_y, indices, weights, S, E, bins, what=None):
         """gx[b,c,bin] = sum_{e: idx[b,e] = bin} w[b,e] * gy[b,c, e mod S] on csrc/scatter_csr.hip (no float atomics,
-        deterministic); None when the shape is outside its range (the callers fall back to the LDS-atomic kernels)."""
+        deterministic); None when the shape is outside its range (the callers fall back to the LDS-atomic kernels).
+        `what` (the caller's name for the operation) is accepted and unused: a failed launch is reported under its symbol."""
         b, c = grad_y.shape[:2]
         wsb = self.lib.lion_scatter_csr_workspace_bytes(b, E, bins)
         if wsb == 0 or ((bins + 7) // 8) * 4 > 60 * 1024 or S * 4 > 128 * 1024:
@@ -105,20 +91,17 @@ class _HipBackend:
         w = weights.contiguous() if weights is not None else None
         ws = torch.empty((wsb,), device=gy.device, dtype=torch.uint8)
         gx = torch.empty((b, c, bins), device=gy.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_scatter_csr(_lib.ptr(gy), _lib.ptr(idx), _lib.ptr(w), b, c, S, E, bins, _lib.ptr(ws), wsb,
-                                             _lib.ptr(gx), _lib.stream_ptr(gx.device)), what)
+        _lib.call("lion_scatter_csr", gy, idx, w, b, c, S, E, bins, ws, wsb, gx)
         return gx
 
     def grouping_backward(self, grad_y, indices, n):
         _lib.require_cuda(grad_y, indices); _f32(grad_y, "grad_y"); _i32(indices, "indices")
         b, c, m, u = grad_y.shape
-        gx = self._scatter_csr(grad_y, indices, None, m * u, m * u, int(n), "grouping_backward (csr)")
+        gx = self._scatter_csr(grad_y, indices, None, m * u, m * u, int(n))
         if gx is not None:
             return gx
         gx = torch.empty((b, c, n), device=grad_y.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_grouping_backward(
-            _lib.ptr(grad_y), _lib.ptr(indices), b, c, n, m, u, _lib.ptr(gx),
-            _lib.stream_ptr(gx.device)), "grouping_backward")
+        _lib.call("lion_grouping_backward", grad_y, indices, b, c, n, m, u, gx)
         return gx
 
     # -- interpolate/neighbor_interpolate.cpp --------------------------------------------------
@@ -133,10 +116,8 @@ class _HipBackend:
         out = torch.empty((b, c, n), device=dev, dtype=torch.float32)
         idx = torch.empty((b, 3, n), device=dev, dtype=torch.int32)
         wgt = torch.empty((b, 3, n), device=dev, dtype=torch.float32)
-        _lib.check(self.lib.lion_three_nn_interpolate_forward(
-            _lib.ptr(points_coords), _lib.ptr(centers_coords), _lib.ptr(centers_features), b, c, n,
-            m, _lib.ptr(out), _lib.ptr(idx), _lib.ptr(wgt), _lib.stream_ptr(dev)),
-            "three_nearest_neighbors_interpolate_forward")
+        _lib.call("lion_three_nn_interpolate_forward", points_coords, centers_coords, centers_features, b, c, n, m,
+                  out, idx, wgt)
         return out, idx, wgt
 
     def three_nearest_neighbors_interpolate_cat_forward(self, points_coords, centers_coords, centers_features, temb_rows,
@@ -155,23 +136,19 @@ class _HipBackend:
         out = torch.empty((b, c1 + c2 + c3, n), device=dev, dtype=torch.float32)
         idx = torch.empty((b, 3, n), device=dev, dtype=torch.int32)
         wgt = torch.empty((b, 3, n), device=dev, dtype=torch.float32)
-        _lib.check(self.lib.lion_three_nn_interpolate_cat_forward(
-            _lib.ptr(points_coords), _lib.ptr(centers_coords), _lib.ptr(centers_features), _lib.ptr(temb_rows), int(ld_t),
-            _lib.ptr(skip), b, c1, c2, c3, n, m, _lib.ptr(out), _lib.ptr(idx), _lib.ptr(wgt), _lib.stream_ptr(dev)),
-            "three_nearest_neighbors_interpolate_cat_forward")
+        _lib.call("lion_three_nn_interpolate_cat_forward", points_coords, centers_coords, centers_features, temb_rows,
+                  int(ld_t), skip, b, c1, c2, c3, n, m, out, idx, wgt)
         return out, idx, wgt
 
     def three_nearest_neighbors_interpolate_backward(self, grad_y, indices, weights, m):
         _lib.require_cuda(grad_y, indices, weights)
         _f32(grad_y, "grad_y"); _i32(indices, "indices"); _f32(weights, "weights")
         b, c, n = grad_y.shape
-        gx = self._scatter_csr(grad_y, indices, weights, n, 3 * n, int(m), "three_nn_interpolate_backward (csr)")
+        gx = self._scatter_csr(grad_y, indices, weights, n, 3 * n, int(m))
         if gx is not None:
             return gx
         gx = torch.empty((b, c, m), device=grad_y.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_three_nn_interpolate_backward(
-            _lib.ptr(grad_y), _lib.ptr(indices), _lib.ptr(weights), b, c, n, m, _lib.ptr(gx),
-            _lib.stream_ptr(gx.device)), "three_nearest_neighbors_interpolate_backward")
+        _lib.call("lion_three_nn_interpolate_backward", grad_y, indices, weights, b, c, n, m, gx)
         return gx
 
     # -- interpolate/trilinear_devox.cpp:18-55 -------------------------------------------------
@@ -189,11 +166,8 @@ class _HipBackend:
         else:  # the reference returns [1]-shaped placeholders (trilinear_devox.cpp:45-54)
             inds = torch.zeros((1,), device=dev, dtype=torch.int32)
             wgts = torch.zeros((1,), device=dev, dtype=torch.float32)
-        _lib.check(self.lib.lion_trilinear_devoxelize_forward(
-            _lib.ptr(coords), _lib.ptr(features), b, c, n, int(r), int(bool(is_training)),
-            _lib.ptr(outs), _lib.ptr(inds) if is_training else None,
-            _lib.ptr(wgts) if is_training else None, _lib.stream_ptr(dev)),
-            "trilinear_devoxelize_forward")
+        _lib.call("lion_trilinear_devoxelize_forward", coords, features, b, c, n, int(r), int(bool(is_training)), outs,
+                  inds if is_training else None, wgts if is_training else None)
         return outs, inds, wgts
 
     # -- interpolate/trilinear_devox.cpp:67-95 -------------------------------------------------
@@ -205,9 +179,7 @@ class _HipBackend:
         # (the atomics-free path of csrc/scatter_csr.hip is correct here too -- tests/test_scatter_csr_gpu.py -- but slower:
         # 32768 mostly empty bins per sample, 373 us against 198 at (64, 2048, 32), B = 32; K8 and K12-grad use it)
         gx = torch.empty((b, c, r3), device=grad_y.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_trilinear_devoxelize_backward(
-            _lib.ptr(grad_y), _lib.ptr(indices), _lib.ptr(weights), b, c, n, r3, _lib.ptr(gx),
-            _lib.stream_ptr(gx.device)), "trilinear_devoxelize_backward")
+        _lib.call("lion_trilinear_devoxelize_backward", grad_y, indices, weights, b, c, n, r3, gx)
         return gx
 
     # -- voxelization/vox.cpp:17-43 -----------------------------------------------------------
@@ -222,9 +194,7 @@ class _HipBackend:
         cnt = torch.empty((b, r3), device=dev, dtype=torch.int32)
         wsb = self.lib.lion_avg_voxelize_workspace_bytes(b, c, n, r)
         ws = torch.empty((wsb,), device=dev, dtype=torch.uint8)
-        _lib.check(self.lib.lion_avg_voxelize_forward(
-            _lib.ptr(features), _lib.ptr(coords), b, c, n, r, _lib.ptr(out), _lib.ptr(ind),
-            _lib.ptr(cnt), _lib.ptr(ws), wsb, _lib.stream_ptr(dev)), "avg_voxelize_forward")
+        _lib.call("lion_avg_voxelize_forward", features, coords, b, c, n, r, out, ind, cnt, ws, wsb)
         return out, ind, cnt
 
     # -- voxelization/vox.cpp:54-79 -----------------------------------------------------------
@@ -234,9 +204,7 @@ class _HipBackend:
         b, c, s = grad_y.shape
         n = indices.shape[1]
         gx = torch.empty((b, c, n), device=grad_y.device, dtype=torch.float32)
-        _lib.check(self.lib.lion_avg_voxelize_backward(
-            _lib.ptr(grad_y), _lib.ptr(indices), _lib.ptr(cnt), b, c, n, s, _lib.ptr(gx),
-            _lib.stream_ptr(gx.device)), "avg_voxelize_backward")
+        _lib.call("lion_avg_voxelize_backward", grad_y, indices, cnt, b, c, n, s, gx)
         return gx
 
     # -- fused: Voxelization.forward (pvcnn2_ada.py:173-188), not part of the reference module ---
@@ -258,10 +226,8 @@ class _HipBackend:
         cnt = torch.empty((b, r3), device=dev, dtype=torch.int32)
         wsb = self.lib.lion_avg_voxelize_workspace_bytes(b, max(c, 1), n, r)
         ws = torch.empty((wsb,), device=dev, dtype=torch.uint8)
-        _lib.check(self.lib.lion_voxelize_points_forward(
-            _lib.ptr(features), _lib.ptr(coords), b, c, n, r, int(bool(normalize)), float(eps),
-            _lib.ptr(out), _lib.ptr(norm), _lib.ptr(ind), _lib.ptr(cnt), _lib.ptr(ws), wsb,
-            _lib.stream_ptr(dev)), "voxelize_points_forward")
+        _lib.call("lion_voxelize_points_forward", features, coords, b, c, n, r, int(bool(normalize)), float(eps),
+                  out, norm, ind, cnt, ws, wsb)
         return out, norm, ind, cnt
 
     # -- the same in two steps: index plan of (coords, r) once, mean-pool per feature tensor --------------------
@@ -279,9 +245,7 @@ class _HipBackend:
         ind = torch.empty((b, n), device=dev, dtype=torch.int32)
         cnt = torch.empty((b, r * r * r), device=dev, dtype=torch.int32)
         ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
-        _lib.check(self.lib.lion_voxel_index(_lib.ptr(coords), b, n, r, int(bool(normalize)), float(eps), _lib.ptr(norm),
-                                             _lib.ptr(ind), _lib.ptr(cnt), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev)),
-                   "voxel_index")
+        _lib.call("lion_voxel_index", coords, b, n, r, int(bool(normalize)), float(eps), norm, ind, cnt, ws, nbytes)
         return {"norm": norm, "ind": ind, "cnt": cnt, "ws": ws, "shape": (b, n, r)}
 
     def voxel_scatter(self, features, plan, occ_m1=None):
@@ -297,12 +261,9 @@ class _HipBackend:
         out = torch.empty((b, c, r * r * r), device=features.device, dtype=torch.float32)
         ws = plan["ws"]
         if occ_m1 is not None:
-            _lib.check(self.lib.lion_voxel_scatter_read(_lib.ptr(features), _lib.ptr(ws), ws.numel(), b, c, n, r,
-                                                        _lib.ptr(occ_m1), _lib.ptr(out), _lib.stream_ptr(features.device)),
-                       "voxel_scatter_read")
+            _lib.call("lion_voxel_scatter_read", features, ws, ws.numel(), b, c, n, r, occ_m1, out)
             return out
-        _lib.check(self.lib.lion_voxel_scatter(_lib.ptr(features), _lib.ptr(ws), ws.numel(), b, c, n, r, _lib.ptr(out),
-                                               _lib.stream_ptr(features.device)), "voxel_scatter")
+        _lib.call("lion_voxel_scatter", features, ws, ws.numel(), b, c, n, r, out)
         return out
 
 

@@ -2,6 +2,8 @@
 conv -> AdaGN -> Swish -> conv -> AdaGN -> SE3d -> devoxelize with no stand-alone pass over the grid.
 Thin wrappers over lion_conv3d_k3_fused_forward / lion_groupnorm_fold /
 lion_trilinear_devoxelize_affine_forward (include/lion_hip.h)."""
+import os
+
 import torch
 
 from . import _lib
@@ -39,10 +41,7 @@ def conv3d_occupancy(counts, r, cout, b, consumer_aware=False):
     lib = _lib.load()
     n = lib.lion_conv3d_occupancy_ints(r, cout, b)
     buf = torch.empty((2, n), device=counts.device, dtype=torch.int32)
-    cnt_c = counts.contiguous()
-    _lib.check(lib.lion_conv3d_tile_occupancy_aware(_lib.ptr(cnt_c), b, r, cout, _lib.ptr(buf[0]), _lib.ptr(buf[1]),
-                                                    int(consumer_aware), _lib.stream_ptr(counts.device)),
-               "conv3d_tile_occupancy_aware")
+    _lib.call("lion_conv3d_tile_occupancy_aware", counts.contiguous(), b, r, cout, buf[0], buf[1], int(consumer_aware))
     return buf[0], buf[1]
 
 
@@ -94,7 +93,6 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
     x = x.contiguous()
     wp = conv_ops.split_packed_weight(conv.weight) if use_split else packed_weight(conv.weight)
     y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
-    st = _lib.stream_ptr(x.device)
     pa = pb = pbias = tconst = None
     if pro is not None:
         pa, pb = pro[0].contiguous(), pro[1].contiguous()
@@ -107,20 +105,15 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
             ws = border_weight_sums(conv.weight)
             pbias = prev_conv.bias.detach().contiguous() if prev_conv.bias is not None else None
             tconst = torch.empty((b, 27, cout), device=x.device, dtype=torch.float32)
-            _lib.check(lib.lion_conv3d_const_response(_lib.ptr(ws), _lib.ptr(bias), _lib.ptr(pbias), _lib.ptr(pa),
-                                                      _lib.ptr(pb), b, cin, cout, _lib.ptr(tconst), st),
-                       "conv3d_const_response")
+            _lib.call("lion_conv3d_const_response", ws, bias, pbias, pa, pb, b, cin, cout, tconst)
     stats = None
     if want_stats:
         tiles = lib.lion_conv3d_split_stat_tiles(r, cout) if use_split else lib.lion_conv3d_stat_tiles(r, cout, b, int(sparse))
         stats = torch.empty((b, cout, tiles, 2), device=x.device, dtype=torch.float32)
     if not sparse:
         occ = None
-    fwd = lib.lion_conv3d_k3_split_forward if use_split else lib.lion_conv3d_k3_fused_forward
-    _lib.check(fwd(
-        _lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias),
-        b, cin, cout, r, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(pbias), _lib.ptr(tconst), _lib.ptr(y), _lib.ptr(stats),
-        _lib.ptr(occ), st), "conv3d_k3_split_forward" if use_split else "conv3d_k3_fused_forward")
+    _lib.call("lion_conv3d_k3_split_forward" if use_split else "lion_conv3d_k3_fused_forward",
+              x, wp, bias, b, cin, cout, r, pa, pb, pbias, tconst, y, stats, occ)
     if fold is not None:
         return y, fold.apply(stats)
     return y, stats
@@ -133,17 +126,11 @@ def groupnorm_fold(stats, gn: torch.nn.GroupNorm, fac, gbias, voxels):
     Bs = torch.empty_like(A)
     cm = torch.empty_like(A)
     # fac / gbias are normally the two halves of the [B, 2C] style projection: consume them in place
-    # (row stride ld) instead of materialising two contiguous copies per fold.  Every temporary is
-    # kept alive in a local until the launch is enqueued: a temporary created inside the argument
-    # list is freed before the next argument is evaluated and the caching allocator hands the same
-    # block to the next allocation (fac would silently become gbias).
+    # (row stride) instead of materialising two contiguous copies per fold.
     if not (fac.stride(1) == 1 and gbias.stride(1) == 1 and fac.stride(0) == gbias.stride(0) and fac.stride(0) >= c):
         fac, gbias = fac.contiguous(), gbias.contiguous()
-    fac_c, gb_c, ld = fac, gbias, int(fac.stride(0))
-    _lib.check(_lib.load().lion_groupnorm_fold(
-        _lib.ptr(stats), b, c, t, gn.num_groups, int(voxels), _lib.ptr(gn.weight.detach()),
-        _lib.ptr(gn.bias.detach()), _lib.ptr(fac_c), _lib.ptr(gb_c), ld, float(gn.eps),
-        _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(cm), _lib.stream_ptr(stats.device)), "groupnorm_fold")
+    _lib.call("lion_groupnorm_fold", stats, b, c, t, gn.num_groups, int(voxels), gn.weight, gn.bias, fac, gbias,
+              int(fac.stride(0)), float(gn.eps), A, Bs, cm)
     return A, Bs, cm
 
 
@@ -158,11 +145,8 @@ def groupnorm_fold_se(stats, gn: torch.nn.GroupNorm, fac, gbias, voxels, se):
     Bs = torch.empty_like(A)
     if not (fac.stride(1) == 1 and gbias.stride(1) == 1 and fac.stride(0) == gbias.stride(0) and fac.stride(0) >= c):
         fac, gbias = fac.contiguous(), gbias.contiguous()
-    fac_c, gb_c, ld = fac, gbias, int(fac.stride(0))   # kept alive until the launch is enqueued (see groupnorm_fold)
-    _lib.check(_lib.load().lion_groupnorm_fold_se(
-        _lib.ptr(stats), b, c, t, gn.num_groups, int(voxels), _lib.ptr(gn.weight.detach()), _lib.ptr(gn.bias.detach()),
-        _lib.ptr(fac_c), _lib.ptr(gb_c), ld, float(gn.eps), _lib.ptr(w1), _lib.ptr(w2), h, _lib.ptr(A), _lib.ptr(Bs),
-        _lib.stream_ptr(stats.device)), "groupnorm_fold_se")
+    _lib.call("lion_groupnorm_fold_se", stats, b, c, t, gn.num_groups, int(voxels), gn.weight, gn.bias, fac, gbias,
+              int(fac.stride(0)), float(gn.eps), w1, w2, h, A, Bs)
     return A, Bs
 
 
@@ -173,8 +157,7 @@ def se_gate_(A, Bs, chmean, se):
     if c > 1024 or h > 128 or not (w1.is_contiguous() and w2.is_contiguous()):
         gate = se.fc(A * chmean + Bs)
         return A * gate, Bs * gate
-    _lib.check(_lib.load().lion_se_gate(_lib.ptr(chmean), _lib.ptr(w1), _lib.ptr(w2), A.shape[0], c, h,
-                                        _lib.ptr(A), _lib.ptr(Bs), _lib.stream_ptr(A.device)), "se_gate")
+    _lib.call("lion_se_gate", chmean, w1, w2, A.shape[0], c, h, A, Bs)
     return A, Bs
 
 
@@ -188,8 +171,7 @@ def devoxelize_plan(coords, r):
     if nbytes == 0 or not coords.is_contiguous() or coords.dtype != torch.float32:
         return None
     buf = torch.empty((nbytes,), device=coords.device, dtype=torch.uint8)
-    _lib.check(lib.lion_trilinear_devoxelize_plan(_lib.ptr(coords), b, n, int(r), _lib.ptr(buf), nbytes,
-                                                  _lib.stream_ptr(coords.device)), "trilinear_devoxelize_plan")
+    _lib.call("lion_trilinear_devoxelize_plan", coords, b, n, int(r), buf, nbytes)
     return {"buf": buf, "coords": coords, "shape": (b, n, int(r))}
 
 
@@ -202,14 +184,9 @@ def devoxelize_affine(grid, coords, r, scale, shift, plan=None):
     co_c, gr_c, sc_c, sh_c = coords.contiguous(), grid.contiguous(), scale.contiguous(), shift.contiguous()
     if plan is not None and plan["shape"] == (b, n, int(r)) and plan["coords"].data_ptr() == co_c.data_ptr():
         buf = plan["buf"]
-        _lib.check(_lib.load().lion_trilinear_devoxelize_planned_forward(
-            _lib.ptr(buf), buf.numel(), _lib.ptr(co_c), _lib.ptr(gr_c), _lib.ptr(sc_c), _lib.ptr(sh_c), b, c, n, int(r),
-            _lib.ptr(out), _lib.stream_ptr(grid.device)), "trilinear_devoxelize_planned_forward")
+        _lib.call("lion_trilinear_devoxelize_planned_forward", buf, buf.numel(), co_c, gr_c, sc_c, sh_c, b, c, n, int(r), out)
         return out
-    _lib.check(_lib.load().lion_trilinear_devoxelize_affine_forward(
-        _lib.ptr(co_c), _lib.ptr(gr_c), _lib.ptr(sc_c), _lib.ptr(sh_c), b, c, n, int(r), _lib.ptr(out),
-        _lib.stream_ptr(grid.device)),
-        "trilinear_devoxelize_affine_forward")
+    _lib.call("lion_trilinear_devoxelize_affine_forward", co_c, gr_c, sc_c, sh_c, b, c, n, int(r), out)
     return out
 
 
@@ -221,17 +198,11 @@ def fusable(conv1, conv2, r, x):
 
 
 def _pw_pack(weight):
-    cout, cin = weight.shape[:2]
-    lib = _lib.load()
-    wp = torch.empty((lib.lion_pwconv_packed_floats(cout, cin),), device=weight.device, dtype=torch.float32)
-    w_c = weight.detach().reshape(cout, cin).contiguous()
-    _lib.check(lib.lion_pwconv_pack_weights(_lib.ptr(w_c), cout, cin, _lib.ptr(wp),
-                                            _lib.stream_ptr(weight.device)), "pwconv_pack_weights")
-    return wp
+    return conv_ops.pack_with(weight, "lion_pwconv_packed_floats", "lion_pwconv_pack_weights", torch.float32, as_matrix=True)
 
 
 _PW_CACHE = WeightCache(_pw_pack)
-PW_ALL = __import__("os").environ.get("LION_PW_ALL", "1") != "0"
+PW_ALL = os.environ.get("LION_PW_ALL", "1") != "0"
 
 
 def pw_packed_weight(weight):
@@ -240,13 +211,8 @@ def pw_packed_weight(weight):
 
 
 def _pw_split_pack(weight):
-    cout, cin = weight.shape[:2]
-    lib = _lib.load()
-    wp = torch.empty((lib.lion_pwconv_split_packed_halfs(cout, cin),), device=weight.device, dtype=torch.int16)
-    w_c = weight.detach().reshape(cout, cin).contiguous()
-    _lib.check(lib.lion_pwconv_split_pack_weights(_lib.ptr(w_c), cout, cin, _lib.ptr(wp),
-                                                  _lib.stream_ptr(weight.device)), "pwconv_split_pack_weights")
-    return wp
+    return conv_ops.pack_with(weight, "lion_pwconv_split_packed_halfs", "lion_pwconv_split_pack_weights", torch.int16,
+                              as_matrix=True)
 
 
 _PW_SPLIT_CACHE = WeightCache(_pw_split_pack)
@@ -256,7 +222,7 @@ _PW_SPLIT_CACHE = WeightCache(_pw_split_pack)
 # prologue) 106 -> 26, 128->256 196 -> 46, 320->256 L=512 63 -> 27; short activations (B x L < 8192 columns: a handful
 # of workgroups, latency bound) and the long thin ones (L >= 8192 with Cin x Cout < 8192: the fp32 kernel already moves
 # 3.1-3.8 TB/s) stay on the fp32 kernels.
-PW_SPLIT = __import__("os").environ.get("LION_PW_SPLIT", "1") != "0"
+PW_SPLIT = os.environ.get("LION_PW_SPLIT", "1") != "0"
 
 
 def pw_use_split(split, b, cin, cout, L):
@@ -298,10 +264,8 @@ def pwconv_fused(x, conv, pro=None, want_stats=True, split=None):
     if pro is not None:
         pa, pb = pro[0].contiguous(), pro[1].contiguous()
     bias = conv.bias.detach().contiguous() if conv.bias is not None else None
-    fwd = lib.lion_pwconv_split_forward if use_split else lib.lion_pwconv_forward
-    _lib.check(fwd(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias), b, cin, cout, L,
-                   _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(y), _lib.ptr(stats),
-                   _lib.stream_ptr(x.device)), "pwconv_split_forward" if use_split else "pwconv_forward")
+    _lib.call("lion_pwconv_split_forward" if use_split else "lion_pwconv_forward",
+              x, wp, bias, b, cin, cout, L, pa, pb, y, stats)
     return y, stats
 
 
@@ -310,7 +274,7 @@ def pwconv_fused(x, conv, pro=None, want_stats=True, split=None):
 # pass without storing a byte against 121 us with its 268 MB output + 42 us for the max pass (208 vs 163 us; the sampling
 # step is unchanged within noise).  The layer is not bound by its bytes: one wave = 64 loads, one wait, 128 MFMAs, with two
 # workgroups per CU to overlap those phases.  Off by default; LION_PW_MAX_RECOMPUTE=1 selects it (saves the 268 MB tensor).
-MAX_RECOMPUTE = __import__("os").environ.get("LION_PW_MAX_RECOMPUTE", "0") != "0"
+MAX_RECOMPUTE = os.environ.get("LION_PW_MAX_RECOMPUTE", "0") != "0"
 
 
 def pwconv_max_recompute(x, conv, gn, style, pro):
@@ -331,18 +295,13 @@ def pwconv_max_recompute(x, conv, gn, style, pro):
     if pro is not None:
         pa, pb = pro[0].contiguous(), pro[1].contiguous()
     bias = conv.bias.detach().contiguous() if conv.bias is not None else None
-    st = _lib.stream_ptr(x.device)
-    rc = lib.lion_pwconv_forward_max(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias), b, cin, cout, L, _lib.ptr(pa), _lib.ptr(pb),
-                                     None, None, _lib.ptr(stats), None, st)
-    if rc == -2:   # LION_EUNSUPPORTED: the caller takes the stored-output path
-        return None
-    _lib.check(rc, "pwconv_forward_max (sums)")
+    if not _lib.call("lion_pwconv_forward_max", x, wp, bias, b, cin, cout, L, pa, pb, None, None, stats, None,
+                     unsupported_ok=True):   # pass 1: the sums
+        return None   # LION_EUNSUPPORTED: the caller takes the stored-output path
     f, g = gn.affine(style)
     A, Bs, _ = groupnorm_fold(stats, gn.norm, f, g, L)
     y = torch.empty((b, cout, m), device=x.device, dtype=torch.float32)
-    _lib.check(lib.lion_pwconv_forward_max(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias), b, cin, cout, L, _lib.ptr(pa),
-                                           _lib.ptr(pb), _lib.ptr(A), _lib.ptr(Bs), None, _lib.ptr(y), st),
-               "pwconv_forward_max (max)")
+    _lib.call("lion_pwconv_forward_max", x, wp, bias, b, cin, cout, L, pa, pb, A, Bs, None, y)   # pass 2: the max
     return y
 
 
@@ -362,9 +321,7 @@ def pwconv_raw(x, w2d, bias=None, cached_param=None, transposed=False):
     if transposed and use_split and cached_param is not None:
         wf = _PW_SPLIT_CACHE.get(cached_param)
         wp = torch.empty((lib.lion_pwconv_split_packed_halfs(cout, cin),), device=x.device, dtype=torch.int16)
-        w_c = w2d.detach().contiguous()
-        _lib.check(lib.lion_pwconv_split_pack_weights_t(_lib.ptr(w_c), cin, cout, _lib.ptr(wf), _lib.ptr(wp),
-                                                        _lib.stream_ptr(x.device)), "pwconv_split_pack_weights_t")
+        _lib.call("lion_pwconv_split_pack_weights_t", w2d.detach().contiguous(), cin, cout, wf, wp)
     elif transposed:
         wp = (_pw_split_pack if use_split else _pw_pack)(w2d.detach().t().contiguous())
     elif cached_param is not None:
@@ -373,9 +330,8 @@ def pwconv_raw(x, w2d, bias=None, cached_param=None, transposed=False):
         wp = (_pw_split_pack if use_split else _pw_pack)(w2d)
     y = torch.empty((b, cout) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
     bias_c = bias.detach().contiguous() if bias is not None else None
-    fwd = lib.lion_pwconv_split_forward if use_split else lib.lion_pwconv_forward
-    _lib.check(fwd(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias_c), b, cin, cout, L, None, None, _lib.ptr(y), None,
-                   _lib.stream_ptr(x.device)), "pwconv_split_forward" if use_split else "pwconv_forward")
+    _lib.call("lion_pwconv_split_forward" if use_split else "lion_pwconv_forward",
+              x, wp, bias_c, b, cin, cout, L, None, None, y, None)
     return y
 
 
@@ -391,8 +347,7 @@ def pwconv_wgrad(x, gy, want_bias=False):
     ws = torch.empty((wsb,), device=x.device, dtype=torch.uint8)
     gw = torch.empty((cout, cin), device=x.device, dtype=torch.float32)
     gb = torch.empty((cout,), device=x.device, dtype=torch.float32) if want_bias else None
-    _lib.check(lib.lion_pwconv_wgrad(_lib.ptr(x), _lib.ptr(gy), b, cin, cout, L, _lib.ptr(ws), wsb, _lib.ptr(gw), _lib.ptr(gb),
-                                     _lib.stream_ptr(x.device)), "pwconv_wgrad")
+    _lib.call("lion_pwconv_wgrad", x, gy, b, cin, cout, L, ws, wsb, gw, gb)
     return (gw, gb) if want_bias else gw
 
 
@@ -403,26 +358,21 @@ def group_points(coords, centers, feat, idx):
     m, u = idx.shape[1], idx.shape[2]
     c = 0 if feat is None else feat.shape[1]
     out = torch.empty((b, 3 + c, m, u), device=coords.device, dtype=torch.float32)
-    co, ce, ix = coords.contiguous(), centers.contiguous(), idx.contiguous()
-    fe = feat.contiguous() if feat is not None else None
-    _lib.check(_lib.load().lion_group_points_forward(_lib.ptr(co), _lib.ptr(ce), _lib.ptr(fe), _lib.ptr(ix), b, c, n,
-                                                     m, u, _lib.ptr(out), _lib.stream_ptr(coords.device)),
-               "group_points_forward")
+    _lib.call("lion_group_points_forward", coords.contiguous(), centers.contiguous(), None if feat is None else feat.contiguous(),
+              idx.contiguous(), b, c, n, m, u, out)
     return out
 
 
 def linear_rows(x, weight, bias=None, act=0, slope=0.0):
     """nn.Linear on [B, K]: act(x W^T + b) in ONE launch on the fp32 MFMA kernel (lion_linear_forward);
     act 0 none / 1 relu / 2 leaky-relu(slope)."""
-    lib = _lib.load()
     x = x.contiguous()
     b, k = x.shape
     o = weight.shape[0]
     wp = pw_packed_weight(weight)
     y = torch.empty((b, o), device=x.device, dtype=torch.float32)
     bias_c = bias.detach().contiguous() if bias is not None else None
-    _lib.check(lib.lion_linear_forward(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias_c), b, k, o, int(act), float(slope),
-                                       _lib.ptr(y), _lib.stream_ptr(x.device)), "linear_forward")
+    _lib.call("lion_linear_forward", x, wp, bias_c, b, k, o, int(act), float(slope), y)
     return y
 
 
@@ -431,43 +381,36 @@ def linear_attention_core(qkv, heads, dim_head):
     qkv = qkv.contiguous()
     b, n = qkv.shape[0], qkv[0, 0].numel()
     out = torch.empty((b, heads * dim_head) + tuple(qkv.shape[2:]), device=qkv.device, dtype=torch.float32)
-    _lib.check(_lib.load().lion_linear_attention_core(_lib.ptr(qkv), b, heads, dim_head, n, _lib.ptr(out),
-                                                      _lib.stream_ptr(qkv.device)), "linear_attention_core")
+    _lib.call("lion_linear_attention_core", qkv, b, heads, dim_head, n, out)
     return out
 
 
 def row_stats(x):
     """x f32[B, C, ...] -> f32[B*C, 2]: per (batch, channel) row the sum and the sum of squares (one streaming pass)"""
-    lib = _lib.load()
     x = x.contiguous()
     rows = x.shape[0] * x.shape[1]
     stats = torch.empty((rows, 2), device=x.device, dtype=torch.float32)
-    _lib.check(lib.lion_row_stats(_lib.ptr(x), rows, x[0, 0].numel(), _lib.ptr(stats), _lib.stream_ptr(x.device)), "row_stats")
+    _lib.call("lion_row_stats", x, rows, x[0, 0].numel(), stats)
     return stats
 
 
 def affine_swish(x, A, Bs, reduce_max=False, add=None):
     """swish(x*A+Bs) per (batch, channel) row; reduce_max: max over the last (neighbour) dimension too; add: a tensor of
     the output's shape summed onto the result in the same pass."""
-    lib = _lib.load()
     b, c = x.shape[:2]
-    st = _lib.stream_ptr(x.device)
     if add is not None and not reduce_max:
         add = add.contiguous()
         assert add.shape == x.shape and add.dtype == torch.float32
         y = torch.empty_like(x)
-        _lib.check(lib.lion_affine_swish_add(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(add), b * c, x[0, 0].numel(),
-                                             _lib.ptr(y), st), "affine_swish_add")
+        _lib.call("lion_affine_swish_add", x, A, Bs, add, b * c, x[0, 0].numel(), y)
         return y
     if reduce_max:
         m, u = x.shape[2], x.shape[3]
         y = torch.empty((b, c, m), device=x.device, dtype=torch.float32)
-        _lib.check(lib.lion_affine_swish_max(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), b * c, m, u, _lib.ptr(y), st),
-                   "affine_swish_max")
+        _lib.call("lion_affine_swish_max", x, A, Bs, b * c, m, u, y)
         return y
     y = torch.empty_like(x)
-    _lib.check(lib.lion_affine_swish(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), b * c, x[0, 0].numel(), _lib.ptr(y), st),
-               "affine_swish")
+    _lib.call("lion_affine_swish", x, A, Bs, b * c, x[0, 0].numel(), y)
     return y
 
 
@@ -477,7 +420,6 @@ def shared_mlp(x, convs, adagns, style, reduce_max=False, add=None):
     emits its own GroupNorm sums -- one read and one write per layer instead of five passes.  Short
     activations keep the library GEMM (+ one row-sum pass).  Only the last layer needs a stand-alone
     apply pass (optionally with the max over the neighbourhood)."""
-    lib = _lib.load()
     pro = None
     for li, (conv, gn) in enumerate(zip(convs, adagns)):
         if (MAX_RECOMPUTE and reduce_max and add is None and li == len(convs) - 1 and x.dim() == 4 and x.shape[3] == 32
@@ -492,10 +434,7 @@ def shared_mlp(x, convs, adagns, style, reduce_max=False, add=None):
             if pro is not None:
                 x = affine_swish(x, pro[0], pro[1])
             x = conv(x).contiguous()
-            b, c = x.shape[:2]
-            st = torch.empty((b, c, 1, 2), device=x.device, dtype=torch.float32)
-            _lib.check(lib.lion_row_stats(_lib.ptr(x), b * c, x[0, 0].numel(), _lib.ptr(st),
-                                          _lib.stream_ptr(x.device)), "row_stats")
+            st = row_stats(x).view(x.shape[0], x.shape[1], 1, 2)
         f, g = gn.affine(style)
         A, Bs, _ = groupnorm_fold(st, gn.norm, f, g, x[0, 0].numel())
         pro = (A, Bs)
@@ -506,24 +445,11 @@ def shared_mlp(x, convs, adagns, style, reduce_max=False, add=None):
 def adagn_swish(x, adagn, style, reduce_max=False):
     """swish(AdaGN(x)) for a 1-D [B,C,N] / 2-D [B,C,M,U] activation in 3 launches (row sums, fold,
     apply); reduce_max=True additionally takes the max over the last (neighbour) dimension."""
-    lib = _lib.load()
     x = x.contiguous()
-    b, c = x.shape[:2]
-    L = x[0, 0].numel()
-    stats = torch.empty((b, c, 1, 2), device=x.device, dtype=torch.float32)
-    st = _lib.stream_ptr(x.device)
-    _lib.check(lib.lion_row_stats(_lib.ptr(x), b * c, L, _lib.ptr(stats), st), "row_stats")
+    stats = row_stats(x).view(x.shape[0], x.shape[1], 1, 2)
     f, g = adagn.affine(style)
-    A, Bs, _ = groupnorm_fold(stats, adagn.norm, f, g, L)
-    if reduce_max:
-        m, u = x.shape[2], x.shape[3]
-        y = torch.empty((b, c, m), device=x.device, dtype=torch.float32)
-        _lib.check(lib.lion_affine_swish_max(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), b * c, m, u, _lib.ptr(y), st),
-                   "affine_swish_max")
-        return y
-    y = torch.empty_like(x)
-    _lib.check(lib.lion_affine_swish(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), b * c, L, _lib.ptr(y), st), "affine_swish")
-    return y
+    A, Bs, _ = groupnorm_fold(stats, adagn.norm, f, g, x[0, 0].numel())
+    return affine_swish(x, A, Bs, reduce_max)
 
 
 # ---- round 6: layout / concatenation passes of a denoiser forward on this library's kernels (no ATen copy in a captured step) --
@@ -541,11 +467,9 @@ def latent_unpack(x, n_points, d, want_all=True, want_coords=True, want_rest=Tru
     """x [B, N*D(,1,1)] point-major latent -> (all [B,D,N], coords [B,3,N], rest [B,D-3,N]) channel-major, one launch
     (was: view + permute + contiguous, slice + contiguous twice -- three ATen copies per step)."""
     b = x.shape[0]
-    xc = x.contiguous()
     mk = lambda c, want: torch.empty((b, c, n_points), device=x.device, dtype=torch.float32) if want and c > 0 else None
     al, co, re = mk(d, want_all), mk(3, want_coords), mk(d - 3, want_rest)
-    _lib.check(_lib.load().lion_latent_unpack(_lib.ptr(xc), b, n_points, d, _lib.ptr(al), _lib.ptr(co), _lib.ptr(re),
-                                              _lib.stream_ptr(x.device)), "latent_unpack")
+    _lib.call("lion_latent_unpack", x.contiguous(), b, n_points, d, al, co, re)
     return al, co, re
 
 
@@ -560,12 +484,8 @@ def concat_broadcast(a, temb):
     b, ca, n = a.shape
     ct = rows.shape[1]
     out = torch.empty((b, ca + ct, n), device=a.device, dtype=torch.float32)
-    rc = _lib.load().lion_concat_broadcast(_lib.ptr(a), _lib.ptr(rows), b, ca, ct, n, ld, _lib.ptr(out),
-                                           _lib.stream_ptr(a.device))
-    if rc == -2:      # LION_EUNSUPPORTED (more than 65535 (sample, channel) rows): the caller's torch.cat
-        return None
-    _lib.check(rc, "concat_broadcast")
-    return out
+    # LION_EUNSUPPORTED (more than 65535 (sample, channel) rows): the caller's torch.cat
+    return out if _lib.call("lion_concat_broadcast", a, rows, b, ca, ct, n, ld, out, unsupported_ok=True) else None
 
 
 def three_nn_interpolate_cat(points, centers, cfeat, temb, skip):
@@ -614,8 +534,7 @@ def to_channel_major_pair(x, t):
     nb = (b + 31) // 32
     ox = torch.empty((nb, vx.shape[1], 32), device=x.device, dtype=torch.float32)
     ot = torch.empty((nb, vt.shape[1], 32), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().lion_to_channel_major(_lib.ptr(vx), ldx, vx.shape[1], _lib.ptr(ox), _lib.ptr(vt), ldt, vt.shape[1],
-                                                 _lib.ptr(ot), b, _lib.stream_ptr(x.device)), "to_channel_major")
+    _lib.call("lion_to_channel_major", vx, ldx, vx.shape[1], ox, vt, ldt, vt.shape[1], ot, b)
     return ox, ot
 
 
@@ -633,19 +552,13 @@ def from_channel_major(xt, b):
     nb, c, _ = xt.shape
     if xt.is_cuda and xt.dtype == torch.float32 and xt.is_contiguous() and not torch.is_grad_enabled():
         y = torch.empty((b, c, 1, 1), device=xt.device, dtype=torch.float32)
-        _lib.check(_lib.load().lion_from_channel_major(_lib.ptr(xt), b, c, _lib.ptr(y), _lib.stream_ptr(xt.device)),
-                   "from_channel_major")
+        _lib.call("lion_from_channel_major", xt, b, c, y)
         return y
     return xt.transpose(1, 2).reshape(nb * 32, c)[:b].reshape(b, c, 1, 1).contiguous()
 
 
 def _sk_pack(weight):
-    cout, cin = weight.shape[:2]
-    wp = torch.empty((_lib.load().lion_skinny_packed_floats(cout, cin),), device=weight.device, dtype=torch.float32)
-    w_c = weight.detach().reshape(cout, cin).contiguous()
-    _lib.check(_lib.load().lion_skinny_pack_weights(_lib.ptr(w_c), cout, cin, _lib.ptr(wp),
-                                                    _lib.stream_ptr(weight.device)), "skinny_pack_weights")
-    return wp
+    return conv_ops.pack_with(weight, "lion_skinny_packed_floats", "lion_skinny_pack_weights", torch.float32, as_matrix=True)
 
 
 _SK_CACHE = WeightCache(_sk_pack)
@@ -667,8 +580,7 @@ def skinny_conv(pin, conv, bias_in=None, act_in=0, add=None):
     cout = conv.out_channels
     wp = skinny_packed_weight(conv.weight)
     out = torch.empty((lib.lion_skinny_splits(cin, cout), nb, cout, 32), device=pin.device, dtype=torch.float32)
-    _lib.check(lib.lion_skinny_gemm(_lib.ptr(pin), ks_in, _lib.ptr(bias_in), int(act_in), _lib.ptr(add), _lib.ptr(wp),
-                                    nb, cin, cout, _lib.ptr(out), _lib.stream_ptr(pin.device)), "skinny_gemm")
+    _lib.call("lion_skinny_gemm", pin, ks_in, bias_in, int(act_in), add, wp, nb, cin, cout, out)
     return out
 
 
@@ -684,9 +596,7 @@ def skinny_conv_se_finish(pin, conv, A, bias_a, resid, act_in=1):
         return None
     wp = skinny_packed_weight(conv.weight)
     y = torch.empty((nb, cout, 32), device=pin.device, dtype=torch.float32)
-    _lib.check(lib.lion_skinny_gemm_se_finish(_lib.ptr(pin), ks_in, None, int(act_in), _lib.ptr(wp), nb, cin, cout, _lib.ptr(A),
-                                              A.shape[0], _lib.ptr(bias_a), _lib.ptr(resid), _lib.ptr(y),
-                                              _lib.stream_ptr(pin.device)), "skinny_gemm_se_finish")
+    _lib.call("lion_skinny_gemm_se_finish", pin, ks_in, None, int(act_in), wp, nb, cin, cout, A, A.shape[0], bias_a, resid, y)
     return y
 
 
@@ -694,8 +604,5 @@ def skinny_finish(A, bias_a, Bp=None, resid=None):
     """[nb, C, 32] from partials: sum A + bias_a (Bp None) or resid + relu(sum A + bias_a) * sigmoid(sum Bp)."""
     ks_a, nb, c, _ = A.shape
     y = torch.empty((nb, c, 32), device=A.device, dtype=torch.float32)
-    _lib.check(_lib.load().lion_skinny_finish(_lib.ptr(A), ks_a, _lib.ptr(bias_a), _lib.ptr(Bp),
-                                              0 if Bp is None else Bp.shape[0], _lib.ptr(resid), nb, c,
-                                              0 if Bp is None else 1, _lib.ptr(y), _lib.stream_ptr(A.device)),
-               "skinny_finish")
+    _lib.call("lion_skinny_finish", A, ks_a, bias_a, Bp, 0 if Bp is None else Bp.shape[0], resid, nb, c, 0 if Bp is None else 1, y)
     return y

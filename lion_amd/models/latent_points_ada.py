@@ -85,10 +85,8 @@ class PVCNN2Unet(nn.Module):
             from .. import _lib
             B = timesteps.shape[0]
             emb = torch.empty(B, self.embed_dim, device=timesteps.device, dtype=torch.float32)
-            tc = timesteps.contiguous()
-            _lib.check(_lib.load().lion_timestep_embedding(_lib.ptr(tc), _lib.ptr(row), float(self.time_emb_scales), B,
-                                                           self.embed_dim // 2, self.embed_dim, _lib.ptr(emb),
-                                                           _lib.stream_ptr(timesteps.device)), "timestep_embedding")
+            _lib.call("lion_timestep_embedding", timesteps.contiguous(), row, float(self.time_emb_scales), B,
+                      self.embed_dim // 2, self.embed_dim, emb)
             return emb
         ang = (timesteps * self.time_emb_scales).unsqueeze(1) * row.unsqueeze(0)
         emb = torch.cat((ang.sin(), ang.cos()), dim=1)

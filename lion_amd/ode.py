@@ -53,10 +53,9 @@ class OdeState:
 
     def __init__(self, n, B, device, x32=None, t_model=None):
         self.n, self.B, self.device = int(n), int(B), torch.device(device)
-        lib = self.lib = _lib.load()
         self.Y = torch.zeros(2, self.n, dtype=torch.float64, device=self.device)
         self.K = torch.zeros(7, self.n, dtype=torch.float64, device=self.device)
-        self.partials = torch.zeros(max(1, lib.lion_ode_partials_bytes(self.n) // 8), dtype=torch.float64,
+        self.partials = torch.zeros(max(1, _lib.load().lion_ode_partials_bytes(self.n) // 8), dtype=torch.float64,
                                     device=self.device)
         self.ctrl = torch.zeros(_CTRL.size, dtype=torch.uint8, device=self.device)
         self.host = torch.zeros(_CTRL.size, dtype=torch.uint8).pin_memory()
@@ -73,25 +72,18 @@ class OdeState:
         self.ctrl.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8), non_blocking=False)
 
     def stage(self, x32=None, t_model=None):
-        st = _lib.stream_ptr(self.device)
-        _lib.check(self.lib.lion_ode_stage(_lib.ptr(self.Y), _lib.ptr(self.K), self.n, _lib.ptr(self.ctrl),
-                                           _lib.ptr(self.x32 if x32 is None else x32),
-                                           _lib.ptr(self.t_model if t_model is None else t_model), self.B, st),
-                   "ode_stage")
+        _lib.call("lion_ode_stage", self.Y, self.K, self.n, self.ctrl, self.x32 if x32 is None else x32,
+                  self.t_model if t_model is None else t_model, self.B)
 
     def drift(self, eps, sched, mix=None, cm_points=0, x32=None, t_model=None):
         eps = eps.float().contiguous()
         a, b = (None, None) if mix is None else mix
-        _lib.check(self.lib.lion_ode_drift(_lib.ptr(eps), int(cm_points), _lib.ptr(self.x32 if x32 is None else x32),
-                                           self.n, _lib.ptr(self.t_model if t_model is None else t_model), *sched,
-                                           _lib.ptr(a), _lib.ptr(b), 0 if a is None else a.numel(), _lib.ptr(self.K),
-                                           _lib.ptr(self.ctrl), _lib.stream_ptr(self.device)), "ode_drift")
+        _lib.call("lion_ode_drift", eps, int(cm_points), self.x32 if x32 is None else x32, self.n,
+                  self.t_model if t_model is None else t_model, *sched, a, b, 0 if a is None else a.numel(), self.K, self.ctrl)
 
     def control(self):
-        st = _lib.stream_ptr(self.device)
-        _lib.check(self.lib.lion_ode_error_partials(_lib.ptr(self.Y), _lib.ptr(self.K), self.n, _lib.ptr(self.ctrl),
-                                                    _lib.ptr(self.partials), st), "ode_error_partials")
-        _lib.check(self.lib.lion_ode_control(_lib.ptr(self.partials), self.n, _lib.ptr(self.ctrl), st), "ode_control")
+        _lib.call("lion_ode_error_partials", self.Y, self.K, self.n, self.ctrl, self.partials)
+        _lib.call("lion_ode_control", self.partials, self.n, self.ctrl)
 
     def read(self) -> dict:
         """the host's one synchronisation per attempted step: async copy to pinned memory + one event wait"""

@@ -106,7 +106,6 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -138,7 +137,6 @@ class Adam(torch.optim.Optimizer):
                     st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
             plan = self._plan(gi, ps, grads, dev)
             b1, b2 = group["betas"]
-            _lib.check(lib.lion_adam_step(_lib.ptr(plan.table), _lib.ptr(plan.numel), _lib.ptr(plan.blockmap), plan.blocks,
-                                          len(ps), _lib.ptr(self._lr(gi, group, dev)), float(b1), float(b2), float(group["eps"]),
-                                          float(group["weight_decay"]), self.ema_decay, _lib.stream_ptr(dev)), "adam_step")
+            _lib.call("lion_adam_step", plan.table, plan.numel, plan.blockmap, plan.blocks, len(ps), self._lr(gi, group, dev),
+                      float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), self.ema_decay)
         return loss

@@ -65,8 +65,7 @@ def _param_grads(pw, want_w, want_b, want_dxs=False):
     B, C = pw.shape[:2]
     dgw, dgb = torch.empty(C, device=pw.device, dtype=torch.float32), torch.empty(C, device=pw.device, dtype=torch.float32)
     dxs = torch.empty(C, device=pw.device, dtype=torch.float32) if want_dxs else None
-    _lib.check(_lib.load().lion_gn_train_param_grads(_lib.ptr(pw), B, C, _lib.ptr(dgw), _lib.ptr(dgb), _lib.ptr(dxs),
-                                                     _lib.stream_ptr(pw.device)), "gn_train_param_grads")
+    _lib.call("lion_gn_train_param_grads", pw, B, C, dgw, dgb, dxs)
     return (dgw if want_w else None), (dgb if want_b else None), dxs
 
 
@@ -129,35 +128,87 @@ def tagged_channel_sum(g, channels):
     return tag[0]
 
 
+def _fold_head(x, gw, gb, factor, bias, groups, eps):
+    """the forward head the AdaGN ops share: double row sums of x (contiguous), the factor / bias row views and the GroupNorm fold
+    -> (stats f64 [B*C, 2], A, Bs, mean, rstd [B, C], contiguous norm weight, norm bias, factor row view | None, its row stride)"""
+    B, C = x.shape[:2]
+    L = x[0, 0].numel()
+    dev = x.device
+    stats = torch.empty(B * C, 2, device=dev, dtype=torch.float64)   # shifted sums, double hand-over (csrc/norm_train.hip)
+    _lib.call("lion_row_stats64", x, B * C, L, stats)
+    A, Bs, mean, rstd = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
+    gwc, gbc = gw.detach().float().contiguous(), gb.detach().float().contiguous()
+    f, fs = _rowview(factor.detach(), B, C) if factor is not None else (None, 0)
+    bb, bs = _rowview(bias.detach(), B, C) if bias is not None else (None, 0)
+    _lib.call("lion_gn_train_fold64", stats, gwc, gbc, f, fs, bb, bs, B, C, groups, L, eps, A, Bs, mean, rstd)
+    return stats, A, Bs, mean, rstd, gwc, gbc, f, fs
+
+
+def _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A=None, stats=None, g=None, Qse=None):
+    """the GroupNorm backward's [B, C] algebra from the row sums S -> (Q, R, d factor, d bias, pw for _param_grads, Aout);
+    g / Qse (the SE gate and its gradient term, _AdaGNSE / _AdaGNSEDevox) fold the gate in and give Aout = A g, else None"""
+    B, C = mean.shape
+    dev = mean.device
+    Q, R = torch.empty(B, C, device=dev, dtype=torch.float32), torch.empty(B, C, device=dev, dtype=torch.float32)
+    Aout = torch.empty(B, C, device=dev, dtype=torch.float32) if g is not None else None
+    dfac, dbias, dstride = _affine_grad_buffers(B, C, has_f, has_b, dev)
+    pw = torch.empty(B, C, 3, device=dev, dtype=torch.float32)
+    _lib.call("lion_gn_train_bwd_fold", S, mean, rstd, gwc, gbc, f if has_f else None, fs, B, C, groups, L, Q, R, dfac, dbias,
+              dstride, pw, A, stats, g, Qse, Aout)
+    return Q, R, dfac, dbias, pw, Aout
+
+
+def _se_gate_fwd(stats, A, Bs, w1, w2, L):
+    """the SE gate from the folded scalars (mean(u) = A mean(x) + Bs) -> (contiguous w1, w2, um, h, g, A2 = g A, B2 = g Bs)"""
+    B, C = A.shape
+    dev = A.device
+    w1c, w2c = w1.detach().float().contiguous(), w2.detach().float().contiguous()
+    Cr = w1c.shape[0]
+    um, g, A2, B2 = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
+    h = torch.empty(B, Cr, device=dev, dtype=torch.float32)
+    _lib.call("lion_gn_se_gate_fwd", stats, A, Bs, w1c, w2c, B, C, Cr, L, um, h, g, A2, B2)
+    return w1c, w2c, um, h, g, A2, B2
+
+
+def _se_gate_bwd(S, stats, A, Bs, g, h, um, w1, w2, L):
+    """the gate's backward from S = {sum gy, sum gy x} -> (Sp: the row sums of du = g gy + Qse, Qse, d w1, d w2)"""
+    B, C = A.shape
+    dev = A.device
+    Cr = w1.shape[0]
+    Sp = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
+    dpre2, Qse = torch.empty(B, C, device=dev, dtype=torch.float32), torch.empty(B, C, device=dev, dtype=torch.float32)
+    dpre1 = torch.empty(B, Cr, device=dev, dtype=torch.float32)
+    dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+    _lib.call("lion_gn_se_gate_bwd", S, stats, A, Bs, g, h, um, w1, w2, B, C, Cr, L, Sp, dpre2, dpre1, Qse, dw1, dw2)
+    return Sp, Qse, dw1, dw2
+
+
+def _unbroadcast(g, shape):
+    """the gradient of a broadcast factor / bias: summed over exactly the dimensions it was spread over"""
+    shape = tuple(int(d) for d in shape)
+    core = shape
+    while len(core) > 2 and core[-1] == 1:
+        core = core[:-1]
+    return g.sum_to_size(core if core else (1,)).reshape(shape)
+
+
 class _AdaGNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gw, gb, factor, bias, groups, eps, act, drop_p=0.0):
-        lib = _lib.load()
         x = x.contiguous()
         B, C = x.shape[:2]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        stats = torch.empty(B * C, 2, device=dev, dtype=torch.float64)   # shifted sums, double hand-over (csrc/norm_train.hip)
-        _lib.check(lib.lion_row_stats64(_lib.ptr(x), B * C, L, _lib.ptr(stats), st), "row_stats64")
-        A, Bs, mean, rstd = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
-        gwc, gbc = gw.detach().float().contiguous(), gb.detach().float().contiguous()
-        f, fs = _rowview(factor.detach(), B, C) if factor is not None else (None, 0)
-        bb, bs = _rowview(bias.detach(), B, C) if bias is not None else (None, 0)
-        _lib.check(lib.lion_gn_train_fold64(_lib.ptr(stats), _lib.ptr(gwc), _lib.ptr(gbc), _lib.ptr(f), fs, _lib.ptr(bb), bs,
-                                          B, C, groups, L, eps, _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(mean), _lib.ptr(rstd),
-                                            st), "gn_train_fold64")
+        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
         y = torch.empty_like(x)
         keep = 1.0 - float(drop_p)
         if drop_p > 0.0:
             # nn.Dropout behind the activation, in the same pass: the mask comes from a seed torch's generator draws on the device
             # (a replayed graph draws a new one) and is regenerated by the backward passes -- it is never stored
-            seed = torch.empty(1, device=dev, dtype=torch.int64).random_()
-            _lib.check(lib.lion_affine_act_dropout(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), B * C, L, int(act), _lib.ptr(seed), keep,
-                                                   _lib.ptr(y), st), "affine_act_dropout")
+            seed = torch.empty(1, device=x.device, dtype=torch.int64).random_()
+            _lib.call("lion_affine_act_dropout", x, A, Bs, B * C, L, int(act), seed, keep, y)
         else:
             seed = x.new_empty(0)
-            _lib.check(lib.lion_affine_act(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), B * C, L, int(act), _lib.ptr(y), st), "affine_act")
+            _lib.call("lion_affine_act", x, A, Bs, B * C, L, int(act), y)
         ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0), seed, stats)
         ctx.meta = (groups, int(act), factor is not None, bias is not None, fs,
                     None if factor is None else factor.shape, None if bias is None else bias.shape, keep)
@@ -166,51 +217,31 @@ class _AdaGNAct(torch.autograd.Function):
     @staticmethod
     @once_differentiable   # raw kernels: a double backward must raise, not silently treat these gradients as constants
     def backward(ctx, gy):
-        lib = _lib.load()
         x, A, Bs, mean, rstd, gwc, gbc, f, seed, stats = ctx.saved_tensors
         groups, act, has_f, has_b, fs, f_shape, b_shape, keep = ctx.meta
         drop = seed.numel() > 0
         gy = gy.contiguous()
         B, C = x.shape[:2]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        S = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
+        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
         if drop:
-            _lib.check(lib.lion_affine_act_dropout_bwd_stats(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), B * C, L, act,
-                                                             _lib.ptr(seed), keep, _lib.ptr(S), st), "affine_act_dropout_bwd_stats")
+            _lib.call("lion_affine_act_dropout_bwd_stats", x, gy, A, Bs, B * C, L, act, seed, keep, S)
         else:
-            _lib.check(lib.lion_affine_act_bwd_stats(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), B * C, L, act,
-                                                     _lib.ptr(S), st), "affine_act_bwd_stats")
-        Q, R = torch.empty(B, C, device=dev, dtype=torch.float32), torch.empty(B, C, device=dev, dtype=torch.float32)
-        dfac, dbias, dstride = _affine_grad_buffers(B, C, has_f, has_b, dev)
-        pw = torch.empty(B, C, 3, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_gn_train_bwd_fold(_lib.ptr(S), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gwc), _lib.ptr(gbc),
-                                              _lib.ptr(f) if has_f else None, fs, B, C, groups, L, _lib.ptr(Q), _lib.ptr(R),
-                                              _lib.ptr(dfac), _lib.ptr(dbias), dstride, _lib.ptr(pw), _lib.ptr(A), _lib.ptr(stats),
-                                              None, None, None, st), "gn_train_bwd_fold")
+            _lib.call("lion_affine_act_bwd_stats", x, gy, A, Bs, B * C, L, act, S)
+        Q, R, dfac, dbias, pw, _ = _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A, stats)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             if drop:
-                _lib.check(lib.lion_affine_act_dropout_bwd_apply(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(Q),
-                                                                 _lib.ptr(R), B * C, L, act, _lib.ptr(seed), keep, _lib.ptr(dx), st),
-                           "affine_act_dropout_bwd_apply")
+                _lib.call("lion_affine_act_dropout_bwd_apply", x, gy, A, Bs, Q, R, B * C, L, act, seed, keep, dx)
             else:
-                _lib.check(lib.lion_affine_act_bwd_apply(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(Q),
-                                                         _lib.ptr(R), B * C, L, act, _lib.ptr(dx), st), "affine_act_bwd_apply")
+                _lib.call("lion_affine_act_bwd_apply", x, gy, A, Bs, Q, R, B * C, L, act, dx)
         # d norm.weight, d norm.bias; for a voxel grid also the sum of dx per channel = the bias gradient of the Conv3d in front
         dgw, dgb, dxs = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], dx is not None and x.dim() == 5)
         if dxs is not None:
             tag_channel_sum(dx, dxs)
-        def back(g, shape):   # the gradient of a broadcast factor: summed over exactly the dimensions it was spread over
-            shape = tuple(int(d) for d in shape)
-            core = shape
-            while len(core) > 2 and core[-1] == 1:
-                core = core[:-1]
-            return g.sum_to_size(core if core else (1,)).reshape(shape)
-        dfac = back(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = back(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
+        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
+        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
         return dx, dgw, dgb, dfac, dbias, None, None, None, None
 
 
@@ -222,24 +253,11 @@ class _AdaGNActMax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gw, gb, factor, bias, groups, eps, act):
-        lib = _lib.load()
         x = x.contiguous()
         B, C, M, U = x.shape
-        L = M * U
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        stats = torch.empty(B * C, 2, device=dev, dtype=torch.float64)
-        _lib.check(lib.lion_row_stats64(_lib.ptr(x), B * C, L, _lib.ptr(stats), st), "row_stats64")
-        A, Bs, mean, rstd = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
-        gwc, gbc = gw.detach().float().contiguous(), gb.detach().float().contiguous()
-        f, fs = _rowview(factor.detach(), B, C) if factor is not None else (None, 0)
-        bb, bs = _rowview(bias.detach(), B, C) if bias is not None else (None, 0)
-        _lib.check(lib.lion_gn_train_fold64(_lib.ptr(stats), _lib.ptr(gwc), _lib.ptr(gbc), _lib.ptr(f), fs, _lib.ptr(bb), bs,
-                                            B, C, groups, L, eps, _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(mean), _lib.ptr(rstd),
-                                            st), "gn_train_fold64")
-        y = torch.empty(B, C, M, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_affine_act_max(_lib.ptr(x), _lib.ptr(A), _lib.ptr(Bs), B * C, M, U, int(act), _lib.ptr(y), st),
-                   "affine_act_max")
+        _, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
+        y = torch.empty(B, C, M, device=x.device, dtype=torch.float32)
+        _lib.call("lion_affine_act_max", x, A, Bs, B * C, M, U, int(act), y)
         ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0))
         ctx.meta = (groups, int(act), factor is not None, bias is not None, fs,
                     None if factor is None else factor.shape, None if bias is None else bias.shape)
@@ -248,40 +266,20 @@ class _AdaGNActMax(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        lib = _lib.load()
         x, A, Bs, mean, rstd, gwc, gbc, f = ctx.saved_tensors
         groups, act, has_f, has_b, fs, f_shape, b_shape = ctx.meta
         gy = gy.contiguous()
         B, C, M, U = x.shape
-        L = M * U
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        S = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_affine_act_max_bwd_stats(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), B * C, M, U, act,
-                                                     _lib.ptr(S), st), "affine_act_max_bwd_stats")
-        Q, R = torch.empty(B, C, device=dev, dtype=torch.float32), torch.empty(B, C, device=dev, dtype=torch.float32)
-        dfac, dbias, dstride = _affine_grad_buffers(B, C, has_f, has_b, dev)
-        pw = torch.empty(B, C, 3, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_gn_train_bwd_fold(_lib.ptr(S), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gwc), _lib.ptr(gbc),
-                                              _lib.ptr(f) if has_f else None, fs, B, C, groups, L, _lib.ptr(Q), _lib.ptr(R),
-                                              _lib.ptr(dfac), _lib.ptr(dbias), dstride, _lib.ptr(pw), None, None, None, None, None,
-                                              st), "gn_train_bwd_fold")
+        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
+        _lib.call("lion_affine_act_max_bwd_stats", x, gy, A, Bs, B * C, M, U, act, S)
+        Q, R, dfac, dbias, pw, _ = _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, M * U)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(lib.lion_affine_act_max_bwd_apply(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(Q),
-                                                         _lib.ptr(R), B * C, M, U, act, _lib.ptr(dx), st),
-                       "affine_act_max_bwd_apply")
+            _lib.call("lion_affine_act_max_bwd_apply", x, gy, A, Bs, Q, R, B * C, M, U, act, dx)
         dgw, dgb, _ = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2])   # d norm.weight, d norm.bias
-
-        def back(g, shape):
-            shape = tuple(int(d) for d in shape)
-            core = shape
-            while len(core) > 2 and core[-1] == 1:
-                core = core[:-1]
-            return g.sum_to_size(core if core else (1,)).reshape(shape)
-        dfac = back(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = back(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
+        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
+        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
         return dx, dgw, dgb, dfac, dbias, None, None, None
 
 
@@ -322,29 +320,13 @@ class _AdaGNSE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gw, gb, factor, bias, w1, w2, groups, eps):
-        lib = _lib.load()
         x = x.contiguous()
         B, C = x.shape[:2]
-        Cr = w1.shape[0]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        stats = torch.empty(B * C, 2, device=dev, dtype=torch.float64)
-        _lib.check(lib.lion_row_stats64(_lib.ptr(x), B * C, L, _lib.ptr(stats), st), "row_stats64")
-        A, Bs, mean, rstd = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
-        gwc, gbc = gw.detach().float().contiguous(), gb.detach().float().contiguous()
-        f, fs = _rowview(factor.detach(), B, C) if factor is not None else (None, 0)
-        bb, bs = _rowview(bias.detach(), B, C) if bias is not None else (None, 0)
-        _lib.check(lib.lion_gn_train_fold64(_lib.ptr(stats), _lib.ptr(gwc), _lib.ptr(gbc), _lib.ptr(f), fs, _lib.ptr(bb), bs,
-                                            B, C, groups, L, eps, _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(mean), _lib.ptr(rstd),
-                                            st), "gn_train_fold64")
-        w1c, w2c = w1.detach().float().contiguous(), w2.detach().float().contiguous()
-        um, g, A2, B2 = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
-        h = torch.empty(B, Cr, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_gn_se_gate_fwd(_lib.ptr(stats), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(w1c), _lib.ptr(w2c), B, C, Cr, L,
-                                           _lib.ptr(um), _lib.ptr(h), _lib.ptr(g), _lib.ptr(A2), _lib.ptr(B2), st), "gn_se_gate_fwd")
+        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
+        w1c, w2c, um, h, g, A2, B2 = _se_gate_fwd(stats, A, Bs, w1, w2, L)
         y = torch.empty_like(x)
-        _lib.check(lib.lion_affine_act(_lib.ptr(x), _lib.ptr(A2), _lib.ptr(B2), B * C, L, 0, _lib.ptr(y), st), "affine_act")
+        _lib.call("lion_affine_act", x, A2, B2, B * C, L, 0, y)
         ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0), stats, um, h, g, w1c, w2c)
         ctx.meta = (groups, factor is not None, bias is not None, fs,
                     None if factor is None else factor.shape, None if bias is None else bias.shape)
@@ -353,49 +335,24 @@ class _AdaGNSE(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        lib = _lib.load()
         x, A, Bs, mean, rstd, gwc, gbc, f, stats, um, h, g, w1, w2 = ctx.saved_tensors
         groups, has_f, has_b, fs, f_shape, b_shape = ctx.meta
         gy = gy.contiguous()
         B, C = x.shape[:2]
-        Cr = w1.shape[0]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        S = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_affine_act_bwd_stats(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(A), _lib.ptr(Bs), B * C, L, 0, _lib.ptr(S), st),
-                   "affine_act_bwd_stats")                      # act 0: S = {sum gy, sum gy x}
-        Sp = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        dpre2, Qse, Q, R, Aout = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(5))
-        dpre1 = torch.empty(B, Cr, device=dev, dtype=torch.float32)
-        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
-        _lib.check(lib.lion_gn_se_gate_bwd(_lib.ptr(S), _lib.ptr(stats), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(g), _lib.ptr(h),
-                                           _lib.ptr(um), _lib.ptr(w1), _lib.ptr(w2), B, C, Cr, L, _lib.ptr(Sp), _lib.ptr(dpre2),
-                                           _lib.ptr(dpre1), _lib.ptr(Qse), _lib.ptr(dw1), _lib.ptr(dw2), st), "gn_se_gate_bwd")
-        dfac, dbias, dstride = _affine_grad_buffers(B, C, has_f, has_b, dev)
-        pw = torch.empty(B, C, 3, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_gn_train_bwd_fold(_lib.ptr(Sp), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gwc), _lib.ptr(gbc),
-                                              _lib.ptr(f) if has_f else None, fs, B, C, groups, L, _lib.ptr(Q), _lib.ptr(R),
-                                              _lib.ptr(dfac), _lib.ptr(dbias), dstride, _lib.ptr(pw), _lib.ptr(A), _lib.ptr(stats),
-                                              _lib.ptr(g), _lib.ptr(Qse), _lib.ptr(Aout), st), "gn_train_bwd_fold")
+        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
+        _lib.call("lion_affine_act_bwd_stats", x, gy, A, Bs, B * C, L, 0, S)   # act 0: S = {sum gy, sum gy x}
+        Sp, Qse, dw1, dw2 = _se_gate_bwd(S, stats, A, Bs, g, h, um, w1, w2, L)
+        Q, R, dfac, dbias, pw, Aout = _bwd_fold(Sp, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A, stats, g, Qse)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            # (act 0: the kernel's Bs argument does not enter)
-            _lib.check(lib.lion_affine_act_bwd_apply(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(Aout), _lib.ptr(Bs), _lib.ptr(Q),
-                                                     _lib.ptr(R), B * C, L, 0, _lib.ptr(dx), st), "affine_act_bwd_apply")
+            _lib.call("lion_affine_act_bwd_apply", x, gy, Aout, Bs, Q, R, B * C, L, 0, dx)   # (act 0: Bs does not enter)
         dgw, dgb, dxs = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], dx is not None and x.dim() == 5)
         if dxs is not None:
             tag_channel_sum(dx, dxs)
-
-        def back(g_, shape):
-            shape = tuple(int(d) for d in shape)
-            core = shape
-            while len(core) > 2 and core[-1] == 1:
-                core = core[:-1]
-            return g_.sum_to_size(core if core else (1,)).reshape(shape)
-        dfac = back(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = back(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
+        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
+        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
         return (dx, dgw, dgb, dfac, dbias, (dw1 if ctx.needs_input_grad[5] else None), (dw2 if ctx.needs_input_grad[6] else None),
                 None, None)
 
@@ -411,27 +368,10 @@ class _AdaGNSEDevox(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gw, gb, factor, bias, w1, w2, coords, groups, eps, r):
         from .functional import backend as _bk
-        lib = _lib.load()
         x = x.contiguous()
-        B, C = x.shape[:2]
-        Cr = w1.shape[0]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        stats = torch.empty(B * C, 2, device=dev, dtype=torch.float64)
-        _lib.check(lib.lion_row_stats64(_lib.ptr(x), B * C, L, _lib.ptr(stats), st), "row_stats64")
-        A, Bs, mean, rstd = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
-        gwc, gbc = gw.detach().float().contiguous(), gb.detach().float().contiguous()
-        f, fs = _rowview(factor.detach(), B, C) if factor is not None else (None, 0)
-        bb, bs = _rowview(bias.detach(), B, C) if bias is not None else (None, 0)
-        _lib.check(lib.lion_gn_train_fold64(_lib.ptr(stats), _lib.ptr(gwc), _lib.ptr(gbc), _lib.ptr(f), fs, _lib.ptr(bb), bs,
-                                            B, C, groups, L, eps, _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(mean), _lib.ptr(rstd),
-                                            st), "gn_train_fold64")
-        w1c, w2c = w1.detach().float().contiguous(), w2.detach().float().contiguous()
-        um, g, A2, B2 = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(4))
-        h = torch.empty(B, Cr, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_gn_se_gate_fwd(_lib.ptr(stats), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(w1c), _lib.ptr(w2c), B, C, Cr, L,
-                                           _lib.ptr(um), _lib.ptr(h), _lib.ptr(g), _lib.ptr(A2), _lib.ptr(B2), st), "gn_se_gate_fwd")
+        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
+        w1c, w2c, um, h, g, A2, B2 = _se_gate_fwd(stats, A, Bs, w1, w2, L)
         dv, inds, wgts = _bk._backend.trilinear_devoxelize_forward(int(r), True, coords[:, :3].contiguous(), x.flatten(2))
         out = torch.addcmul(B2.unsqueeze(-1), dv, A2.unsqueeze(-1))          # [B, C, N]: (g A) devox(x) + g Bs
         wsum = wgts.sum(1)                                                     # [B, N]: the 8 corner weights of a point
@@ -444,49 +384,25 @@ class _AdaGNSEDevox(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gpt):
-        lib = _lib.load()
         x, A, Bs, mean, rstd, gwc, gbc, f, stats, um, h, g, w1, w2, dv, inds, wgts, wsum = ctx.saved_tensors
         groups, has_f, has_b, fs, f_shape, b_shape = ctx.meta
         gpt = gpt.contiguous()
         B, C = x.shape[:2]
-        Cr = w1.shape[0]
         L = x[0, 0].numel()
         N = gpt.shape[2]
-        st = _lib.stream_ptr(x.device)
-        dev = x.device
-        S = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_rows_dot2(_lib.ptr(gpt), _lib.ptr(dv), _lib.ptr(wsum), B, C, N, _lib.ptr(S), st), "rows_dot2")
-        Sp = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        dpre2, Qse, Q, R, Aout = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(5))
-        dpre1 = torch.empty(B, Cr, device=dev, dtype=torch.float32)
-        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
-        _lib.check(lib.lion_gn_se_gate_bwd(_lib.ptr(S), _lib.ptr(stats), _lib.ptr(A), _lib.ptr(Bs), _lib.ptr(g), _lib.ptr(h),
-                                           _lib.ptr(um), _lib.ptr(w1), _lib.ptr(w2), B, C, Cr, L, _lib.ptr(Sp), _lib.ptr(dpre2),
-                                           _lib.ptr(dpre1), _lib.ptr(Qse), _lib.ptr(dw1), _lib.ptr(dw2), st), "gn_se_gate_bwd")
-        dfac, dbias, dstride = _affine_grad_buffers(B, C, has_f, has_b, dev)
-        pw = torch.empty(B, C, 3, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_gn_train_bwd_fold(_lib.ptr(Sp), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gwc), _lib.ptr(gbc),
-                                              _lib.ptr(f) if has_f else None, fs, B, C, groups, L, _lib.ptr(Q), _lib.ptr(R),
-                                              _lib.ptr(dfac), _lib.ptr(dbias), dstride, _lib.ptr(pw), _lib.ptr(A), _lib.ptr(stats),
-                                              _lib.ptr(g), _lib.ptr(Qse), _lib.ptr(Aout), st), "gn_train_bwd_fold")
+        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
+        _lib.call("lion_rows_dot2", gpt, dv, wsum, B, C, N, S)
+        Sp, Qse, dw1, dw2 = _se_gate_bwd(S, stats, A, Bs, g, h, um, w1, w2, L)
+        Q, R, dfac, dbias, pw, Aout = _bwd_fold(Sp, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A, stats, g, Qse)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            _lib.check(lib.lion_trilinear_devoxelize_backward_affine(_lib.ptr(gpt), _lib.ptr(inds), _lib.ptr(wgts), _lib.ptr(x),
-                                                                     _lib.ptr(Aout), _lib.ptr(Q), _lib.ptr(R), B, C, N, L,
-                                                                     _lib.ptr(dx), st), "trilinear_devoxelize_backward_affine")
+            _lib.call("lion_trilinear_devoxelize_backward_affine", gpt, inds, wgts, x, Aout, Q, R, B, C, N, L, dx)
         dgw, dgb, dxs = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], dx is not None and x.dim() == 5)
         if dxs is not None:
             tag_channel_sum(dx, dxs)
-
-        def back(g_, shape):
-            shape = tuple(int(d) for d in shape)
-            core = shape
-            while len(core) > 2 and core[-1] == 1:
-                core = core[:-1]
-            return g_.sum_to_size(core if core else (1,)).reshape(shape)
-        dfac = back(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = back(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
+        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
+        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
         return (dx, dgw, dgb, dfac, dbias, (dw1 if ctx.needs_input_grad[5] else None), (dw2 if ctx.needs_input_grad[6] else None),
                 None, None, None, None)
 
@@ -518,50 +434,41 @@ class _SE3d(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, w2):
-        lib = _lib.load()
         x = x.contiguous()
         B, C = x.shape[:2]
         Cr = w1.shape[0]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
         dev = x.device
         stats = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_row_stats(_lib.ptr(x), B * C, L, _lib.ptr(stats), st), "row_stats")
+        _lib.call("lion_row_stats", x, B * C, L, stats)
         w1c, w2c = w1.detach().float().contiguous(), w2.detach().float().contiguous()
         mean, g, zero = (torch.empty(B, C, device=dev, dtype=torch.float32) for _ in range(3))
         h = torch.empty(B, Cr, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_se_gate_fwd(_lib.ptr(stats), _lib.ptr(w1c), _lib.ptr(w2c), B, C, Cr, L, _lib.ptr(mean), _lib.ptr(h),
-                                        _lib.ptr(g), _lib.ptr(zero), st), "se_gate_fwd")
+        _lib.call("lion_se_gate_fwd", stats, w1c, w2c, B, C, Cr, L, mean, h, g, zero)
         y = torch.empty_like(x)
-        _lib.check(lib.lion_affine_act(_lib.ptr(x), _lib.ptr(g), _lib.ptr(zero), B * C, L, 0, _lib.ptr(y), st), "affine_act")
+        _lib.call("lion_affine_act", x, g, zero, B * C, L, 0, y)
         ctx.save_for_backward(x, w1c, w2c, mean, h, g, zero)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        lib = _lib.load()
         x, w1, w2, mean, h, g, zero = ctx.saved_tensors
         gy = gy.contiguous()
         B, C = x.shape[:2]
         Cr = w1.shape[0]
         L = x[0, 0].numel()
-        st = _lib.stream_ptr(x.device)
         dev = x.device
         S = torch.empty(B * C, 2, device=dev, dtype=torch.float32)
-        _lib.check(lib.lion_affine_act_bwd_stats(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(g), _lib.ptr(zero), B * C, L, 0,
-                                                 _lib.ptr(S), st), "affine_act_bwd_stats")   # S[:, 1] = sum over the voxels of gy * x
+        _lib.call("lion_affine_act_bwd_stats", x, gy, g, zero, B * C, L, 0, S)   # S[:, 1] = sum over the voxels of gy * x
         dpre2, Q = torch.empty(B, C, device=dev, dtype=torch.float32), torch.empty(B, C, device=dev, dtype=torch.float32)
         dpre1 = torch.empty(B, Cr, device=dev, dtype=torch.float32)
         dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
-        _lib.check(lib.lion_se_gate_bwd(_lib.ptr(S), _lib.ptr(g), _lib.ptr(h), _lib.ptr(mean), _lib.ptr(w1), _lib.ptr(w2), B, C, Cr,
-                                        L, _lib.ptr(dpre2), _lib.ptr(dpre1), _lib.ptr(Q), _lib.ptr(dw1), _lib.ptr(dw2), st),
-                   "se_gate_bwd")
+        _lib.call("lion_se_gate_bwd", S, g, h, mean, w1, w2, B, C, Cr, L, dpre2, dpre1, Q, dw1, dw2)
         dx = None
         if ctx.needs_input_grad[0]:   # Q: d loss / d x through the mean, the same for every voxel of a channel
             dx = torch.empty_like(x)
-            _lib.check(lib.lion_affine_act_bwd_apply(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(g), _lib.ptr(zero), _lib.ptr(Q),
-                                                     _lib.ptr(zero), B * C, L, 0, _lib.ptr(dx), st), "affine_act_bwd_apply")
+            _lib.call("lion_affine_act_bwd_apply", x, gy, g, zero, Q, zero, B * C, L, 0, dx)
         return dx, (dw1 if ctx.needs_input_grad[1] else None), (dw2 if ctx.needs_input_grad[2] else None)
 
 
@@ -641,12 +548,10 @@ class _LinAttnCore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, heads):
-        lib = _lib.load()
         qkv = qkv.contiguous()
         b, n = qkv.shape[0], qkv.shape[2]
         out = torch.empty((b, heads * 32, n), device=qkv.device, dtype=torch.float32)
-        _lib.check(lib.lion_linear_attention_core(_lib.ptr(qkv), b, heads, 32, n, _lib.ptr(out),
-                                                  _lib.stream_ptr(qkv.device)), "linear_attention_core")
+        _lib.call("lion_linear_attention_core", qkv, b, heads, 32, n, out)
         ctx.save_for_backward(qkv)
         ctx.heads = heads
         return out
@@ -655,12 +560,10 @@ class _LinAttnCore(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gout):
         (qkv,) = ctx.saved_tensors
-        lib = _lib.load()
         gout = gout.contiguous()
         b, n = qkv.shape[0], qkv.shape[2]
         gqkv = torch.empty_like(qkv)
-        _lib.check(lib.lion_linear_attention_core_backward(_lib.ptr(qkv), _lib.ptr(gout), b, ctx.heads, 32, n, _lib.ptr(gqkv),
-                                                           _lib.stream_ptr(qkv.device)), "linear_attention_core_backward")
+        _lib.call("lion_linear_attention_core_backward", qkv, gout, b, ctx.heads, 32, n, gqkv)
         return gqkv, None
 
 

@@ -131,3 +131,78 @@ def test_host_side_plan_functions():
     assert lib.lion_skinny_splits(256, 2048) == 1
     assert lib.lion_skinny_splits(128, 48) == 0
     assert lib.lion_skinny_packed_floats(2048, 2048) == 2048 * 8 * 256
+
+
+_CTYPE = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32,
+          "lionStream_t": ctypes.c_void_p}
+
+
+def _prototypes():
+    """include/lion_hip.h -> {name: (restype, [argtypes], [C type words of each parameter])}: comments and preprocessor lines
+    stripped, every `ret name(args);`; a parameter with a `*` is a pointer, the others go by their type name"""
+    txt = open(os.path.join(ROOT, "include", "lion_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    txt = re.sub(r"^\s*#[^\n]*", "", txt, flags=re.M)
+    protos = {}
+    for ret, name, args in re.findall(r"\b(\w+)\s+(lion_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
+        params = [] if args.strip() in ("", "void") else [" ".join(a.split()) for a in args.split(",")]
+        kinds = []
+        for p in params:
+            words = [w for w in re.findall(r"\w+", p) if w != "const"]
+            kinds.append("*" if "*" in p else words[0])    # words[-1] is the parameter's name
+        protos[name] = (_CTYPE[ret], [ctypes.c_void_p if k == "*" else _CTYPE[k] for k in kinds], kinds)
+    return protos
+
+
+def test_ctypes_table_matches_the_header_by_type():
+    """every return and argument type of _lib.SIGNATURES is the header's (an int bound where the header says size_t truncates
+    silently), and every entry point has the shape _lib.call relies on: a function with a pointer parameter returns int and
+    takes exactly one lionStream_t, as its last parameter; a function without one takes no stream"""
+    from lion_amd import _lib
+    protos = _prototypes()
+    assert sorted(protos) == _declared() == sorted(_lib.SIGNATURES)
+    for name, (res, args, kinds) in protos.items():
+        assert _lib.SIGNATURES[name][0] is res, f"{name}: return type"
+        bound = _lib.SIGNATURES[name][1]
+        assert len(bound) == len(args), f"{name}: {len(bound)} bound arguments, {len(args)} declared"
+        for i, (a, b) in enumerate(zip(bound, args)):
+            assert a is b, f"{name}: argument {i} bound as {a.__name__}, declared {kinds[i]}"
+        launches = "*" in kinds
+        assert (bool(kinds) and kinds[-1] == "lionStream_t") == launches, f"{name}: stream iff pointers"
+        assert kinds.count("lionStream_t") == (1 if launches else 0), name
+        assert not launches or res is ctypes.c_int, f"{name}: a launch returns int"
+
+
+def test_call_refuses_cpu_tensors_before_the_library():
+    """_lib.call checks the device of every tensor before the library is entered: a CPU tensor is an exception that says so,
+    never a pointer handed to a kernel -- also through entry points that had no check of their own"""
+    from lion_amd import _lib, fused_ops, train_ops
+    x, out = torch.zeros(4, 8), torch.zeros(4, 2)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        _lib.call("lion_row_stats", x, 4, 8, out)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        fused_ops.row_stats(torch.zeros(2, 3, 8))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        train_ops.linear_attention_core(torch.zeros(1, 96, 8), 1)
+
+
+def test_call_checks_the_argument_count():
+    """one argument too few: a TypeError that names the symbol, raised before anything is launched"""
+    from lion_amd import _lib
+    with pytest.raises(TypeError, match="lion_row_stats"):
+        _lib.call("lion_row_stats", None, 4, 8)
+    with pytest.raises(TypeError, match="lion_row_stats"):
+        _lib.call("lion_row_stats", None, 4, 8, None, None)
+
+
+def test_every_launch_goes_through_call():
+    """no file under lion_amd/ other than _lib.py builds a launch by hand (pointer, stream and error label per site)"""
+    bad = []
+    for dp, _, fns in os.walk(os.path.join(ROOT, "lion_amd")):
+        for fn in fns:
+            path = os.path.join(dp, fn)
+            if fn.endswith(".py") and os.path.relpath(path, ROOT) != os.path.join("lion_amd", "_lib.py"):
+                src = open(path).read()
+                bad += [f"{path}: {w}" for w in ("_lib.ptr(", "_lib.stream_ptr(", "_lib.check(") if w in src]
+    assert not bad, bad
