@@ -304,6 +304,18 @@ int lion_conv3d_split_stat_tiles(int r, int Cout);
 int lion_conv3d_k3_split_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout,
                                  int r, const float *pro_a, const float *pro_b, const float *pro_bias,
                                  const float *tconst, float *y, float *stats, int32_t *occ, lionStream_t stream);
+/* ---- C3 at reduced precision, on purpose (csrc/conv3d_half.hip) ----------------------------------------------
+ * lion_conv3d_k3_split_forward with ONE fp16 product per operand pair (main += W_h X_h, no low pieces, no corr): a third
+ * of the MFMAs.  Same arguments, same modes (prologue, tile sums, occ / tconst, consumer-aware levels), same tile geometry
+ * (stats has lion_conv3d_split_stat_tiles(r, Cout) tiles) and the SAME packed weights -- wp from
+ * lion_conv3d_split_pack_weights, of which only the hi pieces and the scale are read.  With the block scaling a hi piece is
+ * the operand rounded to an 11-bit significand, so the result is conv(rne11(W), rne11(act(X))) accumulated in fp32:
+ * |y - conv64(W, X)| <= 2^-10 * conv64(|W|, |X|) elementwise; no clamp, inf / nan propagate.  Inference only.
+ * r in {16, 32}, Cin % 16 == 0, Cout % 32 == 0; anything else (r = 8 included, which stays on the split kernel) is
+ * LION_EINVAL and nothing is written. */
+int lion_conv3d_k3_half_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout,
+                                int r, const float *pro_a, const float *pro_b, const float *pro_bias,
+                                const float *tconst, float *y, float *stats, int32_t *occ, lionStream_t stream);
 /* ---- D2: global denoiser, models/score_sde/resnet.py:60-90, :195-218 -----------------------------------
  * The 1x1 convs of the [B, C, 1, 1] style-latent network as 32-row GEMMs on channel-major activations
  * f32[nb][C][32] (batch padded to 32 per slab), split over K into lion_skinny_splits workgroup rows that write raw

@@ -21,6 +21,15 @@ def invalidate_weight_caches() -> None:
     _wcache.invalidate_all()
 
 
+def conv_precision(value):
+    """``with lion_amd.conv_precision("half"):`` -- the supported reduced-precision mode: inside, the voxel convolutions of
+    an inference forward at r = 16 / 32 run ONE fp16 product per operand pair on the project's own kernel
+    (csrc/conv3d_half.hip; |error| <= 2^-10 sum |w||x|); "fp32" (the default everywhere) is the fp32-accurate path.
+    r = 8, gradients and training stay fp32-accurate.  See conv_ops.conv_precision."""
+    from . import conv_ops
+    return conv_ops.conv_precision(value)
+
+
 def _poison_uninitialised():
     """LION_DEBUG_POISON=1: every torch.empty / empty_like on the GPU is filled with NaN (float) / a large negative
     number (int32), so that a kernel reading memory it was supposed to overwrite first shows up as NaN / an index far

@@ -1,4 +1,5 @@
 """Conv3d (3x3x3, pad 1) on the fp32 matrix cores: lion_conv3d_k3_forward over the C ABI."""
+import contextlib
 import os
 
 import torch
@@ -33,6 +34,53 @@ def use_split(split, cin, cout, r):
     if split is None:
         return SPLIT and split_preferred(cin, cout, r)
     return bool(split) and split_supported(cin, cout, r)
+
+
+# The supported reduced-precision mode (csrc/conv3d_half.hip), inference only:
+#   "fp32" (default) -> every voxel convolution is fp32-accurate (the kernels above);
+#   "half"           -> where the split kernel would run at r = 16 / 32, ONE fp16 product per operand pair instead of three:
+#                       conv(rne11(W), rne11(X)) with fp32 accumulation, |error| <= 2^-10 sum |w||x| elementwise.
+# r = 8, the VAE decode of the samplers, every gradient and every training op stay fp32-accurate.
+# Set by LION_CONV_PRECISION, by `with lion_amd.conv_precision("half"):` or by the samplers' conv_precision= keyword.
+PRECISIONS = ("fp32", "half")
+PRECISION = os.environ.get("LION_CONV_PRECISION", "fp32")
+if PRECISION not in PRECISIONS:
+    raise ValueError(f"LION_CONV_PRECISION={PRECISION!r}: expected one of {PRECISIONS}")
+
+
+@contextlib.contextmanager
+def conv_precision(value):
+    """`with conv_precision("half"):` -- the voxel convolutions inside run at this precision; the previous setting comes back on
+    exit, also after an exception.  A chain captured under one setting is re-captured under the other (chain.policy_key)."""
+    global PRECISION
+    if value not in PRECISIONS:
+        raise ValueError(f"conv_precision={value!r}: expected one of {PRECISIONS}")
+    prev, PRECISION = PRECISION, value
+    try:
+        yield
+    finally:
+        PRECISION = prev
+
+
+def requested_precision(value):
+    """the context of a sampler's conv_precision= keyword: "half" selects the mode for the denoiser evaluations of that
+    call; "fp32" asks for no reduction and leaves the ambient setting (PRECISION) as it is"""
+    if value not in PRECISIONS:
+        raise ValueError(f"conv_precision={value!r}: expected one of {PRECISIONS}")
+    return conv_precision(value) if value != "fp32" else contextlib.nullcontext()
+
+
+def half_supported(cin, cout, r):
+    """what csrc/conv3d_half.hip can run: the split kernel's shapes at r = 16 / 32 (r = 8 stays on the three-product kernel)"""
+    return r in (16, 32) and cout % 32 == 0 and cin >= 16 and cin % 16 == 0
+
+
+def use_half(cin, cout, r, x=None):
+    """True where a convolution the split kernel would take runs on the single-product kernel instead: the policy says
+    "half", the shape allows, and -- inference only -- `x` is not an input that requires grad under an enabled autograd."""
+    if PRECISION != "half" or not half_supported(cin, cout, r):
+        return False
+    return not (x is not None and torch.is_grad_enabled() and x.requires_grad)
 
 
 def pack_with(weight, size_query, pack, dtype, as_matrix=False):
@@ -70,13 +118,15 @@ def packed_weight(weight):
     return _PACK_CACHE.get(weight)
 
 
-def conv3d_k3(x, weight, bias=None, split=None, packed=None, occ=None):
+def conv3d_k3(x, weight, bias=None, split=None, packed=None, occ=None, half=None):
     """x [B,Cin,r,r,r] fp32 -> [B,Cout,r,r,r]; Cin is zero-padded to a multiple of 4 if needed.
     split: None = the module default (SPLIT), False = the exact-fp32 MFMA kernel, True = split operands if supported.
     packed: callable(kind) -> the packed copy of `weight` for kind in ("split", "f32"), for callers whose `weight` is a
     derived temporary and who cache its packed forms under the ORIGINAL parameter (the data-gradient path).
     occ: the tile occupancy of a freshly voxelised `x` (fused_ops.conv3d_occupancy(counts)[0]): tiles without a point within
-    one voxel skip their K loop (output = bias exactly); split kernel only, ignored otherwise."""
+    one voxel skip their K loop (output = bias exactly); split kernel only, ignored otherwise.
+    half: None = the precision policy (use_half) decides between the split kernel and the single-product one, False = never
+    (the training ops)."""
     _lib.require_cuda(x)
     b, cin, r = x.shape[0], x.shape[1], x.shape[2]
     cout = weight.shape[0]
@@ -85,8 +135,8 @@ def conv3d_k3(x, weight, bias=None, split=None, packed=None, occ=None):
         y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
         bias_c = bias.detach().contiguous() if bias is not None else None
         wp = packed("split") if packed is not None else split_packed_weight(weight)
-        _lib.call("lion_conv3d_k3_split_forward", x, wp, bias_c, b, cin, cout, r, None, None, None, None, y, None,
-                  occ if r >= 16 else None)
+        entry = "lion_conv3d_k3_half_forward" if (half is None and use_half(cin, cout, r, x)) else "lion_conv3d_k3_split_forward"
+        _lib.call(entry, x, wp, bias_c, b, cin, cout, r, None, None, None, None, y, None, occ if r >= 16 else None)
         return y
     if cin % 4:
         pad = 4 - cin % 4
@@ -139,7 +189,7 @@ def conv3d_k3_dgrad(gy, weight, counts=None):
     if counts is not None and TRAIN_SPARSE and r in (16, 32) and use_split(None, gy.shape[1], wt.shape[0], r):
         from . import fused_ops
         occ = fused_ops.conv3d_occupancy(counts, r, wt.shape[0], gy.shape[0])[0]
-    return conv3d_k3(gy, wt, None, occ=occ,
+    return conv3d_k3(gy, wt, None, occ=occ, half=False,
                      packed=lambda kind: (_DGRAD_SPLIT_CACHE if kind == "split" else _DGRAD_PACK_CACHE).get(weight))
 
 
@@ -189,7 +239,7 @@ class _Conv3dK3(torch.autograd.Function):
         if counts is not None and TRAIN_SPARSE and r in (16, 32) and use_split(None, x.shape[1], cout, r):
             from . import fused_ops
             occ = fused_ops.conv3d_occupancy(counts, r, cout, x.shape[0])[0]
-        return conv3d_k3(x, weight, bias, occ=occ)
+        return conv3d_k3(x, weight, bias, occ=occ, half=False)
 
     @staticmethod
     def backward(ctx, gy):

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import chain as _chain
+from . import conv_ops
 from . import diffusion_ops
 
 
@@ -192,9 +193,17 @@ class DiffusionDiscretized(object):
     def run_denoising_diffusion(self, model, num_samples, shape, temp=1.0, enable_autocast=False,
                                 is_image=False, prior_var=1.0, condition_input=None, given_noise=None,
                                 clip_feat=None, cls_emb=None, grid_emb=None, graph=True, keep_trajectory=True,
-                                noise_scale=None):
+                                noise_scale=None, conv_precision="fp32"):
         """Ancestral DDPM sampling, T model evaluations (reference :224-303).  ``noise_scale(t)`` overrides the
-        per-step noise standard deviation sqrt(beta_t) (LION.sample's scheduler variance)."""
+        per-step noise standard deviation sqrt(beta_t) (LION.sample's scheduler variance).
+        conv_precision="half": the denoiser's voxel convolutions run at reduced precision (conv_ops.PRECISION)."""
+        with conv_ops.requested_precision(conv_precision):
+            return self._run_denoising_diffusion(model, num_samples, shape, temp, enable_autocast, is_image, prior_var,
+                                                 condition_input, given_noise, clip_feat, cls_emb, grid_emb, graph,
+                                                 keep_trajectory, noise_scale)
+
+    def _run_denoising_diffusion(self, model, num_samples, shape, temp, enable_autocast, is_image, prior_var, condition_input,
+                                 given_noise, clip_feat, cls_emb, grid_emb, graph, keep_trajectory, noise_scale):
         model.eval()
         dev = self.device
         size = [num_samples] + list(shape)
@@ -245,14 +254,25 @@ class DiffusionDiscretized(object):
     def run_ddim(self, model, num_samples, shape, temp=1.0, enable_autocast=False, is_image=True,
                  prior_var=1.0, condition_input=None, ddim_step=100, skip_type='uniform', kappa=1.0,
                  clip_feat=None, grid_emb=None, x_noisy=None, dae_index=-1, noise='device',
-                 keep_trajectory=True, graph=True, given_noise=None, state_hook=None):
+                 keep_trajectory=True, graph=True, given_noise=None, state_hook=None, conv_precision="fp32"):
         """DDIM sampling with ``ddim_step`` model evaluations; kappa is DDIM's eta (reference :390-473).
         noise='cpu': EVERY draw of the chain -- the start and the per-step noise -- comes from torch's CPU generator, so
         that one seed gives one chain on any device (the reference draws the per-step noise there, :465-466, and the
         start on its device).  given_noise = (start, [z_0, z_1, ...]): run the eager loop on exactly these draws (the
         counterpart of run_denoising_diffusion's given_noise; tests replay a graphed chain's recorded noise with it).
         state_hook(i, x): called before the i-th model evaluation with the chain's latent, which it may overwrite in place
-        (device-side launches only; known-region replacement, bench.py's forced clouds)."""
+        (device-side launches only; known-region replacement, bench.py's forced clouds).
+        conv_precision="half": the supported reduced-precision mode -- the denoiser's voxel convolutions at r = 16 / 32 run
+        one fp16 product per operand pair on the project's own kernel, inside the captured chain (conv_ops.PRECISION;
+        DESIGN.md 4.3).  enable_autocast is unrelated to it and keeps its behaviour."""
+        with conv_ops.requested_precision(conv_precision):
+            return self._run_ddim(model, num_samples, shape, temp, enable_autocast, is_image, prior_var, condition_input,
+                                  ddim_step, skip_type, kappa, clip_feat, grid_emb, x_noisy, dae_index, noise,
+                                  keep_trajectory, graph, given_noise, state_hook)
+
+    def _run_ddim(self, model, num_samples, shape, temp, enable_autocast, is_image, prior_var, condition_input, ddim_step,
+                  skip_type, kappa, clip_feat, grid_emb, x_noisy, dae_index, noise, keep_trajectory, graph, given_noise,
+                  state_hook):
         model.eval()
         dev = self.device
         size = [num_samples] + list(shape)

@@ -21,6 +21,7 @@ from timeit import default_timer as timer
 import numpy as np
 import torch
 
+from . import conv_ops
 from . import ode as _ode
 
 _NOT_PORTED = ('geometric_sde', 'sub_vpsde', 'power_vpsde', 'sub_power_vpsde', 'vesde')
@@ -179,17 +180,19 @@ class DiffusionVPSDE(object):
     @torch.no_grad()
     def sample_model_ode(self, dae, num_samples, shape, ode_eps, ode_solver_tol, enable_autocast, temp, noise=None,
                          condition_input=None, mixing_logit=None, init_t=1.0, return_all_sample=False, clip_feat=None,
-                         graph=True):
+                         graph=True, conv_precision="fp32"):
         """latent noise at init_t -> latent at ode_eps.  Returns (x, nfe, seconds), or with return_all_sample
         (x, [start, x], nfe, seconds): the two points odeint reports.  mixing_logit replaces the model's own logit in the
-        mixed prediction (models with mixed_prediction only, as in the reference)."""
+        mixed prediction (models with mixed_prediction only, as in the reference).
+        conv_precision="half": the denoiser's voxel convolutions run at reduced precision (conv_ops.PRECISION)."""
         dae.eval()
         if noise is None:
             noise = torch.randn(size=[num_samples] + list(shape), device=self.device)
         start_x = temp * noise
         tic = timer()
-        x, ctrl = self._integrate(dae, start_x, init_t, ode_eps, ode_solver_tol, condition_input, clip_feat, graph,
-                                  enable_autocast, mixing_logit)
+        with conv_ops.requested_precision(conv_precision):
+            x, ctrl = self._integrate(dae, start_x, init_t, ode_eps, ode_solver_tol, condition_input, clip_feat, graph,
+                                      enable_autocast, mixing_logit)
         seconds = timer() - tic
         self.last_ode = ctrl
         if return_all_sample:

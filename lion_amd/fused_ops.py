@@ -80,7 +80,9 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
         epilogue (27 border configurations), the MFMA loop runs on the delta and skips tiles with no point within
         2 voxels.
     split (None = conv_ops.SPLIT): run on the split-operand kernel (fp16 x 2 pieces on the 16-bit MFMA pipe, fp32
-    accurate, csrc/conv3d_split.hip) where Cin % 16 == 0; same modes, same results within fp32 rounding.
+    accurate, csrc/conv3d_split.hip) where Cin % 16 == 0; same modes, same results within fp32 rounding.  Under
+    conv_ops.PRECISION == "half" such a launch at r = 16 / 32 goes to the single-product kernel (csrc/conv3d_half.hip)
+    instead: same arguments, same packed weights, same tile sums layout.
     fold (a FoldSpec): return (y, (A, Bs)) -- the GroupNorm fold of y (+ SE gate) -- instead of (y, stats)."""
     lib = _lib.load()
     b, cin, r = x.shape[0], x.shape[1], x.shape[2]
@@ -112,8 +114,10 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
         stats = torch.empty((b, cout, tiles, 2), device=x.device, dtype=torch.float32)
     if not sparse:
         occ = None
-    _lib.call("lion_conv3d_k3_split_forward" if use_split else "lion_conv3d_k3_fused_forward",
-              x, wp, bias, b, cin, cout, r, pa, pb, pbias, tconst, y, stats, occ)
+    entry = "lion_conv3d_k3_fused_forward"
+    if use_split:
+        entry = "lion_conv3d_k3_half_forward" if conv_ops.use_half(cin, cout, r, x) else "lion_conv3d_k3_split_forward"
+    _lib.call(entry, x, wp, bias, b, cin, cout, r, pa, pb, pbias, tconst, y, stats, occ)
     if fold is not None:
         return y, fold.apply(stats)
     return y, stats

@@ -74,9 +74,10 @@ class LION(object):
         print(f'INFO finish loading from {model_path}')
 
     @torch.no_grad()
-    def sample(self, num_samples=10, clip_feat=None, save_img=False):
+    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32"):
         """1000 ancestral steps of the global prior, 1000 of the local prior, one decode
-        (reference :38-80)."""
+        (reference :38-80).  conv_precision="half": the priors' voxel convolutions run at reduced precision
+        (conv_ops.PRECISION); the decode stays fp32-accurate."""
         self.priors.eval()
         self.vae.eval()
         self.scheduler.set_timesteps(self.diffusion._diffusion_steps, device=self.device)
@@ -91,7 +92,7 @@ class LION(object):
             # the scheduler's mean / variance rule feeds the chain's coefficient table (lion_amd/chain.py)
             x, _ = self.diffusion.run_denoising_diffusion(
                 prior, num_samples, shp, condition_input=condition_input, clip_feat=clip_feat,
-                keep_trajectory=False, noise_scale=self.scheduler._noise_scale)
+                keep_trajectory=False, noise_scale=self.scheduler._noise_scale, conv_precision=conv_precision)
             prior.eval()
             sampled.append(x)
             output_dict[key] = x

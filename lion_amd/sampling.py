@@ -12,7 +12,8 @@ import torch
 def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable_autocast=False,
                                  temp=1.0, ddim_step=0, clip_feat=None, ddim_skip_type='uniform',
                                  ddim_kappa=1.0, noise='device', step_callback=None, graph=True, given_noise=None,
-                                 state_hook=None, ode_sample=0, ode_eps=1e-5, ode_solver_tol=1e-5, start_noise=None):
+                                 state_hook=None, ode_sample=0, ode_eps=1e-5, ode_solver_tol=1e-5, start_noise=None,
+                                 conv_precision="fp32"):
     """shape: vae.latent_shape(); dae: [global prior, local prior].  Returns (points [B,N,3], info).
     graph=True (default): every chain is replayed from one captured hipGraph per prior (lion_amd/chain.py);
     graph=False: the eager per-step loop; noise='cpu' draws the start and every step's noise from torch's CPU generator
@@ -22,7 +23,11 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
     device-side launches, no host synchronisation).
     ode_sample=1 (train_2prior.py:58-75): each prior integrates the probability-flow ODE of a continuous diffusion
     (diffusion_continuous.DiffusionVPSDE) from t = 1 to ode_eps at tolerance ode_solver_tol, starting from
-    start_noise[i] if given (else fresh N(0, I) draws); info['nfe'] lists the evaluations per prior."""
+    start_noise[i] if given (else fresh N(0, I) draws); info['nfe'] lists the evaluations per prior.
+    conv_precision="half": the supported reduced-precision mode -- the denoiser evaluations of every chain run their voxel
+    convolutions at r = 16 / 32 with one fp16 product per operand pair, inside the captured chain (conv_ops.PRECISION,
+    DESIGN.md 4.3); the VAE decode stays fp32-accurate.  enable_autocast is unrelated and keeps its behaviour (it leaves
+    the captured chain for the vendor libraries)."""
     condition_input = None
     all_eps = []
     nfes = []
@@ -33,7 +38,8 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
             eps, nfe, _ = diffusion.sample_model_ode(dae[i], num_samples, shape[i], ode_eps, ode_solver_tol,
                                                      enable_autocast, temp,
                                                      None if start_noise is None else start_noise[i],
-                                                     condition_input=condition_input, clip_feat=clip_feat, graph=graph)
+                                                     condition_input=condition_input, clip_feat=clip_feat, graph=graph,
+                                                     conv_precision=conv_precision)
             nfes.append(nfe)
         elif ddim_step > 0:
             eps, _ = diffusion.run_ddim(dae[i], num_samples, shape[i], temp, enable_autocast,
@@ -43,12 +49,13 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
                                         keep_trajectory=False, graph=graph,
                                         given_noise=None if given_noise is None else given_noise[i],
                                         state_hook=None if state_hook is None else
-                                        (lambda k, x, _i=i: state_hook(_i, k, x)))
+                                        (lambda k, x, _i=i: state_hook(_i, k, x)), conv_precision=conv_precision)
         else:
             eps, _ = diffusion.run_denoising_diffusion(dae[i], num_samples, shape[i], temp,
                                                        enable_autocast, is_image=False,
                                                        condition_input=condition_input,
-                                                       clip_feat=clip_feat, graph=graph, keep_trajectory=False)
+                                                       clip_feat=clip_feat, graph=graph, keep_trajectory=False,
+                                                       conv_precision=conv_precision)
         condition_input = eps
         if i == 0:
             condition_input = vae.global2style(condition_input)
