@@ -8,9 +8,10 @@ of the same shape (seen as a flaky parity test).  Least-recently-used entries ar
 
 The version counter only sees writes made through the tensor itself: ``p.data.copy_()`` / ``p.data[...] = `` write
 the same storage WITHOUT bumping it.  Writers inside this package therefore use ``with torch.no_grad(): p.copy_()``
-and additionally call ``invalidate_all()``, which advances a process-wide generation every entry (and every derived
-object: ``StylePlan``, ``GraphedDenoiser``) is validated against; code outside the package that pokes ``.data`` must
-call ``lion_amd.invalidate_weight_caches()`` itself."""
+and additionally call ``invalidate_all()``, which advances a process-wide generation every entry and every derived
+object is validated against: a ``StylePlan``, and every captured graph through ``chain.CapturedStep.valid()`` --
+``GraphedChain``, ``OdeGraph`` and ``GraphedDenoiser`` capture again before they would replay a stale one.  Code outside
+the package that pokes ``.data`` must call ``lion_amd.invalidate_weight_caches()`` itself."""
 from collections import OrderedDict
 from contextlib import contextmanager
 

@@ -5,18 +5,20 @@ One denoiser evaluation of the local prior is ~500 kernel launches; the referenc
 (utils/diffusion_pvd.py:224-303, :390-473) additionally issue ~10 elementwise launches, a ``torch.full`` and a
 host-side ``randn`` + H2D copy per step.  Here a captured step holds
     lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise
-and a chain of S steps is S replays of it: one hipGraph for models without set abstraction (the global prior); for the
-point-voxel denoiser three single-branch graphs on the main stream and the step's FPS / ball-query chain as two graphs on a
-second stream, ordered by events between the launches (GraphedChain.__init__; round 3 -- branches INSIDE one graph replay
-slower than one stream on ROCm 7.2, separate graphs on separate streams overlap).  Everything that changes from step to step lives in device memory:
-the schedule table (timestep for the model + the update's coefficients, S x 8 floats uploaded once per chain), the
-step counter, the Philox seed, the latent ``x`` (updated in place).  The host issues one to five ``hipGraphLaunch`` per step
-and never synchronises inside the chain.
-
-A captured graph bakes in the packed-weight pointers of its model: it is keyed by ``_wcache.fingerprint(model)``
-and re-captured when any parameter changed (optimizer step, EMA swap, checkpoint load).
+and a chain of S steps is S replays of it.  Two things live here, apart:
+  * ``CapturedStep``: warm-up, capture and replay of ANY step given as a callable -- the one capture path of the package
+    (this chain, ode.OdeGraph, graph.GraphedDenoiser).  One hipGraph for models without set abstraction (the global prior);
+    for the point-voxel denoiser three single-branch graphs on the main stream and the step's FPS / ball-query chain as two
+    graphs on a second stream, ordered by events between the launches.  A graph bakes in the packed-weight pointers of its
+    model: it pins them, and ``valid()`` fails once any parameter (optimizer step, EMA swap, checkpoint load) or a
+    kernel-selecting switch (``policy_key()``) changed -- the owner then captures again.
+  * ``GraphedChain``: the chain's state, all of it in device memory -- the schedule table (timestep for the model + the
+    update's coefficients, S x 8 floats uploaded once per chain), the step counter, the Philox seed, the latent ``x``
+    (updated in place).  The host issues one to five ``hipGraphLaunch`` per step and never synchronises inside the chain.
 """
 from __future__ import annotations
+
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -40,67 +42,52 @@ def policy_key() -> tuple:
             pvcnn2_ada.SKIP_UNREAD, pvcnn2_ada.SKIP_UNREAD_LEVEL2, CHANNEL_MAJOR_EPS, conv_ops.PRECISION)
 
 
-class GraphedChain:
-    def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
-                 record_noise=False, step_fn=None):
-        """step_fn(chain), if given, replaces the chain's step: another driver's kernels around the same forward, captured
-        with the same machinery (lion_amd/ode.py: [ODE stage -> forward -> drift]); it reads chain.x / chain.t / chain.cond /
-        chain.clip as the model's inputs."""
-        self.model, self.mode, self.capacity = model, mode, int(capacity)
-        self.fingerprint = _wcache.fingerprint(model)
-        dev = torch.device(device)
-        size = [num_samples] + list(shape)
-        self.x = torch.zeros(size, device=dev)
-        self.t = torch.zeros(num_samples, device=dev)
-        self.cond = None if condition_input is None else condition_input.detach().clone().contiguous()
-        self.clip = None if clip_feat is None else clip_feat.detach().clone().contiguous()
-        self.table = torch.zeros(self.capacity, 8, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.seed = torch.zeros(2, dtype=torch.int32, device=dev)   # two 32-bit words of the Philox key
-        self.cur = torch.zeros(8, device=dev)
-        self.z = torch.zeros(size, device=dev) if record_noise else None   # tests: the noise each step used
-        # identity rows until run() uploads a schedule: the warm-up / capture passes must run on finite values (an
-        # all-zero DDPM row is 0/0 -> the second warm-up forward would voxelize NaN latents)
-        self.table[:, 0] = 1.0   # t_model
-        self.table[:, 1] = 1.0   # a0: x passes through
-        self.table[:, 3] = 1.0   # a2: DDPM divisor (DDIM: z has weight 1 -- finite)
-        # The time embedding of a step depends on the step's timestep alone: its rows for the whole chain are computed once
-        # per run() (model.time_embedding over the schedule) and a replayed step picks its row by the device-resident step
-        # index -- instead of 7 (global prior) / 3 (local prior) launches per step that recompute it for every sample.
-        self.temb_table = None
-        self.use_temb_table = step_fn is None and TEMB_TABLE and hasattr(model, "time_embedding") and not getattr(model, "embed_dim", 1) == 0
-        self.policy = policy_key()
+def channel_major(model, shape) -> bool:
+    """the model hands back its channel-major [B, 4, N] output and the step's last kernel reads it in that layout"""
+    n_pts, n_cls = getattr(model, "num_points", 0), getattr(model, "num_classes", 0)
+    return CHANNEL_MAJOR_EPS and hasattr(model, "geometry_source") and n_cls == 4 and int(np.prod(shape)) == n_pts * n_cls
+
+
+def same_conditioning(owner, condition_input, clip_feat) -> bool:
+    """owner.cond / owner.clip, the static conditioning buffers of a capture, can take these inputs"""
+    same = lambda buf, new: (buf is None) == (new is None) and (buf is None or buf.shape == new.shape)
+    return same(owner.cond, condition_input) and same(owner.clip, clip_feat)
+
+
+class LRU:
+    """a handful of captured objects by key (each holds the private memory pool of one forward pass)"""
+
+    def __init__(self, capacity=4):
+        self._entries, self._capacity = OrderedDict(), capacity
+
+    def lookup(self, key, usable, build):
+        """the entry of `key` if usable(entry); else it is dropped and build() takes its place"""
+        hit = self._entries.get(key)
+        if hit is not None and usable(hit):
+            self._entries.move_to_end(key)
+            return hit
+        self._entries.pop(key, None)
+        hit = self._entries[key] = build()
+        while len(self._entries) > self._capacity:
+            self._entries.popitem(last=False)
+        return hit
+
+    def clear(self):
+        self._entries.clear()
+
+
+class CapturedStep:
+    """The capture machinery of every graphed driver (the chain below, ode.OdeGraph, graph.GraphedDenoiser).  ``step`` is a
+    zero-argument callable that issues one step's launches on the current stream, reading and writing only buffers its
+    caller owns; ``x`` is the static tensor ``model.geometry_source(x)`` derives the coordinates from.  Warm-up, capture
+    (``split=None``: the split-geometry form where the switches and the model allow it; ``False``: always one graph) and
+    the pinned packed weights live here, with what the graphs are valid for: ``fingerprint`` and ``policy``."""
+
+    def __init__(self, model, step, x, *, warmup=2, split=None):
+        self.model, self.x = model, x
+        self.fingerprint, self.policy = _wcache.fingerprint(model), policy_key()
         self.pinned = []         # strong references to every packed / mirrored weight the captured launches point at
-
-        # the local prior hands back its channel-major [B, 4, N] output; the update reads it in that layout (round 6: no
-        # transposing ATen copy at the end of a step)
-        n_pts, n_cls = getattr(model, "num_points", 0), getattr(model, "num_classes", 0)
-        self.cm_out = (CHANNEL_MAJOR_EPS and hasattr(model, "geometry_source") and n_cls == 4
-                       and int(np.prod(shape)) == n_pts * n_cls and not getattr(model, "mixed_prediction", False))
-
-        def step():
-            if step_fn is not None:
-                step_fn(self)
-                return
-            extra = {}
-            if self.temb_table is not None:   # the step's time-embedding row, copied by the prologue kernel itself
-                _lib.call("lion_chain_begin_step_temb", self.table, self.capacity, self.counter, self.t, num_samples, self.cur,
-                          self.temb_table, self.temb_row.numel(), self.temb_row)
-                extra["temb"] = self.temb_row
-            else:
-                _lib.call("lion_chain_begin_step", self.table, self.capacity, self.counter, self.t, num_samples, self.cur)
-            if self.cm_out:
-                pred = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, channel_major_out=True,
-                             **extra)
-                eps = pred.float().contiguous()
-                assert tuple(eps.shape) == (num_samples, n_cls, n_pts)
-                _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
-                          self.z)
-                return
-            pred = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **extra)
-            eps = pred.float().contiguous()
-            _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
-
+        dev = x.device
         # Split-graph geometry overlap (geometry.SPLIT_GRAPH, models with a geometry_source()): the FPS / ball-query chain of
         # a step depends on the coordinates of x alone, is latency bound (0.7 ms on 32 CUs) and, on one stream, serial.
         # A parallel BRANCH inside one hipGraph replays slower than one stream on ROCm 7.2 (geometry.py), but separate
@@ -111,14 +98,9 @@ class GraphedChain:
         # ordered with two events per step.  Models without set abstraction never reach "first use": one graph, as before.
         from . import geometry
         src = getattr(model, "geometry_source", None)
-        self.geo_graphs = self.graph_b = None
-        self.geo_plan = None
-        split = geometry.SPLIT_GRAPH and src is not None and not geometry.ENABLED
-        if self.use_temb_table:
-            with torch.no_grad():
-                row = model.time_embedding(torch.ones(1, device=dev))
-            self.temb_table = torch.zeros((self.capacity,) + tuple(row.shape[1:]), device=dev)
-            self.temb_row = torch.zeros((1,) + tuple(row.shape[1:]), device=dev)
+        self.geo_graphs = self.graph_b = self.graphs = self.waits = self.geo_plan = None
+        if split is None:
+            split = geometry.SPLIT_GRAPH and src is not None and not geometry.ENABLED
         main = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(main)
@@ -134,7 +116,7 @@ class GraphedChain:
                 self.ev_step = torch.cuda.Event()
 
                 def geo(boundary=None):
-                    mods, coords = src(self.x)
+                    mods, coords = src(x)
                     return geometry.compute_chain(mods, coords, boundary=boundary)
                 self.geo_stream.wait_stream(main)
                 with torch.no_grad(), torch.cuda.stream(self.geo_stream):
@@ -197,7 +179,7 @@ class GraphedChain:
         self.pinned = list({id(v): v for v in self.pinned}.values())   # one reference per distinct object
 
     def replay(self):
-        """one chain step on the current stream (+ the geometry stream in split mode)"""
+        """one step on the current stream (+ the geometry stream in split mode)"""
         if self.graph_b is None:
             self.graph.replay()
             return
@@ -214,10 +196,66 @@ class GraphedChain:
                 main.wait_event(self.ev_geo[g])
             self.graphs[k + 1].replay()
 
+    def valid(self):
+        """the graphs still point at the model's current weights and were captured under the current switches"""
+        return self.fingerprint == _wcache.fingerprint(self.model) and self.policy == policy_key()
+
+
+class GraphedChain:
+    def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
+                 record_noise=False):
+        self.model, self.mode, self.capacity = model, mode, int(capacity)
+        dev = torch.device(device)
+        size = [num_samples] + list(shape)
+        self.x = torch.zeros(size, device=dev)
+        self.t = torch.zeros(num_samples, device=dev)
+        self.cond = None if condition_input is None else condition_input.detach().clone().contiguous()
+        self.clip = None if clip_feat is None else clip_feat.detach().clone().contiguous()
+        self.table = torch.zeros(self.capacity, 8, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.seed = torch.zeros(2, dtype=torch.int32, device=dev)   # two 32-bit words of the Philox key
+        self.cur = torch.zeros(8, device=dev)
+        self.z = torch.zeros(size, device=dev) if record_noise else None   # tests: the noise each step used
+        # identity rows until run() uploads a schedule: the warm-up / capture passes must run on finite values (an
+        # all-zero DDPM row is 0/0 -> the second warm-up forward would voxelize NaN latents)
+        self.table[:, 0] = 1.0   # t_model
+        self.table[:, 1] = 1.0   # a0: x passes through
+        self.table[:, 3] = 1.0   # a2: DDPM divisor (DDIM: z has weight 1 -- finite)
+        # The time embedding of a step depends on the step's timestep alone: its rows for the whole chain are computed once
+        # per run() (model.time_embedding over the schedule) and a replayed step picks its row by the device-resident step
+        # index -- instead of 7 (global prior) / 3 (local prior) launches per step that recompute it for every sample.
+        self.temb_table = None
+        if TEMB_TABLE and hasattr(model, "time_embedding") and not getattr(model, "embed_dim", 1) == 0:
+            with torch.no_grad():
+                row = model.time_embedding(torch.ones(1, device=dev))
+            self.temb_table = torch.zeros((self.capacity,) + tuple(row.shape[1:]), device=dev)
+            self.temb_row = torch.zeros((1,) + tuple(row.shape[1:]), device=dev)
+        # the local prior hands back its channel-major [B, 4, N] output; the update reads it in that layout (round 6: no
+        # transposing ATen copy at the end of a step)
+        n_pts, n_cls = getattr(model, "num_points", 0), getattr(model, "num_classes", 0)
+        self.cm_out = channel_major(model, shape) and not getattr(model, "mixed_prediction", False)
+
+        def step():
+            extra = {}
+            if self.temb_table is not None:   # the step's time-embedding row, copied by the prologue kernel itself
+                _lib.call("lion_chain_begin_step_temb", self.table, self.capacity, self.counter, self.t, num_samples, self.cur,
+                          self.temb_table, self.temb_row.numel(), self.temb_row)
+                extra["temb"] = self.temb_row
+            else:
+                _lib.call("lion_chain_begin_step", self.table, self.capacity, self.counter, self.t, num_samples, self.cur)
+            if self.cm_out:
+                eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, channel_major_out=True,
+                            **extra).float().contiguous()
+                assert tuple(eps.shape) == (num_samples, n_cls, n_pts)
+                _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
+                          self.z)
+                return
+            eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **extra).float().contiguous()
+            _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
+        self.step = CapturedStep(model, step, self.x, warmup=warmup)
+
     def matches(self, condition_input, clip_feat):
-        same = lambda buf, new: (buf is None) == (new is None) and (buf is None or buf.shape == new.shape)
-        return same(self.cond, condition_input) and same(self.clip, clip_feat) \
-            and self.fingerprint == _wcache.fingerprint(self.model) and self.policy == policy_key()
+        return same_conditioning(self, condition_input, clip_feat) and self.step.valid()
 
     @torch.no_grad()
     def run(self, x_init, table: np.ndarray, seed: int, condition_input=None, clip_feat=None, trajectory=None,
@@ -267,38 +305,20 @@ class GraphedChain:
         return S
 
 
-class ChainCache:
-    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape) -> GraphedChain; a handful of
-    entries (each holds the private memory pool of one forward pass)."""
+for _name in ("replay", "graph", "graphs", "graph_b", "geo_graphs", "pinned", "policy", "fingerprint"):   # the capture's
+    setattr(GraphedChain, _name, property(lambda self, _name=_name: getattr(self.step, _name)))
 
-    def __init__(self, capacity=4):
-        self._entries = {}
-        self._order = []
-        self._capacity = capacity
+
+class ChainCache(LRU):
+    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape) -> GraphedChain"""
 
     def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity):
         rec = RECORD is not None
-        key = (id(model), mode, int(num_samples), tuple(shape), str(device), rec)
-        hit = self._entries.get(key)
-        if hit is not None and hit.model is model and hit.capacity >= table_capacity \
-                and hit.matches(condition_input, clip_feat):
-            self._order.remove(key)
-            self._order.append(key)
-            return hit
-        if hit is not None:
-            del self._entries[key]
-            self._order.remove(key)
-        chain = GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity,
-                             record_noise=rec)
-        self._entries[key] = chain
-        self._order.append(key)
-        while len(self._order) > self._capacity:
-            del self._entries[self._order.pop(0)]
-        return chain
-
-    def clear(self):
-        self._entries.clear()
-        self._order = []
+        return self.lookup(
+            (id(model), mode, int(num_samples), tuple(shape), str(device), rec),
+            lambda hit: hit.model is model and hit.capacity >= table_capacity and hit.matches(condition_input, clip_feat),
+            lambda: GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity,
+                                 record_noise=rec))
 
 
 def draw_seed() -> int:

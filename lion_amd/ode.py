@@ -8,9 +8,9 @@ stage combinations, the error norm and the step-size controller live in device m
     one evaluation      lion_ode_stage -> denoiser forward -> lion_ode_drift        (stage index in device memory)
     one attempted step  6 evaluations -> lion_ode_error_partials -> lion_ode_control -> ONE read of the control struct
 
-With ``graph=True`` an evaluation is lion_ode_stage followed by the replay of [forward -> drift] captured by
-``chain.GraphedChain`` (split geometry stream, ``_wcache.fingerprint`` re-capture, ``policy_key()``); ``graph=False``
-runs the same launches eagerly.  The solver's own reductions have a fixed order (no float atomics): a solve repeats
+With ``graph=True`` an evaluation is lion_ode_stage followed by the replay of [forward -> drift], which ``OdeGraph``
+captures on its own buffers with ``chain.CapturedStep`` (split geometry stream, re-capture when the weights or the
+kernel-selecting switches change); ``graph=False`` runs the same launches eagerly.  The solver's own reductions have a fixed order (no float atomics): a solve repeats
 itself bit for bit whenever the model does.
 """
 from __future__ import annotations
@@ -51,7 +51,7 @@ class OdeState:
     """The device buffers of one solve of n unknowns (B samples): Y f64[2, n], K f64[7, n], the norm partials and the
     control struct, plus a pinned host mirror of the struct and the event the host waits on once per attempted step."""
 
-    def __init__(self, n, B, device, x32=None, t_model=None):
+    def __init__(self, n, B, device):
         self.n, self.B, self.device = int(n), int(B), torch.device(device)
         self.Y = torch.zeros(2, self.n, dtype=torch.float64, device=self.device)
         self.K = torch.zeros(7, self.n, dtype=torch.float64, device=self.device)
@@ -60,8 +60,8 @@ class OdeState:
         self.ctrl = torch.zeros(_CTRL.size, dtype=torch.uint8, device=self.device)
         self.host = torch.zeros(_CTRL.size, dtype=torch.uint8).pin_memory()
         self.event = torch.cuda.Event()
-        self.x32 = x32 if x32 is not None else torch.zeros(self.n, device=self.device)
-        self.t_model = t_model if t_model is not None else torch.zeros(self.B, device=self.device)
+        self.x32 = torch.zeros(self.n, device=self.device)       # the model's inputs, written by the stage kernel
+        self.t_model = torch.zeros(self.B, device=self.device)
 
     def reset(self, y0, t0, t_bound, rtol, atol, sign):
         """solve_ivp(fun, (t0, t_bound), y0, method='RK45', rtol, atol) from stage f0; y0 is widened to float64."""
@@ -71,15 +71,14 @@ class OdeState:
                         sign=float(sign), stage=STAGE_F0)
         self.ctrl.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8), non_blocking=False)
 
-    def stage(self, x32=None, t_model=None):
-        _lib.call("lion_ode_stage", self.Y, self.K, self.n, self.ctrl, self.x32 if x32 is None else x32,
-                  self.t_model if t_model is None else t_model, self.B)
+    def stage(self):
+        _lib.call("lion_ode_stage", self.Y, self.K, self.n, self.ctrl, self.x32, self.t_model, self.B)
 
-    def drift(self, eps, sched, mix=None, cm_points=0, x32=None, t_model=None):
+    def drift(self, eps, sched, mix=None, cm_points=0):
         eps = eps.float().contiguous()
         a, b = (None, None) if mix is None else mix
-        _lib.call("lion_ode_drift", eps, int(cm_points), self.x32 if x32 is None else x32, self.n,
-                  self.t_model if t_model is None else t_model, *sched, a, b, 0 if a is None else a.numel(), self.K, self.ctrl)
+        _lib.call("lion_ode_drift", eps, int(cm_points), self.x32, self.n, self.t_model, *sched, a, b,
+                  0 if a is None else a.numel(), self.K, self.ctrl)
 
     def control(self):
         _lib.call("lion_ode_error_partials", self.Y, self.K, self.n, self.ctrl, self.partials)
@@ -121,10 +120,7 @@ def solve(state: OdeState, evaluate, max_attempts=1_000_000) -> dict:
 
 # ---- the denoiser as the right-hand side ---------------------------------------------------------------------------
 
-def _channel_major(model, shape):
-    n_pts, n_cls = getattr(model, "num_points", 0), getattr(model, "num_classes", 0)
-    return (_chain.CHANNEL_MAJOR_EPS and hasattr(model, "geometry_source") and n_cls == 4
-            and int(np.prod(shape)) == n_pts * n_cls)
+_channel_major = _chain.channel_major   # the chain's rule, without its "not mixed_prediction": the drift mixes itself
 
 
 def _mixing(model, mixing_logit=None):
@@ -138,33 +134,30 @@ def _mixing(model, mixing_logit=None):
 
 
 class OdeGraph:
-    """[stage -> forward -> drift] of one (model, batch shape, schedule) captured once; the solve's buffers belong to it."""
+    """[forward -> drift] of one (model, batch shape, schedule) captured once on this object's buffers: the model's
+    inputs x / t / cond / clip and the solve's OdeState, whose stage kernel writes x and t."""
 
     def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, sched):
         self.model, self.sched = model, sched
         self.cm = _channel_major(model, shape)
-        n = num_samples * int(np.prod(shape))
-        self.state = None
-        self.mix = None
+        self.cond = None if condition_input is None else condition_input.detach().clone().contiguous()
+        self.clip = None if clip_feat is None else clip_feat.detach().clone().contiguous()
+        # the warm-up / capture passes evaluate stage f0 of an all-zero state: finite, and reset before every solve
+        self.state = OdeState(num_samples * int(np.prod(shape)), num_samples, device)
+        self.x, self.t = self.state.x32.view([num_samples] + list(shape)), self.state.t_model
+        self.state.reset(self.x, 1.0, 0.0, 1e-5, 1e-5, 1.0)
+        self.mix = _mixing(model)   # the captured drift reads these two buffers: set_mixing() refreshes them per solve
+        kw = {"channel_major_out": True} if self.cm else {}
 
         # the stage kernel is launched before the replay, not captured: in the split-geometry mode the replay starts the
-        # FPS / ball-query graphs on a second stream from the model input (chain.x), which must already hold this stage
-        def step_fn(ch):
-            st = self.state
-            kw = {"channel_major_out": True} if self.cm else {}
-            pred = model(x=ch.x, t=ch.t, condition_input=ch.cond, clip_feat=ch.clip, **kw)
-            st.drift(pred, self.sched, self.mix, model.num_points if self.cm else 0, ch.x, ch.t)
-
-        # the warm-up / capture passes evaluate stage f0 of an all-zero state: finite, and reset before every solve
-        self.state = OdeState(n, num_samples, device)
-        self.mix = _mixing(model)   # the captured drift reads these two buffers: set_mixing() refreshes them per solve
-        self.state.reset(torch.zeros(n, device=device), 1.0, 0.0, 1e-5, 1e-5, 1.0)
-        self.chain = _chain.GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, _chain.DDIM, 1,
-                                         step_fn=step_fn)
-        self.state.x32, self.state.t_model = self.chain.x.view(-1), self.chain.t
+        # FPS / ball-query graphs on a second stream from the model input (x), which must already hold this stage
+        def step():
+            pred = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **kw)
+            self.state.drift(pred, self.sched, self.mix, model.num_points if self.cm else 0)
+        self.step = _chain.CapturedStep(model, step, self.x)
 
     def matches(self, condition_input, clip_feat, sched):
-        return self.chain.matches(condition_input, clip_feat) and self.sched == sched
+        return _chain.same_conditioning(self, condition_input, clip_feat) and self.step.valid() and self.sched == sched
 
     def set_mixing(self, mixing_logit=None):
         mix = _mixing(self.model, mixing_logit)
@@ -175,8 +168,8 @@ class OdeGraph:
             self.mix[1].copy_(mix[1])
 
     def evaluate(self):
-        self.state.stage(self.chain.x, self.chain.t)
-        self.chain.replay()
+        self.state.stage()
+        self.step.replay()
 
 
 def eager_evaluator(st, model, shape, sched, condition_input=None, clip_feat=None, enable_autocast=False,
@@ -195,24 +188,16 @@ def eager_evaluator(st, model, shape, sched, condition_input=None, clip_feat=Non
     return evaluate
 
 
-_GRAPHS = {}
+_GRAPHS = _chain.LRU()
 
 
 def graph_for(model, num_samples, shape, condition_input, clip_feat, device, sched) -> OdeGraph:
-    key = (id(model), int(num_samples), tuple(shape), str(device))
-    g = _GRAPHS.get(key)
-    if g is not None and g.model is model and g.matches(condition_input, clip_feat, sched):
-        return g
-    _GRAPHS.pop(key, None)
-    g = OdeGraph(model, num_samples, shape, condition_input, clip_feat, device, sched)
-    _GRAPHS[key] = g
-    while len(_GRAPHS) > 4:
-        _GRAPHS.pop(next(iter(_GRAPHS)))
-    return g
+    return _GRAPHS.lookup((id(model), int(num_samples), tuple(shape), str(device)),
+                          lambda g: g.model is model and g.matches(condition_input, clip_feat, sched),
+                          lambda: OdeGraph(model, num_samples, shape, condition_input, clip_feat, device, sched))
 
 
-def clear_graphs():
-    _GRAPHS.clear()
+clear_graphs = _GRAPHS.clear
 
 
 @torch.no_grad()
@@ -222,20 +207,19 @@ def integrate(model, y0, t0, t_bound, sign, rtol, atol, sched, condition_input=N
     torchdiffeq hands them to scipy, ``sign`` = -1 for a reversed span; ``mixing_logit`` overrides the model's own.
     Returns (y at t_bound in fp32, control struct)."""
     B, shape = y0.shape[0], list(y0.shape[1:])
-    dev = y0.device
     use_graph = graph and y0.is_cuda and not enable_autocast
     if use_graph:
-        g = graph_for(model, B, shape, condition_input, clip_feat, dev, sched)
-        if g.chain.cond is not None:
-            g.chain.cond.copy_(condition_input)
-        if g.chain.clip is not None:
-            g.chain.clip.copy_(clip_feat)
+        g = graph_for(model, B, shape, condition_input, clip_feat, y0.device, sched)
+        if g.cond is not None:
+            g.cond.copy_(condition_input)
+        if g.clip is not None:
+            g.clip.copy_(clip_feat)
         g.set_mixing(mixing_logit)
         st = g.state
         st.reset(y0, t0, t_bound, rtol, atol, sign)
         c = solve(st, g.evaluate)
     else:
-        st = OdeState(y0.numel(), B, dev)
+        st = OdeState(y0.numel(), B, y0.device)
         st.reset(y0, t0, t_bound, rtol, atol, sign)
         c = solve(st, eager_evaluator(st, model, shape, sched, condition_input, clip_feat, enable_autocast, mixing_logit))
     return st.result(c).float().view_as(y0).clone(), c

@@ -95,8 +95,8 @@ def bench(args):
         B = z.shape[0]
         with torch.no_grad():
             g = ode.graph_for(model, B, shape, cond, None, z.device, sched)
-            if g.chain.cond is not None:
-                g.chain.cond.copy_(cond)
+            if g.cond is not None:
+                g.cond.copy_(cond)
             g.state.reset(z, t0, tb, args.tol, args.tol, sign)      # stage f0 repeated: drift does not advance it
             graphed = ms_per(g.evaluate, args.evals)
             st = ode.OdeState(z.numel(), B, z.device)
