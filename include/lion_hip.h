@@ -562,6 +562,26 @@ int lion_adam_row(void);
 int lion_adam_step(const uint64_t *table, const int32_t *numel, const int32_t *blockmap, int blocks, int tensors, const float *lr,
                    float beta1, float beta2, float eps, float weight_decay, float ema_decay, lionStream_t stream);
 
+/* ---- global gradient-norm clipping in front of the update (reference trainers/hvae_trainer.py:124-126, train_2prior.py:336-339:
+ * torch.nn.utils.clip_grad_norm_(params, max_norm), error_if_nonfinite=False) over the SAME table / numel / blockmap, without
+ * float atomics: the same gradients give the same bits on every rank.
+ * lion_grad_sqnorm_partials: partials f32[blocks], one per blockmap row = the fp32 sum of squares of that chunk of the gradient
+ *   (column 1 of the table row; nothing else is read, nothing else written).  Several tables (parameter groups) write into slices
+ *   of one partials buffer.
+ * lion_grad_clip_coef: ONE norm over partials[0..n), added in double in a fixed order; out2 f32[2] (device) = {norm, coef},
+ *   norm = (float)sqrt(sum), coef = min(1, max_norm / (norm + 1e-6f)) in fp32 with a correctly rounded division (torch's
+ *   `max_norm / (total_norm + 1e-6)` is reciprocal * max_norm: up to 1 ulp apart).  A NaN norm gives a NaN coefficient, an infinite
+ *   norm 0, as torch's clamp(max=1.0) does.  max_norm > 0.
+ * lion_adam_step_scaled: lion_adam_step with the gradient multiplied by grad_scale[0] (device; out2 + 1 above) in registers, one
+ *   fp32 rounding, before the weight-decay term -- the gradient in memory is NOT rewritten, unlike clip_grad_norm_'s in-place
+ *   multiply.  grad_scale NULL: lion_adam_step, bit for bit. */
+int lion_grad_sqnorm_partials(const uint64_t *table, const int32_t *numel, const int32_t *blockmap, int blocks, float *partials,
+                              lionStream_t stream);
+int lion_grad_clip_coef(const float *partials, int n, float max_norm, float *out2, lionStream_t stream);
+int lion_adam_step_scaled(const uint64_t *table, const int32_t *numel, const int32_t *blockmap, int blocks, int tensors,
+                          const float *lr, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                          const float *grad_scale, lionStream_t stream);
+
 /* ---- probability-flow ODE of the VPSDE: scipy's RK45 on the device (csrc/ode.hip) --------------------------------------
  * utils/diffusion_continuous.py:90-255 (compute_ode_nll / sample_model_ode) hand the PF-ODE of the whole batch -- ONE system
  * of n = B*D unknowns -- to scipy.integrate.solve_ivp(method='RK45') (rk.py RK45._step_impl, common.py select_initial_step)

@@ -110,6 +110,9 @@ SIGNATURES = {
     "lion_adam_chunk": (_i, []),
     "lion_adam_row": (_i, []),
     "lion_adam_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _f, _f, _f, _f, _f, _vp]),
+    "lion_grad_sqnorm_partials": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "lion_grad_clip_coef": (_i, [_vp, _i, _f, _vp, _vp]),
+    "lion_adam_step_scaled": (_i, [_vp, _vp, _vp, _i, _i, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
     "lion_se_gate_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lion_se_gate_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lion_rows_dot2": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -10,7 +10,21 @@ captured step replays: call ``sync_lr()`` after changing ``group['lr']`` when st
 (utils/ema.py:31-89, ``state[p]['ema']``; decay 0.9999 in every released config) is updated by the same launch -- the wrapper's
 form is a stack, a multiply-add and an unstack per parameter shape after the step.  ``lion_amd.training.EMA`` around this optimizer
 hands its decay over and keeps ``swap_parameters_with_ema``.  float32 HIP parameters only -- anything else is an error, not a
-fallback."""
+fallback.
+
+``max_grad_norm > 0``: global gradient-norm clipping in front of the update -- what the reference's trainers do with
+``torch.nn.utils.clip_grad_norm_(params, max_norm)`` between the gradient averaging and ``optimizer.step()``
+(trainers/hvae_trainer.py:124-126, ``trainer.opt.grad_clip``; train_2prior.py:336-339, ``sde.grad_clip_max_norm``).  ONE norm over
+the gradients of every param group (parameters without a gradient take no part): a read-only pass over the same pointer tables
+leaves one fp32 sum of squares per 4096-element chunk, one workgroup adds them in double in a fixed order and writes
+``norm = sqrt(sum)`` and ``coef = min(1, max_norm / (norm + 1e-6))`` (fp32; no float atomics, so every rank of a data-parallel run
+gets the same bits from the same averaged gradients), and the update multiplies each gradient by ``coef`` in registers before the
+weight-decay term.  Two differences from ``clip_grad_norm_``: ``p.grad`` is NOT rewritten (the clipped gradient exists only inside
+the update), and the division is a correctly rounded one where torch's ``max_norm / (total_norm + 1e-6)`` is
+``reciprocal * max_norm`` (up to 1 ulp of the coefficient apart).  Non-finite gradients follow ``error_if_nonfinite=False``: an
+infinite norm gives coefficient 0, a NaN norm NaN.  ``opt.grad_norm`` is the norm before clipping of the last step, a 0-d device
+tensor (what ``clip_grad_norm_`` returns); reading it is the caller's synchronisation.  ``get_opt`` builds the optimizer from a
+``trainer.opt`` config (reference utils/utils.py:115-138), ``grad_clip`` included."""
 from __future__ import annotations
 
 import numpy as np
@@ -24,10 +38,16 @@ class _Plan:
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, max_grad_norm=None):
         if not 0.0 <= ema_decay <= 1.0:
             raise ValueError(f"Invalid ema_decay: {ema_decay}")
         self.ema_decay = float(ema_decay)
+        if max_grad_norm is not None and max_grad_norm != max_grad_norm:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        # None or <= 0 (the reference's configs say -1): no clipping, the launches of an optimizer without the argument
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm is not None and max_grad_norm > 0 else None
+        self._partials = None  # f32[>= chunks of all groups]: one sum of squares per chunk
+        self._clip = None      # f32[2]: {norm, coef} of the last step
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
@@ -62,10 +82,19 @@ class Adam(torch.optim.Optimizer):
             if ps:
                 self._lr(gi, group, ps[0].device)
 
+    @property
+    def grad_norm(self):
+        """global norm of the gradients of the last ``step()`` before clipping (0-d device tensor, a view of the optimizer's own
+        buffer: the next step overwrites it); None without ``max_grad_norm`` or before the first step"""
+        return None if self._clip is None else self._clip[0]
+
     # -- the pointer table ------------------------------------------------------------------------------------------------
     def _plan(self, gi, ps, grads, dev):
         ema = self.ema_decay > 0.0
-        key = tuple((p.data_ptr(), g.data_ptr(), p.numel(), self.state[p]["ema"].data_ptr() if ema else 0) for p, g in zip(ps, grads))
+        # every address the table holds: load_state_dict replaces the moments and the step counts under unchanged gradients
+        key = tuple((p.data_ptr(), g.data_ptr(), p.numel(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                     st["step"].data_ptr(), st["ema"].data_ptr() if ema else 0)
+                    for p, g, st in ((p, g, self.state[p]) for p, g in zip(ps, grads)))
         plan = self._plans.get(gi)
         if plan is not None and plan.key == key:
             return plan
@@ -106,6 +135,7 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        work = []
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -135,8 +165,51 @@ class Adam(torch.optim.Optimizer):
                     # state that arrives with steps already taken but no average (a plain Adam checkpoint) starts from the
                     # parameter as it is
                     st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
-            plan = self._plan(gi, ps, grads, dev)
+            work.append((gi, group, len(ps), self._plan(gi, ps, grads, dev), dev))
+        coef = None
+        if self.max_grad_norm is not None and work:
+            # ONE norm over every group: each group's chunks into its slice of the partials, one finalising launch over all of them
+            dev = work[0][4]
+            if any(w[4] != dev for w in work):
+                raise RuntimeError("lion_amd.optim.Adam: max_grad_norm needs every param group on one device")
+            total = sum(w[3].blocks for w in work)
+            if self._clip is None or self._clip.device != dev:
+                self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
+                self._partials = None
+            if self._partials is None or self._partials.numel() < total:   # sized with the plans: fixed addresses under replay
+                self._partials = torch.empty(total, dtype=torch.float32, device=dev)
+            off = 0
+            for _, _, _, plan, _ in work:
+                _lib.call("lion_grad_sqnorm_partials", plan.table, plan.numel, plan.blockmap, plan.blocks,
+                          self._partials[off:off + plan.blocks])
+                off += plan.blocks
+            _lib.call("lion_grad_clip_coef", self._partials, total, self.max_grad_norm, self._clip)
+            coef = self._clip[1:]
+        for gi, group, T, plan, dev in work:
             b1, b2 = group["betas"]
-            _lib.call("lion_adam_step", plan.table, plan.numel, plan.blockmap, plan.blocks, len(ps), self._lr(gi, group, dev),
-                      float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), self.ema_decay)
+            args = (plan.table, plan.numel, plan.blockmap, plan.blocks, T, self._lr(gi, group, dev), float(b1), float(b2),
+                    float(group["eps"]), float(group["weight_decay"]), self.ema_decay)
+            if coef is None:
+                _lib.call("lion_adam_step", *args)
+            else:
+                _lib.call("lion_adam_step_scaled", *args, coef)
         return loss
+
+
+def get_opt(params, cfgopt, use_ema=False, grad_clip=None):
+    """The optimizer of a ``trainer.opt`` config -- the Adam branch of the reference's utils/utils.py:115-138: ``lr``,
+    ``(beta1, beta2)`` and ``weight_decay`` from ``cfgopt``, wrapped in ``lion_amd.training.EMA`` when ``use_ema`` (decay
+    ``cfgopt.ema_decay`` if the config has one, else the reference's 0.9999).  ``max_grad_norm`` is ``grad_clip`` if given (the
+    prior trainers pass ``cfg.sde.grad_clip_max_norm``), else ``cfgopt.grad_clip``; <= 0 (the released configs' -1) disables
+    clipping.  The reference's other optimizer types are not implemented here."""
+    kind = getattr(cfgopt, "type", None)
+    if kind != "adam":
+        raise NotImplementedError(f"lion_amd.optim.get_opt: optimizer type {kind!r} (only 'adam')")
+    if grad_clip is None:
+        grad_clip = getattr(cfgopt, "grad_clip", None)
+    opt = Adam(params, lr=float(cfgopt.lr), betas=(float(cfgopt.beta1), float(cfgopt.beta2)),
+               weight_decay=float(cfgopt.weight_decay), max_grad_norm=None if grad_clip is None else float(grad_clip))
+    if use_ema:
+        from .training import EMA
+        opt = EMA(opt, float(getattr(cfgopt, "ema_decay", 0.9999)))
+    return opt

@@ -340,6 +340,11 @@ class EMA(torch.optim.Optimizer):
     def zero_grad(self, set_to_none=True):
         return self.optimizer.zero_grad(set_to_none=set_to_none)
 
+    @property
+    def grad_norm(self):
+        """the wrapped optimizer's pre-clip gradient norm of the last step (lion_amd.optim.Adam(max_grad_norm=...)), else None"""
+        return getattr(self.optimizer, "grad_norm", None)
+
     def state_dict(self):
         return self.optimizer.state_dict()
 
