@@ -154,6 +154,23 @@ int lion_chamfer_forward(const float *xyz1, const float *xyz2, int B, int N, int
 int lion_chamfer_backward(const float *xyz1, const float *xyz2, const float *gdist1,
                           const float *gdist2, const int32_t *idx1, const int32_t *idx2, int B,
                           int N, int M, float *gxyz1, float *gxyz2, lionStream_t stream);
+/* Chamfer reconstruction loss (utils/model_helper.py:43-52: 'chamfer' = the mean over points of both directions, 'cd_sum' = their
+ * sum) on top of lion_chamfer_forward's outputs, and its gradient without atomics (stands for chamfer3D.cu:155-185 under that loss).
+ * loss_reduce: loss f32[B], loss[b] = s1 * sum_j dist1[b,j] + s2 * sum_k dist2[b,k]; fixed order: a lane adds dist[b, t], [t + 256],
+ *   ... in fp32 (the longest chain has P = ceil(max(N,M) / 256) terms), the 256 lane sums of each direction are added in double by a
+ *   fixed tree, loss[b] = (float)((double)s1 * S1 + (double)s2 * S2).
+ * loss_backward: gloss f32[B] (device memory) = d(objective)/d(loss); gxyz1 f32[B,N,3] / gxyz2 f32[B,M,3] are fully written by plain
+ *   stores (no pre-zeroing); either may be NULL and that direction is skipped (both NULL: LION_EINVAL).  Gather form, one rounding
+ *   per written operation, c1 = 2 * (gloss[b] * s1), c2 = 2 * (gloss[b] * s2):
+ *     gxyz1[b,j] = c1 * (x1[j] - x2[idx1[j]])                 -- the own term first
+ *                  + c2 * (x1[j] - x2[k])  for every k with idx2[b,k] == j, added one by one in ascending k (a single fp32 chain)
+ *     gxyz2[b,k] = c2 * (x2[k] - x1[idx2[k]])  + c1 * (x2[k] - x1[j])  for every j with idx1[b,j] == k, in ascending j
+ *   -> the same bits on every run and on every rank; lion_chamfer_backward's float atomics add in arrival order. */
+int lion_chamfer_loss_reduce(const float *dist1, const float *dist2, int B, int N, int M, float s1,
+                             float s2, float *loss, lionStream_t stream);
+int lion_chamfer_loss_backward(const float *xyz1, const float *xyz2, const int32_t *idx1,
+                               const int32_t *idx2, const float *gloss, int B, int N, int M, float s1,
+                               float s2, float *gxyz1, float *gxyz2, lionStream_t stream);
 
 /* ---- E2: emd_ext.approxmatch_forward / matchcost_forward / matchcost_backward ------------
  * PyTorchEMD/cuda/emd.cpp:7-27 (emd_kernel.cu:24-156, :199-241, :285-353).

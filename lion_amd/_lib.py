@@ -40,6 +40,8 @@ SIGNATURES = {
     "lion_three_nn_interpolate_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lion_chamfer_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "lion_chamfer_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "lion_chamfer_loss_reduce": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
+    "lion_chamfer_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "lion_emd_workspace_bytes": (_sz, [_i, _i, _i]),
     "lion_emd_approxmatch": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "lion_emd_cost": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),

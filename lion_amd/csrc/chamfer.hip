@@ -135,6 +135,120 @@ __global__ void chamfer_grad_scatter_kernel(const float *__restrict__ xa,
   atomicAdd(o + 2, -mul_rn(g, sub_rn(pa[2], pb[2])));
 }
 
+// ---- Chamfer reconstruction loss (utils/model_helper.py:43-52 on top of chamfer_fwd_kernel's outputs) ------------------------
+// Loss value: loss[b] = s1 * sum_j dist1[b,j] + s2 * sum_k dist2[b,k], one workgroup per cloud pair, no atomics:
+//   lane t:  a1 = dist1[b,t];  a1 = add_rn(a1, dist1[b, t + CHL_LANES]);  ... ascending  (likewise a2 over dist2)
+//   S1, S2:  the CHL_LANES lane sums added in double by a fixed LDS tree (the pattern of grad_clip_coef_kernel)
+//   loss[b] = (float)((double)s1 * S1 + (double)s2 * S2)
+// The longest fp32 chain of a lane has P = ceil(max(N, M) / CHL_LANES) terms (chl_chain_P): what the tests size their bound by.
+constexpr int CHL_LANES = 256;
+constexpr int chl_chain_P(int N, int M) { return ((N > M ? N : M) + CHL_LANES - 1) / CHL_LANES; }
+
+__global__ __launch_bounds__(CHL_LANES) void chamfer_loss_reduce_kernel(const float *__restrict__ dist1,
+                                                                        const float *__restrict__ dist2, int N, int M,
+                                                                        float s1, float s2, float *__restrict__ loss) {
+  __shared__ double sh1[CHL_LANES], sh2[CHL_LANES];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const float *d1 = dist1 + (size_t)b * N, *d2 = dist2 + (size_t)b * M;
+  float a1 = 0.f, a2 = 0.f;
+  if (tid < N) {
+    a1 = d1[tid];
+    for (int j = tid + CHL_LANES; j < N; j += CHL_LANES) a1 = add_rn(a1, d1[j]);
+  }
+  if (tid < M) {
+    a2 = d2[tid];
+    for (int k = tid + CHL_LANES; k < M; k += CHL_LANES) a2 = add_rn(a2, d2[k]);
+  }
+  sh1[tid] = (double)a1;
+  sh2[tid] = (double)a2;
+  __syncthreads();
+  for (int s = CHL_LANES / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      sh1[tid] += sh1[tid + s];
+      sh2[tid] += sh2[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) loss[b] = (float)((double)s1 * sh1[0] + (double)s2 * sh2[0]);
+}
+
+// Gradient of that loss in GATHER form: one lane owns one receiving point and every output element is stored once with a plain
+// store (torch.empty buffers, no pre-zeroing, no atomics -> the same bits on every run; chamfer_grad_scatter_kernel's float
+// atomics add in arrival order).  With g = gloss[b] read from device memory (a captured step replays it),
+//   c1 = mul_rn(2, mul_rn(g, s1)),  c2 = mul_rn(2, mul_rn(g, s2))
+// and per coordinate x (y, z alike), one rounding per written operation:
+//   gxyz1[b,j].x:  acc = mul_rn(c1, sub_rn(x1[j].x, x2[idx1[j]].x))                             -- own term first
+//                  for k = 0 .. M-1 ascending, where idx2[b,k] == j:
+//                    acc = add_rn(acc, mul_rn(c2, sub_rn(x1[j].x, x2[k].x)))                    -- one fp32 chain
+//   gxyz2[b,k].x:  acc = mul_rn(c2, sub_rn(x2[k].x, x1[idx2[k]].x))
+//                  for j = 0 .. N-1 ascending, where idx1[b,j] == k:
+//                    acc = add_rn(acc, mul_rn(c1, sub_rn(x2[k].x, x1[j].x)))
+// The scan stages the other cloud's coordinates and its arg-min indices in LDS tiles of CH_TILE points (as the forward stages
+// its targets); a lane reads four indices per LDS access and a wave-wide "any lane matched" test skips the arithmetic for
+// the great majority of them: N * M index compares per direction, next to the forward's N * M distance evaluations.
+// blockIdx.z + dir0 is the direction (0: gxyz1, 1: gxyz2), so a caller that needs one gradient launches one.
+__global__ __launch_bounds__(256) void chamfer_loss_bwd_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2,
+                                                               const int32_t *__restrict__ idx1,
+                                                               const int32_t *__restrict__ idx2,
+                                                               const float *__restrict__ gloss, int N, int M, float s1,
+                                                               float s2, float *__restrict__ gxyz1,
+                                                               float *__restrict__ gxyz2, int dir0) {
+  __shared__ __attribute__((aligned(16))) int sidx[CH_TILE];
+  __shared__ float sxyz[CH_TILE * 3];
+  const int tid = threadIdx.x, b = blockIdx.y, dir = blockIdx.z + dir0;
+  const int nr = dir == 0 ? N : M, no = dir == 0 ? M : N; // receiving cloud, other cloud
+  if (blockIdx.x * 256 >= nr) return;                     // uniform per block
+  const float *xr = (dir == 0 ? xyz1 : xyz2) + (size_t)b * nr * 3;
+  const float *xo = (dir == 0 ? xyz2 : xyz1) + (size_t)b * no * 3;
+  const int32_t *ir = (dir == 0 ? idx1 : idx2) + (size_t)b * nr; // the receiver's own arg-min, into the other cloud
+  const int32_t *io = (dir == 0 ? idx2 : idx1) + (size_t)b * no; // the other cloud's arg-mins, into the receiving cloud
+  float *out = (dir == 0 ? gxyz1 : gxyz2) + (size_t)b * nr * 3;
+  const float g = gloss[b];
+  const float c_own = mul_rn(2.0f, mul_rn(g, dir == 0 ? s1 : s2));
+  const float c_oth = mul_rn(2.0f, mul_rn(g, dir == 0 ? s2 : s1));
+
+  const int j0 = blockIdx.x * 256 + tid;
+  const bool live = j0 < nr;
+  const int j = live ? j0 : -1; // staged indices are >= 0 or the pad value -2: a dead lane never matches
+  float px = 0.f, py = 0.f, pz = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
+  if (live) {
+    px = xr[(size_t)j * 3]; py = xr[(size_t)j * 3 + 1]; pz = xr[(size_t)j * 3 + 2];
+    const int o = min(max(ir[j], 0), no - 1);
+    ax = mul_rn(c_own, sub_rn(px, xo[(size_t)o * 3]));
+    ay = mul_rn(c_own, sub_rn(py, xo[(size_t)o * 3 + 1]));
+    az = mul_rn(c_own, sub_rn(pz, xo[(size_t)o * 3 + 2]));
+  }
+  for (int t0 = 0; t0 < no; t0 += CH_TILE) {
+    const int tn = min(CH_TILE, no - t0), tn4 = (tn + 3) & ~3; // tn4 <= CH_TILE: CH_TILE is a multiple of 4
+    __syncthreads();
+    for (int k = tid; k < tn4; k += 256) sidx[k] = k < tn ? io[t0 + k] : -2;
+    for (int i = tid; i < tn * 3; i += 256) sxyz[i] = xo[(size_t)t0 * 3 + i];
+    __syncthreads();
+    for (int k = 0; k < tn4; k += 4) {
+      const int4 i4 = *reinterpret_cast<const int4 *>(&sidx[k]);
+      const bool m0 = i4.x == j, m1 = i4.y == j, m2 = i4.z == j, m3 = i4.w == j;
+      if (__any(m0 | m1 | m2 | m3)) {
+#define LION_CHL_TERM(m, kk)                                                  \
+  if (m) {                                                                    \
+    ax = add_rn(ax, mul_rn(c_oth, sub_rn(px, sxyz[(kk) * 3])));               \
+    ay = add_rn(ay, mul_rn(c_oth, sub_rn(py, sxyz[(kk) * 3 + 1])));           \
+    az = add_rn(az, mul_rn(c_oth, sub_rn(pz, sxyz[(kk) * 3 + 2])));           \
+  }
+        LION_CHL_TERM(m0, k)
+        LION_CHL_TERM(m1, k + 1)
+        LION_CHL_TERM(m2, k + 2)
+        LION_CHL_TERM(m3, k + 3)
+#undef LION_CHL_TERM
+      }
+    }
+  }
+  if (live) {
+    out[(size_t)j * 3] = ax;
+    out[(size_t)j * 3 + 1] = ay;
+    out[(size_t)j * 3 + 2] = az;
+  }
+}
+
 } // namespace
 
 extern "C" {
@@ -162,6 +276,27 @@ int lion_chamfer_backward(const float *xyz1, const float *xyz2, const float *gdi
   chamfer_grad_own_kernel<<<dim3(lion_cdiv(M, 256), B), 256, 0, st>>>(xyz2, xyz1, gdist2, idx2, M, N, gxyz2);
   chamfer_grad_scatter_kernel<<<dim3(lion_cdiv(N, 256), B), 256, 0, st>>>(xyz1, xyz2, gdist1, idx1, N, M, gxyz2);
   chamfer_grad_scatter_kernel<<<dim3(lion_cdiv(M, 256), B), 256, 0, st>>>(xyz2, xyz1, gdist2, idx2, M, N, gxyz1);
+  LION_LAUNCH_CHECK();
+  return 0;
+}
+
+int lion_chamfer_loss_reduce(const float *dist1, const float *dist2, int B, int N, int M, float s1, float s2, float *loss,
+                             lionStream_t stream) {
+  if (!dist1 || !dist2 || !loss || B <= 0 || N <= 0 || M <= 0) return LION_EINVAL;
+  chamfer_loss_reduce_kernel<<<B, CHL_LANES, 0, static_cast<hipStream_t>(stream)>>>(dist1, dist2, N, M, s1, s2, loss);
+  LION_LAUNCH_CHECK();
+  return 0;
+}
+
+int lion_chamfer_loss_backward(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
+                               const float *gloss, int B, int N, int M, float s1, float s2, float *gxyz1, float *gxyz2,
+                               lionStream_t stream) {
+  if (!xyz1 || !xyz2 || !idx1 || !idx2 || !gloss || (!gxyz1 && !gxyz2) || B <= 0 || N <= 0 || M <= 0)
+    return LION_EINVAL;
+  const int dir0 = gxyz1 ? 0 : 1, ndir = (gxyz1 && gxyz2) ? 2 : 1; // a NULL gradient: that direction is not launched
+  const int nmax = ndir == 2 ? (N > M ? N : M) : (dir0 == 0 ? N : M);
+  chamfer_loss_bwd_kernel<<<dim3(lion_cdiv(nmax, 256), B, ndir), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      xyz1, xyz2, idx1, idx2, gloss, N, M, s1, s2, gxyz1, gxyz2, dir0);
   LION_LAUNCH_CHECK();
   return 0;
 }
