@@ -323,7 +323,7 @@ int lion_conv3d_k3_split_forward(const float *x, const uint16_t *wp, const float
                                  const float *tconst, float *y, float *stats, int32_t *occ, lionStream_t stream);
 /* ---- C3 at reduced precision, on purpose (csrc/conv3d_half.hip) ----------------------------------------------
  * lion_conv3d_k3_split_forward with ONE fp16 product per operand pair (main += W_h X_h, no low pieces, no corr): a third
- * of the MFMAs.  Same arguments, same modes (prologue, tile sums, occ / tconst, consumer-aware levels), same tile geometry
+ * of the MFMAs -- the P = 1 instantiation of the split kernel (csrc/conv3d_split_kernel.h).  Same arguments, same modes (prologue, tile sums, occ / tconst, consumer-aware levels), same tile geometry
  * (stats has lion_conv3d_split_stat_tiles(r, Cout) tiles) and the SAME packed weights -- wp from
  * lion_conv3d_split_pack_weights, of which only the hi pieces and the scale are read.  With the block scaling a hi piece is
  * the operand rounded to an 11-bit significand, so the result is conv(rne11(W), rne11(act(X))) accumulated in fp32:

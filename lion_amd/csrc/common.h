@@ -33,6 +33,20 @@ static inline int lion_current_device(int *dev) {
   if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= LION_MAX_DEVICES) return LION_EINVAL;
   return 0;
 }
+// Compute units of the current device, asked of the runtime once per device (hipGetDeviceProperties is slow): what a
+// persistent (work-queue) launch sizes its grid by.
+static inline int lion_cu_count(int *n) {
+  static int cu_count[LION_MAX_DEVICES] = {0};
+  int dev = 0;
+  if (int e = lion_current_device(&dev)) return e;
+  if (!cu_count[dev]) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return LION_EINVAL;
+    cu_count[dev] = prop.multiProcessorCount;
+  }
+  *n = cu_count[dev];
+  return 0;
+}
 template <typename K>
 static inline int lion_dynamic_lds(K kernel, size_t bytes, LionLdsLimit &limit) {
   int dev = 0;

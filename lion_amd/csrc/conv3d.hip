@@ -553,15 +553,8 @@ static int launch_conv_t(const float *x, const float *wp, const float *bias, flo
                          int Cout, int r, const float *pa, const float *pb, const float *pbias, const float *tconst,
                          float *stats, int32_t *occ, hipStream_t st) {
   const int tiles = (r / TD) * (r / TH) * (r / TW);
-  static int cu_count[LION_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (int e = lion_current_device(&dev)) return e;
-  if (!cu_count[dev]) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return LION_EINVAL;
-    cu_count[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = cu_count[dev];
+  int n_cu = 0;
+  if (int e = lion_cu_count(&n_cu)) return e;
   const long items = (long)B * tiles * (Cout / COT);
   const dim3 grid = occ ? dim3((unsigned)(items < 2L * n_cu ? items : 2L * n_cu)) : dim3(B, tiles, Cout / COT);
   constexpr int NT = 256;

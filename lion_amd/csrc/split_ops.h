@@ -49,6 +49,12 @@ __device__ __forceinline__ void cut2(float a, float b, unsigned &hi2, unsigned &
   hi2 = __builtin_bit_cast(unsigned, h);
   lo2 = __builtin_bit_cast(unsigned, l);
 }
+// the hi pieces of a pair alone: the first conversion of cut2, bit for bit (v_cvt_pk_f16_f32, round to nearest even)
+__device__ __forceinline__ unsigned hi2(float a, float b) {
+  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+  typedef float f2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_t{a, b}, h2_t));
+}
 __device__ __forceinline__ f32x16 mma(u4 a, u4 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
 }

@@ -29,7 +29,7 @@ def kernels(tmp_path_factory):
                           cwd=CSRC, stderr=subprocess.DEVNULL)
     listing = open(out).read()
     found = []
-    for m in re.finditer(r'^(\S*conv3d_half_kernelILi\S*):', listing, re.M):
+    for m in re.finditer(r'^(\S*conv3d_split_kernelILi\S*):', listing, re.M):
         end = re.compile(r'^\.Lfunc_end\d+:', re.M).search(listing, m.end()).start()
         body = [ln.strip().split(';')[0].strip() for ln in listing[m.end():end].split('\n')]
         found.append((m.group(1), [ln for ln in body if ln]))
