@@ -217,6 +217,11 @@ __global__ __launch_bounds__(256) void concat_broadcast_kernel(const float *__re
 
 } // namespace
 
+// The (batch, channel) row rides on blockIdx.y, and 65535 is the largest gridDim.y that is portable (B = 128 at the 512
+// channels of the last SA stage is 65536 rows): more rows go out in chunks of that many, each on offset pointers.  Up to
+// 65535 rows this is the one launch it always was.
+constexpr int kMaxGridY = 65535;
+
 extern "C" {
 
 // x f32[rows, L] (rows = B*C) -> stats f32[rows, 2] (== the [B,C,T=1,2] layout of lion_groupnorm_fold)
@@ -230,9 +235,13 @@ int lion_row_stats(const float *x, int rows, int L, float *stats, lionStream_t s
 int lion_affine_swish(const float *x, const float *A, const float *Bs, int rows, int L, float *y,
                       lionStream_t stream) {
   if (!x || !A || !Bs || !y || rows <= 0 || L <= 0) return LION_EINVAL;
-  affine_swish_kernel<<<dim3(lion_cdiv(lion_cdiv(L, 4), 256), rows), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      x, A, Bs, L, y);
-  LION_LAUNCH_CHECK();
+  for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
+    const int nr = rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY;
+    const size_t off = (size_t)r0 * L;
+    affine_swish_kernel<<<dim3(lion_cdiv(lion_cdiv(L, 4), 256), nr), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        x + off, A + r0, Bs + r0, L, y + off);
+    LION_LAUNCH_CHECK();
+  }
   return 0;
 }
 
@@ -247,9 +256,13 @@ int lion_timestep_embedding(const float *t, const float *row, float scale, int B
 int lion_affine_swish_add(const float *x, const float *A, const float *Bs, const float *addend, int rows, int L, float *y,
                           lionStream_t stream) {
   if (!x || !A || !Bs || !addend || !y || rows <= 0 || L <= 0) return LION_EINVAL;
-  affine_swish_add_kernel<<<dim3(lion_cdiv(lion_cdiv(L, 4), 256), rows), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      x, A, Bs, addend, L, y);
-  LION_LAUNCH_CHECK();
+  for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
+    const int nr = rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY;
+    const size_t off = (size_t)r0 * L;
+    affine_swish_add_kernel<<<dim3(lion_cdiv(lion_cdiv(L, 4), 256), nr), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        x + off, A + r0, Bs + r0, addend + off, L, y + off);
+    LION_LAUNCH_CHECK();
+  }
   return 0;
 }
 
@@ -257,15 +270,20 @@ int lion_affine_swish_max(const float *x, const float *A, const float *Bs, int r
                           float *y, lionStream_t stream) {
   if (!x || !A || !Bs || !y || rows <= 0 || M <= 0 || U <= 0) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool al = (((uintptr_t)x) & 15) == 0;
+  const bool al = (((uintptr_t)x) & 15) == 0; // a chunk starts 65535 * M * U floats on: 16-byte aligned when U % 4 == 0
 #define LION_ASM_COOP(LPM_)                                                                                  \
-  affine_swish_max_coop_kernel<LPM_><<<dim3(lion_cdiv(M, 4 * (64 / LPM_) * 8), rows), 256, 0, st>>>(x, A, Bs, M, y)
-  if (al && U == 32) LION_ASM_COOP(8);
-  else if (al && U == 16) LION_ASM_COOP(4);
-  else if (al && U == 64) LION_ASM_COOP(16);
-  else affine_swish_max_kernel<<<dim3(lion_cdiv(M, 256), rows), 256, 0, st>>>(x, A, Bs, M, U, y);
+  affine_swish_max_coop_kernel<LPM_><<<dim3(lion_cdiv(M, 4 * (64 / LPM_) * 8), nr), 256, 0, st>>>(xc, A + r0, Bs + r0, M, yc)
+  for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
+    const int nr = rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY;
+    const float *xc = x + (size_t)r0 * M * U;
+    float *yc = y + (size_t)r0 * M;
+    if (al && U == 32) LION_ASM_COOP(8);
+    else if (al && U == 16) LION_ASM_COOP(4);
+    else if (al && U == 64) LION_ASM_COOP(16);
+    else affine_swish_max_kernel<<<dim3(lion_cdiv(M, 256), nr), 256, 0, st>>>(xc, A + r0, Bs + r0, M, U, yc);
+    LION_LAUNCH_CHECK();
+  }
 #undef LION_ASM_COOP
-  LION_LAUNCH_CHECK();
   return 0;
 }
 
