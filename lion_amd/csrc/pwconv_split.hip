@@ -19,6 +19,14 @@
 // tensor; a workgroup's slice of a chunk (64 B x channels) travels by LDS-DMA D chunks ahead (ring of D + 1), the
 // activation rows D chunks ahead in registers; one barrier per chunk.
 // A wave owns VB x 32 columns x CB x 32 channels; 4 waves = 128 VB columns per workgroup.
+//
+// WIDE (L % 4 == 0, x and y 16-byte aligned; chosen by the launcher): the activation moves in 16-byte pieces.  A chunk's
+// 16 rows x 128 VB columns travel by range-checked 16-byte LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave
+// instruction: 2 VB per wave and chunk instead of 8 VB dword loads) into the ring slot behind the chunk's weight slice,
+// and each lane reads its 8 k-values of its column from there (ds_read_b32, 32 consecutive floats per half-wave:
+// conflict-free).  The results leave through the wave's 32 x 36 LDS transposition that the statistics use, as 16-byte
+// stores (8 lanes = 128 contiguous bytes of one channel row).  Per column the arithmetic is the narrow path's, value for
+// value: y and stats are bit-identical.  The narrow instantiation stays as the fallback for every other L / alignment.
 #include "split_ops.h"
 
 namespace {
@@ -30,7 +38,7 @@ __device__ unsigned long long g_pws_t[128];
 #define PWS_T(i) do { } while (0)
 #endif
 
-template <int CB, int VB, bool PRO, bool STATS, int NR>
+template <int CB, int VB, bool PRO, bool STATS, int NR, bool WIDE>
 __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__restrict__ x, const u4 *__restrict__ wp,
                                                            const float *__restrict__ wtail,
                                                            const float *__restrict__ bias, float *__restrict__ y,
@@ -39,11 +47,14 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
                                                            const float *__restrict__ pro_b, float *__restrict__ stats) {
   constexpr int COT = 32 * CB, WPL = 4 * COT;        // u4 per chunk slice: [piece][k-half][COT]
   constexpr int NDMA = WPL / 64, DMIN = NDMA / 4;    // wave instructions per slice; at least DMIN by every wave
+  constexpr int XROW = 128 * VB;                     // WIDE: floats per activation row of a ring slot
+  constexpr int XDMA = WIDE ? 2 * VB : 0;            // WIDE: row instructions per wave and chunk (16 rows x XROW floats / 4 KiB)
+  constexpr int SLOT = WPL + (WIDE ? KS * XROW / 4 : 0); // u4 per ring slot: weight slice, then [16][XROW] activation rows
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int D = NR - 1;                          // prefetch distance in chunks (rows in registers, slices in LDS)
-  u4 *sw = reinterpret_cast<u4 *>(smem);             // [NR][WPL]
+  u4 *sw = reinterpret_cast<u4 *>(smem);             // [NR][SLOT]
   const int nchunks = (Cin + KS - 1) / KS;
-  constexpr int RING_U4 = NR * WPL > 4 * 32 * 9 ? NR * WPL : 4 * 32 * 9; // the statistics reuse the ring: 4 x 32 x 36 floats
+  constexpr int RING_U4 = NR * SLOT > 4 * 32 * 9 ? NR * SLOT : 4 * 32 * 9; // the statistics reuse the ring: 4 x 32 x 36 floats
   float *spa = reinterpret_cast<float *>(sw + RING_U4);  // [nchunks * 16] prologue scale / shift (PRO)
   float *spb = spa + (PRO ? nchunks * KS : 0);
   float *sbias = spb + (PRO ? nchunks * KS : 0);     // [COT] (zero beyond Cout)
@@ -74,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
   const uint32_t sw_lds = (uint32_t)(uintptr_t)(lds_byte *)reinterpret_cast<unsigned char *>(sw);
   auto weights_dma = [&](int q) { // slice of chunk q -> ring slot q % NR; lane-linear element e = (plane, channel)
     if (q >= nchunks) return;
-    const uint32_t dst0 = sw_lds + (uint32_t)((q % NR) * WPL * 16);
+    const uint32_t dst0 = sw_lds + (uint32_t)((q % NR) * SLOT * 16);
     for (int i = wave; i < NDMA; i += 4) {
       const int e = i * 64 + lane;
       const u4 *gp = wp + ((size_t)q * 4 + e / COT) * Cpad + co0 + e % COT;
@@ -82,6 +93,31 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
       unsigned keep;
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(gp), "s"(dst) : "memory");
+    }
+  };
+  // WIDE: rows 16 q .. 16 q + 15 x the workgroup's XROW columns -> ring slot q % NR behind the weights, lane-linear: piece
+  // e = 64 i + lane is row e / (XROW / 4), columns 4 (e % (XROW / 4)) .. + 3.  The whole byte offset sits in the VGPR, which
+  // the range check covers: rows past Cin lie past num_records and arrive as 0; a piece past column L reads the next rows
+  // of this batch entry's slice (or 0 past its end) and is dropped by `cok` below -- nothing outside x's slice is read.
+  int xoff[WIDE ? XDMA : 1];
+  if (WIDE) {
+#pragma unroll
+    for (int n = 0; n < XDMA; ++n) {
+      const int e = (wave + 4 * n) * 64 + lane;
+      xoff[n] = ((e / (XROW / 4)) * L + blockIdx.x * XROW + 4 * (e % (XROW / 4))) * 4;
+    }
+  }
+  auto x_dma = [&](int q) {
+    if (q >= nchunks) return;
+    const uint32_t dst0 = sw_lds + (uint32_t)(((q % NR) * SLOT + WPL) * 16);
+    const int qoff = q * KS * L * 4;
+#pragma unroll
+    for (int n = 0; n < XDMA; ++n) {
+      const uint32_t dst = __builtin_amdgcn_readfirstlane(dst0 + (uint32_t)((wave + 4 * n) * 1024));
+      const int off = xoff[WIDE ? n : 0] + qoff;
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(off), "s"(xrs), "s"(dst) : "memory");
     }
   };
   // rows k = 16 q + 8 kh + j of this lane's columns, clamped past Cin.  UNCONDITIONAL, also for the D chunks past the end:
@@ -116,18 +152,35 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
     // the count can only be too strict
     static_assert((D - 1) * (DMIN + 8 * VB) <= 63, "vmcnt is a 6-bit counter");
     const int behind = max(0, min(D - 1, nchunks - 1 - q)); // chunks behind q whose slices were issued
-    if (behind >= 3 && D > 3) wait_vm<(D - 1) * 8 * VB + (D > 3 ? 3 : 0) * DMIN>();
-    else if (behind == 2 && D > 2) wait_vm<(D - 1) * 8 * VB + (D > 2 ? 2 : 0) * DMIN>();
-    else if (behind == 1 && D > 1) wait_vm<(D - 1) * 8 * VB + DMIN>();
-    else wait_vm<(D - 1) * 8 * VB>();
+    if (WIDE) {
+      // the only memory operations in flight are the LDS-DMAs: behind chunk q's, XDMA row pieces and at least DMIN slice
+      // pieces for each of the `behind` existing chunks q + 1 .. q + D - 1 (none are issued for chunks past the end)
+      if (behind >= 3 && D > 3) wait_vm<(D > 3 ? 3 : 0) * (DMIN + XDMA)>();
+      else if (behind == 2 && D > 2) wait_vm<(D > 2 ? 2 : 0) * (DMIN + XDMA)>();
+      else if (behind == 1 && D > 1) wait_vm<DMIN + XDMA>();
+      else wait_vm<0>();
+    } else {
+      if (behind >= 3 && D > 3) wait_vm<(D - 1) * 8 * VB + (D > 3 ? 3 : 0) * DMIN>();
+      else if (behind == 2 && D > 2) wait_vm<(D - 1) * 8 * VB + (D > 2 ? 2 : 0) * DMIN>();
+      else if (behind == 1 && D > 1) wait_vm<(D - 1) * 8 * VB + DMIN>();
+      else wait_vm<(D - 1) * 8 * VB>();
+    }
     PWS_T(2 + 4 * q);
     __syncthreads(); // slice q visible to all waves; ring slot (q + D) % NR (chunk q - 1) no longer read
     PWS_T(3 + 4 * q);
     weights_dma(q + D);
-    issue_x(q + D, vnext);
+    if (WIDE) x_dma(q + D);
+    else issue_x(q + D, vnext);
     PWS_T(4 + 4 * q);
     if (q >= nchunks) return; // a padding chunk of the last round: barrier and prefetch only (uniform)
-    const u4 *swq = sw + (q % NR) * WPL;
+    const u4 *swq = sw + (q % NR) * SLOT;
+    if (WIDE) { // this lane's 8 k-values of its columns, from the slot's activation rows
+      const float *xq = reinterpret_cast<const float *>(swq + WPL) + (kh * 8) * XROW + wave * VB * 32 + l32;
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[vb][j] = xq[j * XROW + vb * 32];
+    }
     u4 wh[CB], wl[CB]; // the weight fragments first: their LDS latency runs under the cut of the activation rows
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) { wh[cb] = swq[(0 + kh) * COT + cb * 32 + l32]; wl[cb] = swq[(2 + kh) * COT + cb * 32 + l32]; }
@@ -188,14 +241,21 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
   };
 
   static_assert(D >= 1 && D <= 4, "the wait above distinguishes up to 3 chunks in flight behind the awaited one");
-  float ring[NR][VB][8];
+  float ring[WIDE ? 1 : NR][VB][8];
+  if (WIDE) {
 #pragma unroll
-  for (int p = 0; p < D; ++p) { weights_dma(p); issue_x(p, ring[p]); }
-  PWS_T(1);
-  for (int q0 = 0; q0 < nchunks; q0 += NR) {
+    for (int p = 0; p < D; ++p) { weights_dma(p); x_dma(p); }
+    PWS_T(1);
+    for (int q = 0; q < nchunks; ++q) chunk(q, ring[0], ring[0]); // the rows live in LDS: no static register slots
+  } else { // (the WIDE ? 0 : only keeps the indices inside the one-slot array this branch is still compiled against)
 #pragma unroll
-    for (int p = 0; p < NR; ++p)
-      chunk(q0 + p, ring[p], ring[(p + D) % NR]); // static ring slots: chunk q lives in slot q % NR
+    for (int p = 0; p < D; ++p) { weights_dma(p); issue_x(p, ring[WIDE ? 0 : p]); }
+    PWS_T(1);
+    for (int q0 = 0; q0 < nchunks; q0 += NR) {
+#pragma unroll
+      for (int p = 0; p < NR; ++p)
+        chunk(q0 + p, ring[WIDE ? 0 : p], ring[WIDE ? 0 : (p + D) % NR]); // static ring slots: chunk q lives in slot q % NR
+    }
   }
 
   // epilogue: D = (main + corr / 2048) * 2^-(E + ew) + bias, [B, Cout, L] store.  acc register i of lane l: channel row
@@ -215,6 +275,7 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
         const float o = ((acc[cb][vb][i] + cor[cb][vb][i] * (1.f / 2048.f)) * us_x) * us_w + sbias[co];
         acc[cb][vb][i] = cok[vb] ? o : 0.f;
       }
+    if (WIDE) continue; // stored below, through the transposition
     float *yc = yb + colc[vb];
     if (full) {
       if (cok[vb]) {
@@ -233,8 +294,8 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
         }
     }
   }
-  PWS_T(102);
-  if (STATS) { // per (batch, channel, column tile) sum and sum of squares.
+  if (!WIDE) PWS_T(102);
+  if (STATS || WIDE) { // per (batch, channel, column tile) sum and sum of squares.
     // 64 channel rows per lane pair x a 32-lane butterfly each was 7.7k cycles of DPP per wave (s_memtime); instead the
     // wave transposes a 32-channel x 32-column block through LDS (its own 4.5 KiB of the weight ring, rows padded to 36
     // floats) and lane (channel, column half) sums 16 columns in a fixed order; the two halves
@@ -242,6 +303,7 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
     __syncthreads(); // the weight ring is no longer read
     float *T = reinterpret_cast<float *>(sw) + wave * (32 * 36);
     const int hc = lane >> 5; // which 16 columns of the row this lane sums
+    const int r8 = lane >> 3, c4 = 4 * (lane & 7); // WIDE: 8 lanes store 128 contiguous bytes of channel row r8 + 8 r
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
       float s1 = 0.f, s2 = 0.f;
@@ -252,6 +314,16 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (WIDE) {
+          const int col = ((blockIdx.x * 4 + wave) * VB + vb) * 32 + c4; // L % 4 == 0: a piece is inside or outside
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int co = cb * 32 + r * 8 + r8;
+            const float4 t = *reinterpret_cast<const float4 *>(T + (r * 8 + r8) * 36 + c4);
+            if (col < L && (full || co0 + co < CoutY)) *reinterpret_cast<float4 *>(yb + (size_t)co * L + col) = t;
+          }
+        }
+        if (STATS)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float4 t = *reinterpret_cast<const float4 *>(T + l32 * 36 + hc * 16 + 4 * j);
@@ -264,11 +336,15 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
         __builtin_amdgcn_wave_barrier();
       }
       // {columns 0-15, columns 16-31} of channel cb * 32 + l32: two partials per wave, summed in a fixed order below
-      sred[((wave * 2 + hc) * COT + cb * 32 + l32) * 2] = s1;
-      sred[((wave * 2 + hc) * COT + cb * 32 + l32) * 2 + 1] = s2;
+      if (STATS) {
+        sred[((wave * 2 + hc) * COT + cb * 32 + l32) * 2] = s1;
+        sred[((wave * 2 + hc) * COT + cb * 32 + l32) * 2 + 1] = s2;
+      }
     }
+    if (WIDE) PWS_T(102);
     PWS_T(103);
-    __syncthreads();
+    if (STATS) __syncthreads();
+    if (STATS)
     for (int c = tid; c < COT && co0 + c < CoutY; c += 256) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -310,6 +386,19 @@ __global__ void pw_split_pack_kernel(const float *__restrict__ w, int Cout, int 
 #ifndef PWS_NR
 #define PWS_NR 5
 #endif
+// ring depth of the WIDE instantiations per plan: a slot also holds the chunk's activation rows (8 KiB x VB), and two
+// workgroups share a CU's 160 KiB.  Measured over 12 in-step shapes at B = 32 (graph replay, us summed; profiles/
+// pw_split_wide_ab.txt): depths 3 / 2 / 2 = 245, 4 / 3 / 3 = 248, the 4-byte path 284 -- the shallower rings are no slower
+// (within the 1 % the repeats differ by) and take 48 / 40 / 36 KiB instead of 64 / 60 / 54.
+#ifndef PWS_NR_W41
+#define PWS_NR_W41 3
+#endif
+#ifndef PWS_NR_W22
+#define PWS_NR_W22 2
+#endif
+#ifndef PWS_NR_W12
+#define PWS_NR_W12 2
+#endif
 struct PwSplitPlan { int cb, vb; };
 static int pws_pad(int Cout) { return (Cout + 31) / 32 * 32; }
 static PwSplitPlan pws_plan(int Cout) {
@@ -321,18 +410,18 @@ static PwSplitPlan pws_plan(int Cout) {
 }
 static size_t pws_halfs(int Cout, int Cin) { return (size_t)((Cin + KS - 1) / KS) * 4 * pws_pad(Cout) * 8; }
 
-template <int CB, int VB, int NR>
+template <int CB, int VB, int NR, bool WIDE>
 static int launch_pws(const float *x, const u4 *wp, const float *wtail, const float *bias, float *y, int B, int Cin,
                       int Cout, int L, const float *pa, const float *pb, float *stats, hipStream_t st) {
   const int Cpad = pws_pad(Cout), nchunks = (Cin + KS - 1) / KS;
   const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
-  const size_t ring = (size_t)NR * 4 * CB * 32 * 16, tile = (size_t)4 * 32 * 36 * 4; // weight ring, reused by the statistics
+  const size_t ring = (size_t)NR * (4 * CB * 32 * 16 + (WIDE ? KS * 128 * VB * 4 : 0)), tile = (size_t)4 * 32 * 36 * 4; // weight ring, reused by the statistics
   const size_t lds = (ring > tile ? ring : tile) + (size_t)((pa ? 2 * nchunks * KS : 0) + CB * 32 + 8 * CB * 32 * 2) * 4;
 #define LION_PWS_GO(PRO_, ST_)                                                                             \
   {                                                                                                        \
     static LionLdsLimit cfg = {};                                                                          \
-    if (int e = lion_dynamic_lds(&pwconv_split_kernel<CB, VB, PRO_, ST_, NR>, lds, cfg)) return e;             \
-    pwconv_split_kernel<CB, VB, PRO_, ST_, NR><<<grid, 256, lds, st>>>(x, wp, wtail, bias, y, Cin, Cpad, Cout, L, pa, pb, stats); \
+    if (int e = lion_dynamic_lds(&pwconv_split_kernel<CB, VB, PRO_, ST_, NR, WIDE>, lds, cfg)) return e;             \
+    pwconv_split_kernel<CB, VB, PRO_, ST_, NR, WIDE><<<grid, 256, lds, st>>>(x, wp, wtail, bias, y, Cin, Cpad, Cout, L, pa, pb, stats); \
   }
   if (pa && stats) LION_PWS_GO(true, true)
   else if (pa) LION_PWS_GO(true, false)
@@ -401,10 +490,21 @@ int lion_pwconv_split_forward(const float *x, const uint16_t *wp, const float *b
   const u4 *w4 = reinterpret_cast<const u4 *>(wp);
   const float *wtail = reinterpret_cast<const float *>(wp + pws_halfs(Cout, Cin));
   const PwSplitPlan p = pws_plan(Cout);
+  // the 16-byte transport needs whole 16-byte pieces per row: L % 4 == 0 (which also aligns every row and batch stride)
+  // and 16-byte aligned x and y; everything else runs the 4-byte path
+  const bool wide = L % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
+  if (wide) {
+    switch (p.cb) {
+    case 4: return launch_pws<4, 1, PWS_NR_W41, true>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+    case 2: return launch_pws<2, 2, PWS_NR_W22, true>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+    case 1: return launch_pws<1, 2, PWS_NR_W12, true>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+    default: return LION_EUNSUPPORTED;
+    }
+  }
   switch (p.cb) {
-  case 4: return launch_pws<4, 1, PWS_NR>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  case 2: return launch_pws<2, 2, PWS_NR>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  case 1: return launch_pws<1, 2, PWS_NR>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+  case 4: return launch_pws<4, 1, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+  case 2: return launch_pws<2, 2, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+  case 1: return launch_pws<1, 2, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
   default: return LION_EUNSUPPORTED;
   }
 }
