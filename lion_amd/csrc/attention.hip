@@ -242,9 +242,7 @@ extern "C" {
 int lion_linear_attention_core(const float *qkv, int B, int H, int D, int N, float *out, lionStream_t stream) {
   if (!qkv || !out || B <= 0 || H <= 0 || N <= 0) return LION_EINVAL;
   if (D != AD) return LION_EUNSUPPORTED;
-  linattn_core_kernel<<<dim3(H, B), 256, 0, static_cast<hipStream_t>(stream)>>>(qkv, H, N, out);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<linattn_core_kernel>(dim3(H, B), 256, 0, static_cast<hipStream_t>(stream), qkv, H, N, out);
 }
 
 // gradient of lion_linear_attention_core: qkv as the forward's, gout f32[B, H*32, N] -> gqkv f32[B, 3*H*32, N]
@@ -252,9 +250,8 @@ int lion_linear_attention_core_backward(const float *qkv, const float *gout, int
                                         lionStream_t stream) {
   if (!qkv || !gout || !gqkv || B <= 0 || H <= 0 || N <= 0) return LION_EINVAL;
   if (D != AD) return LION_EUNSUPPORTED;
-  linattn_core_bwd_kernel<<<dim3(H, B), 256, 0, static_cast<hipStream_t>(stream)>>>(qkv, gout, H, N, gqkv);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<linattn_core_bwd_kernel>(dim3(H, B), 256, 0, static_cast<hipStream_t>(stream), qkv, gout, H, N,
+                                              gqkv);
 }
 
 } // extern "C"

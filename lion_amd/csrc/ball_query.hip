@@ -90,8 +90,6 @@ extern "C" int lion_ball_query(const float *centers, const float *points, int B,
                                float radius, int U, int32_t *idx, lionStream_t stream) {
   if (!centers || !points || !idx || B <= 0 || M <= 0 || N <= 0 || U <= 0) return LION_EINVAL;
   const float r2 = radius * radius; // ball_query.cpp:24
-  ball_query_kernel<<<dim3(lion_cdiv(M, 4 * BQ_CPW), B), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      centers, points, M, N, r2, U, idx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<ball_query_kernel>(dim3(lion_cdiv(M, 4 * BQ_CPW), B), 256, 0, static_cast<hipStream_t>(stream),
+                                        centers, points, M, N, r2, U, idx);
 }

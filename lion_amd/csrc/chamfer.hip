@@ -258,11 +258,8 @@ int lion_chamfer_forward(const float *xyz1, const float *xyz2, int B, int N, int
   if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2 || B <= 0 || N <= 0 || M <= 0)
     return LION_EINVAL;
   const int nmax = N > M ? N : M;
-  chamfer_fwd_kernel<<<dim3(lion_cdiv(nmax, CH_QPB), B, 2), 256, 0,
-                       static_cast<hipStream_t>(stream)>>>(xyz1, xyz2, N, M, dist1, dist2, idx1,
-                                                           idx2);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<chamfer_fwd_kernel>(dim3(lion_cdiv(nmax, CH_QPB), B, 2), 256, 0, static_cast<hipStream_t>(stream),
+                                         xyz1, xyz2, N, M, dist1, dist2, idx1, idx2);
 }
 
 int lion_chamfer_backward(const float *xyz1, const float *xyz2, const float *gdist1,
@@ -272,20 +269,24 @@ int lion_chamfer_backward(const float *xyz1, const float *xyz2, const float *gdi
       N <= 0 || M <= 0)
     return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  chamfer_grad_own_kernel<<<dim3(lion_cdiv(N, 256), B), 256, 0, st>>>(xyz1, xyz2, gdist1, idx1, N, M, gxyz1);
-  chamfer_grad_own_kernel<<<dim3(lion_cdiv(M, 256), B), 256, 0, st>>>(xyz2, xyz1, gdist2, idx2, M, N, gxyz2);
-  chamfer_grad_scatter_kernel<<<dim3(lion_cdiv(N, 256), B), 256, 0, st>>>(xyz1, xyz2, gdist1, idx1, N, M, gxyz2);
-  chamfer_grad_scatter_kernel<<<dim3(lion_cdiv(M, 256), B), 256, 0, st>>>(xyz2, xyz1, gdist2, idx2, M, N, gxyz1);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<chamfer_grad_own_kernel>(dim3(lion_cdiv(N, 256), B), 256, 0, st, xyz1, xyz2, gdist1, idx1, N,
+                                                   M, gxyz1))
+    return e;
+  if (int e = lion_launch<chamfer_grad_own_kernel>(dim3(lion_cdiv(M, 256), B), 256, 0, st, xyz2, xyz1, gdist2, idx2, M,
+                                                   N, gxyz2))
+    return e;
+  if (int e = lion_launch<chamfer_grad_scatter_kernel>(dim3(lion_cdiv(N, 256), B), 256, 0, st, xyz1, xyz2, gdist1, idx1,
+                                                       N, M, gxyz2))
+    return e;
+  return lion_launch<chamfer_grad_scatter_kernel>(dim3(lion_cdiv(M, 256), B), 256, 0, st, xyz2, xyz1, gdist2, idx2, M,
+                                                  N, gxyz1);
 }
 
 int lion_chamfer_loss_reduce(const float *dist1, const float *dist2, int B, int N, int M, float s1, float s2, float *loss,
                              lionStream_t stream) {
   if (!dist1 || !dist2 || !loss || B <= 0 || N <= 0 || M <= 0) return LION_EINVAL;
-  chamfer_loss_reduce_kernel<<<B, CHL_LANES, 0, static_cast<hipStream_t>(stream)>>>(dist1, dist2, N, M, s1, s2, loss);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<chamfer_loss_reduce_kernel>(B, CHL_LANES, 0, static_cast<hipStream_t>(stream), dist1, dist2, N, M,
+                                                 s1, s2, loss);
 }
 
 int lion_chamfer_loss_backward(const float *xyz1, const float *xyz2, const int32_t *idx1, const int32_t *idx2,
@@ -295,10 +296,9 @@ int lion_chamfer_loss_backward(const float *xyz1, const float *xyz2, const int32
     return LION_EINVAL;
   const int dir0 = gxyz1 ? 0 : 1, ndir = (gxyz1 && gxyz2) ? 2 : 1; // a NULL gradient: that direction is not launched
   const int nmax = ndir == 2 ? (N > M ? N : M) : (dir0 == 0 ? N : M);
-  chamfer_loss_bwd_kernel<<<dim3(lion_cdiv(nmax, 256), B, ndir), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      xyz1, xyz2, idx1, idx2, gloss, N, M, s1, s2, gxyz1, gxyz2, dir0);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<chamfer_loss_bwd_kernel>(dim3(lion_cdiv(nmax, 256), B, ndir), 256, 0,
+                                              static_cast<hipStream_t>(stream), xyz1, xyz2, idx1, idx2, gloss, N, M, s1,
+                                              s2, gxyz1, gxyz2, dir0);
 }
 
 } // extern "C"

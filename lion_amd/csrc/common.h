@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 #include "lion_hip.h"
 
@@ -58,6 +59,33 @@ static inline int lion_dynamic_lds(K kernel, size_t bytes, LionLdsLimit &limit) 
     limit.bytes[dev] = bytes;
   }
   return 0;
+}
+
+// The one door to the device: lion_launch<kernel<...>>(grid, block, dynamic LDS bytes, stream, kernel arguments...)
+// raises the kernel's dynamic-LDS limit where the launch asks for any, launches, and returns 0 or the launch's error.
+// The limit slot is a static of this function, so there is exactly one per kernel instantiation (and translation
+// unit): no launch site can share a sibling's.  The arguments are the kernel's own parameter types, so they convert
+// exactly as at a direct call.
+template <auto Kernel> struct LionLaunch;
+template <typename... P, void (*Kernel)(P...)> struct LionLaunch<Kernel> {
+  int operator()(dim3 grid, dim3 block, size_t lds, hipStream_t st, P... args) const {
+    if (lds > 0) {
+      static LionLdsLimit limit = {};
+      if (int e = lion_dynamic_lds(Kernel, lds, limit)) return e;
+    }
+    Kernel<<<grid, block, lds, st>>>(args...);
+    return (int)hipGetLastError();
+  }
+};
+template <auto Kernel> static constexpr LionLaunch<Kernel> lion_launch{};
+
+// Runtime flags -> compile-time flags for a generic lambda: f(BoolC<a>{}) / f(BoolC<a>{}, BoolC<b>{}); IntC likewise
+// carries a small integer.  Read them as decltype(flag)::value.
+template <bool V> using BoolC = std::bool_constant<V>;
+template <int V> using IntC = std::integral_constant<int, V>;
+template <typename F> static inline int lion_with_flags(bool a, F f) { return a ? f(BoolC<true>{}) : f(BoolC<false>{}); }
+template <typename F> static inline int lion_with_flags(bool a, bool b, F f) {
+  return lion_with_flags(a, [&](auto A) { return lion_with_flags(b, [&](auto B) { return f(A, B); }); });
 }
 
 // Parity-critical float arithmetic: one IEEE rounding per operation, never contracted into

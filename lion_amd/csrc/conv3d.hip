@@ -548,9 +548,10 @@ __global__ void conv3d_pack_kernel(const float *__restrict__ w, int Cout, int Ci
   wp[i] = ci < Cin ? w[((size_t)co * Cin + ci) * 27 + t] : 0.f;
 }
 
+template <int TD, int TH, int TW, int COT, int VB> struct ConvTile {}; // spatial tile, output channels, voxel blocks per wave
 template <int TD, int TH, int TW, int COT, int VB>
-static int launch_conv_t(const float *x, const float *wp, const float *bias, float *y, int B, int Cin,
-                         int Cout, int r, const float *pa, const float *pb, const float *pbias, const float *tconst,
+static int launch_conv_t(ConvTile<TD, TH, TW, COT, VB>, const float *x, const float *wp, const float *bias, float *y, int B,
+                         int Cin, int Cout, int r, const float *pa, const float *pb, const float *pbias, const float *tconst,
                          float *stats, int32_t *occ, hipStream_t st) {
   const int tiles = (r / TD) * (r / TH) * (r / TW);
   int n_cu = 0;
@@ -563,21 +564,10 @@ static int launch_conv_t(const float *x, const float *wp, const float *bias, flo
   static_assert(KC * HALO >= 27 * COT, "the response table must fit the input tile buffer");
   const size_t LDS = (size_t)(((KC * HALO + 3) & ~3) + 2 * SWS + COT + (pa ? 3 * ((Cin + 63) & ~63) : 0) +
                               (NT / 64) * COT * 2) * 4;
-#define LION_CONV_GO(PRO_, ST_)                                                                           \
-  {                                                                                                       \
-    static LionLdsLimit cfg = {};                                                                         \
-    if (int e = lion_dynamic_lds(&conv3d_k3_kernel<TD, TH, TW, COT, VB, PRO_, ST_>, LDS, cfg)) return e;  \
-    conv3d_k3_kernel<TD, TH, TW, COT, VB, PRO_, ST_><<<grid, NT, LDS, st>>>(x, wp, bias, y, Cin, Cout, r, \
-                                                                            pa, pb, pbias, tconst, stats, occ, B, \
-                                                                            tiles);                      \
-  }
-  if (pa && stats) LION_CONV_GO(true, true)
-  else if (pa) LION_CONV_GO(true, false)
-  else if (stats) LION_CONV_GO(false, true)
-  else LION_CONV_GO(false, false)
-#undef LION_CONV_GO
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
+    return lion_launch<conv3d_k3_kernel<TD, TH, TW, COT, VB, decltype(PRO)::value, decltype(ST)::value>>(
+        grid, NT, LDS, st, x, wp, bias, y, Cin, Cout, r, pa, pb, pbias, tconst, stats, occ, B, tiles);
+  });
 }
 
 // Tile choice per (r, Cout): spatial tile = 4 waves x VB x 32 voxels, COT output channels per workgroup.
@@ -611,20 +601,20 @@ static int launch_conv(const float *x, const float *wp, const float *bias, float
                        int r, const float *pa, const float *pb, const float *pbias, const float *tconst, float *stats,
                        int32_t *occ, hipStream_t st) {
   const ConvPlan p = conv_plan(r, Cout, B, occ != nullptr);
-#define LION_CONV_TILE(R_, VB_, COT_, TD_, TH_, TW_)                                                       \
-  if (r == R_ && p.vb == VB_ && p.cot == COT_)                                                             \
-    return launch_conv_t<TD_, TH_, TW_, COT_, VB_>(x, wp, bias, y, B, Cin, Cout, r, pa, pb, pbias, tconst, stats, occ, st);
-  LION_CONV_TILE(32, 2, 64, 2, 4, 32)
-  LION_CONV_TILE(32, 4, 64, 4, 4, 32)
-  LION_CONV_TILE(16, 4, 64, 8, 4, 16)
-  LION_CONV_TILE(32, 4, 32, 4, 4, 32)
-  LION_CONV_TILE(32, 2, 32, 2, 4, 32)
-  LION_CONV_TILE(16, 2, 32, 4, 4, 16)
-  LION_CONV_TILE(16, 2, 64, 4, 4, 16)
-  LION_CONV_TILE(16, 4, 32, 8, 4, 16)
-  LION_CONV_TILE(8, 2, 64, 4, 8, 8)
-  LION_CONV_TILE(8, 1, 32, 2, 8, 8)
-#undef LION_CONV_TILE
+  auto go = [&](auto tile) {
+    return launch_conv_t(tile, x, wp, bias, y, B, Cin, Cout, r, pa, pb, pbias, tconst, stats, occ, st);
+  };
+  const int vb = p.vb, cot = p.cot; // -> ConvTile<TD, TH, TW, COT, VB>
+  if (r == 32 && vb == 2 && cot == 64) return go(ConvTile<2, 4, 32, 64, 2>{});
+  if (r == 32 && vb == 4 && cot == 64) return go(ConvTile<4, 4, 32, 64, 4>{});
+  if (r == 16 && vb == 4 && cot == 64) return go(ConvTile<8, 4, 16, 64, 4>{});
+  if (r == 32 && vb == 4 && cot == 32) return go(ConvTile<4, 4, 32, 32, 4>{});
+  if (r == 32 && vb == 2 && cot == 32) return go(ConvTile<2, 4, 32, 32, 2>{});
+  if (r == 16 && vb == 2 && cot == 32) return go(ConvTile<4, 4, 16, 32, 2>{});
+  if (r == 16 && vb == 2 && cot == 64) return go(ConvTile<4, 4, 16, 64, 2>{});
+  if (r == 16 && vb == 4 && cot == 32) return go(ConvTile<8, 4, 16, 32, 4>{});
+  if (r == 8 && vb == 2 && cot == 64) return go(ConvTile<4, 8, 8, 64, 2>{});
+  if (r == 8 && vb == 1 && cot == 32) return go(ConvTile<2, 8, 8, 32, 1>{});
   return LION_EUNSUPPORTED;
 }
 
@@ -652,9 +642,8 @@ int lion_conv3d_pack_weights(const float *w, int Cout, int Cin, float *wp, lionS
   if (!w || !wp || Cout <= 0 || Cin <= 0) return LION_EINVAL;
   const int Cin_pad = (Cin + KC - 1) / KC * KC;
   const int total = Cin_pad * 27 * Cout;
-  conv3d_pack_kernel<<<lion_cdiv(total, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(w, Cout, Cin, Cin_pad, wp);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv3d_pack_kernel>(lion_cdiv(total, 256), 256, 0, static_cast<hipStream_t>(stream), w, Cout, Cin,
+                                         Cin_pad, wp);
 }
 
 // x f32[B,Cin,r,r,r] with Cin % 4 == 0, wp from lion_conv3d_pack_weights, bias f32[Cout] or NULL
@@ -694,10 +683,8 @@ int lion_conv3d_const_response(const float *wsum, const float *bias2, const floa
                                const float *pro_b, int B, int Cin, int Cout, float *tconst, lionStream_t stream) {
   if (!wsum || !pro_a || !pro_b || !tconst || B <= 0 || Cin <= 0 || Cout <= 0) return LION_EINVAL;
   if (Cin > 256) return LION_EUNSUPPORTED;
-  conv_tconst_kernel<<<dim3(27, B), 256, 0, static_cast<hipStream_t>(stream)>>>(wsum, bias2, bias1, pro_a, pro_b, Cin,
-                                                                                 Cout, tconst);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv_tconst_kernel>(dim3(27, B), 256, 0, static_cast<hipStream_t>(stream), wsum, bias2, bias1,
+                                         pro_a, pro_b, Cin, Cout, tconst);
 }
 
 size_t lion_conv3d_occupancy_ints(int r, int Cout, int B) {
@@ -726,10 +713,8 @@ int lion_conv3d_tile_occupancy_aware(const int32_t *cnt, int B, int r, int Cout,
   int td, th, tw;
   conv_tile_dims(r, p.vb, &td, &th, &tw);
   // the reader map of the first buffer is derived from the second margin's flags: both are computed in any case
-  conv_tile_occ_kernel<<<B, 1024, 0, static_cast<hipStream_t>(stream)>>>(cnt, r, td, th, occ_m1, occ_m2,
-                                                                         consumer_aware == 2 ? 2 : consumer_aware ? 1 : 0);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv_tile_occ_kernel>(B, 1024, 0, static_cast<hipStream_t>(stream), cnt, r, td, th, occ_m1, occ_m2,
+                                           consumer_aware == 2 ? 2 : consumer_aware ? 1 : 0);
 }
 
 int lion_conv3d_stat_tiles(int r, int Cout, int B, int sparse) {
@@ -744,10 +729,8 @@ int lion_groupnorm_fold_se(const float *stats, int B, int C, int T, int G, int v
   if (!stats || !gamma || !beta || !fac || !gbias || !w1 || !w2 || !A || !Bs) return LION_EINVAL;
   if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G != 0 || ld_fg < C || H <= 0) return LION_EINVAL;
   if (C > 256 || C < 4 || H > 128) return LION_EUNSUPPORTED;
-  gn_fold_se_kernel<<<B, 256, 0, static_cast<hipStream_t>(stream)>>>(stats, C, T, G, (float)voxels, gamma, beta, fac, gbias,
-                                                                     ld_fg, eps, w1, w2, H, A, Bs);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<gn_fold_se_kernel>(B, 256, 0, static_cast<hipStream_t>(stream), stats, C, T, G, (float)voxels,
+                                        gamma, beta, fac, gbias, ld_fg, eps, w1, w2, H, A, Bs);
 }
 
 // stats f32[B,C,T,2] -> A, Bs, chmean f32[B,C]   (GroupNorm(G) folded with the AdaGN affine fac/gbias f32[B,C])
@@ -756,10 +739,8 @@ int lion_groupnorm_fold(const float *stats, int B, int C, int T, int G, int voxe
                         float *A, float *Bs, float *chmean, lionStream_t stream) {
   if (!stats || !gamma || !beta || !fac || !gbias || !A || !Bs || !chmean) return LION_EINVAL;
   if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G != 0 || C / G > 64 || ld_fg < C) return LION_EINVAL;
-  gn_fold_kernel<<<dim3(G, B), 256, 0, static_cast<hipStream_t>(stream)>>>(stats, C, T, G, (float)voxels, gamma,
-                                                                         beta, fac, gbias, ld_fg, eps, A, Bs, chmean);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<gn_fold_kernel>(dim3(G, B), 256, 0, static_cast<hipStream_t>(stream), stats, C, T, G,
+                                     (float)voxels, gamma, beta, fac, gbias, ld_fg, eps, A, Bs, chmean);
 }
 
 } // extern "C"

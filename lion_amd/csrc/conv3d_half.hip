@@ -29,26 +29,9 @@ extern "C" {
 int lion_conv3d_k3_half_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout, int r,
                                 const float *pro_a, const float *pro_b, const float *pro_bias, const float *tconst,
                                 float *y, float *stats, int32_t *occ, lionStream_t stream) {
-  if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0) return LION_EINVAL;
-  if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
-  if (tconst && !pro_a) return LION_EINVAL;
-  if (occ && pro_a && !tconst) return LION_EINVAL;
-  if ((r != 16 && r != 32) || Cin % KS != 0 || Cout % 32 != 0) return LION_EINVAL; // r = 8 stays on the three-product kernel
-  if (pro_a && Cin > 256) return LION_EUNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const u4 *w4 = reinterpret_cast<const u4 *>(wp);
-  const float *wtail = reinterpret_cast<const float *>(wp + split_piece_halfs(Cout, Cin));
-  const int cb = Cout % 64 == 0 ? 2 : 1;
-#define LION_HALF_TILE(R_, CB_, TD_, TH_, TW_, OCC_)                                                          \
-  if (r == R_ && cb == CB_)                                                                                   \
-    return launch_split_t<TD_, TH_, TW_, CB_, 2, OCC_, 1>(x, w4, wtail, bias, y, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, \
-                                                       stats, occ, st);
-  LION_HALF_TILE(32, 2, 2, 4, 32, 2)
-  LION_HALF_TILE(32, 1, 2, 4, 32, 2)
-  LION_HALF_TILE(16, 2, 4, 4, 16, 2)
-  LION_HALF_TILE(16, 1, 4, 4, 16, 2)
-#undef LION_HALF_TILE
-  return LION_EINVAL;
+  const int e = split_tile_forward<1>(x, wp, bias, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, y, stats, occ,
+                                      static_cast<hipStream_t>(stream));
+  return e == LION_SPLIT_NO_TILE ? LION_EINVAL : e; // r = 8 stays on the three-product kernel
 }
 
 } // extern "C"

@@ -63,7 +63,8 @@ __global__ void split_pack_kernel(const float *__restrict__ w, int Cout, int Cin
 // 32 B/clk and issues a 32x32x16 MFMA every ~64 cycles, whatever else the CU does -- four waves x (32 channels x 64
 // voxels: 6 fragment reads per 6 MFMAs) sit on both limits (taps: 331 cycles per tap round for 192 of MFMA).  So the
 // default is EIGHT waves (two per SIMD) x one column block: 4 reads per 3 MFMAs and wave, 255 B/clk of LDS with the
-// conflict-free row order below, 54 -> 48 us at 128 -> 128, B = 32 (LION_CONV_R8_WAVES=4 selects the 4-wave form).
+// conflict-free row order below, 54 -> 48 us at 128 -> 128, B = 32.  (Only that form is built: the quad staging below
+// static_asserts NW == 8, and the 4-wave geometry survives in the index arithmetic alone.)
 // Voxel -> lane: a column block of 32 voxels is 8 w x 4 halo rows chosen so that a 32-lane group of a ds_read_b128
 // touches every 16-byte slot of the 512-byte LDS window once: rows {h, h+2, h+4, h+6} at row stride 12 (8 waves), rows
 // {h, h+4, h+1, h+5} at stride 10 (4 waves: conflict free in 16-lane groups at the 128 B/clk four waves can draw).
@@ -312,32 +313,10 @@ static int launch_split_pipe(const float *x, const u4 *wp, const float *wtail, c
   const dim3 grid(B, 2, Cout / COT);
   const size_t LDS = (size_t)(2 * 4 * HP + 3 * 9 * 4 * COT) * 16 +
                      (size_t)(COT + (pa ? 2 * ((Cin + 63) & ~63) : 0) + NW * COT * 2) * 4;
-#define LION_PIPE_GO(PRO_, ST_)                                                                              \
-  {                                                                                                          \
-    static LionLdsLimit cfg = {};                                                                            \
-    if (int e = lion_dynamic_lds(&conv3d_split_pipe_kernel<PRO_, ST_, NW>, LDS, cfg)) return e;              \
-    conv3d_split_pipe_kernel<PRO_, ST_, NW><<<grid, 64 * NW, LDS, st>>>(x, wp, wtail, bias, y, Cin, Cout, pa, pb, stats); \
-  }
-  if (pa && stats) LION_PIPE_GO(true, true)
-  else if (pa) LION_PIPE_GO(true, false)
-  else if (stats) LION_PIPE_GO(false, true)
-  else LION_PIPE_GO(false, false)
-#undef LION_PIPE_GO
-  LION_LAUNCH_CHECK();
-  return 0;
-}
-
-// tiles: always the 4 waves x 2 column blocks geometry of the product's sparse plan (so that the occupancy lists of
-// lion_conv3d_tile_occupancy apply unchanged), one column block per wave at r = 8
-struct SplitPlan { int vb, cb, tiles; };
-static SplitPlan split_plan(int r, int Cout) {
-  const int r3 = r * r * r;
-  const int cb = Cout % 64 == 0 ? 2 : Cout % 32 == 0 ? 1 : 0;
-  // r = 8: the pipelined half-sample kernel (conv3d_split_pipe_kernel): 2 tiles of 256 voxels, 32 channels per workgroup
-  // (history: 128-voxel tiles 144 us, whole-sample tiles x 32 channels on B * Cout/32 = 128 workgroups 104-108 us at
-  // 128->128, B=32, against 114 us of the fp32 kernel)
-  if (r == 8) return {2, Cout % 32 == 0 ? 1 : 0, 2};
-  return {2, cb, r3 / 256};
+  return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
+    return lion_launch<conv3d_split_pipe_kernel<decltype(PRO)::value, decltype(ST)::value, NW>>(
+        grid, 64 * NW, LDS, st, x, wp, wtail, bias, y, Cin, Cout, pa, pb, stats);
+  });
 }
 
 } // namespace
@@ -355,17 +334,18 @@ int lion_conv3d_split_pack_weights(const float *w, int Cout, int Cin, uint16_t *
   unsigned *tail = reinterpret_cast<unsigned *>(wp + split_piece_halfs(Cout, Cin));
   const int n = Cout * Cin * 27;
   if (hipMemsetAsync(tail, 0, 16, st) != hipSuccess) return LION_EINVAL;
-  split_wmax_kernel<<<min(lion_cdiv(n, 2048), 128), 256, 0, st>>>(w, n, tail);
-  split_pack_kernel<<<lion_cdiv(n, 256), 256, 0, st>>>(w, Cout, Cin, wp, tail);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<split_wmax_kernel>(min(lion_cdiv(n, 2048), 128), 256, 0, st, w, n, tail)) return e;
+  return lion_launch<split_pack_kernel>(lion_cdiv(n, 256), 256, 0, st, w, Cout, Cin, wp, tail);
 }
 
 // @phase-reader
 
 int lion_conv3d_split_stat_tiles(int r, int Cout) {
   if (r != 8 && r != 16 && r != 32) return 0;
-  return split_plan(r, Cout).tiles;
+  // r = 8: the pipelined half-sample kernel (conv3d_split_pipe_kernel): 2 tiles of 256 voxels, 32 channels per workgroup
+  // (history: 128-voxel tiles 144 us, whole-sample tiles x 32 channels on B * Cout/32 = 128 workgroups 104-108 us at
+  // 128->128, B=32, against 114 us of the fp32 kernel); r = 16 / 32: the 256-voxel tiles of split_tile_forward
+  return r == 8 ? 2 : r * r * r / 256;
 }
 
 // Arguments exactly as lion_conv3d_k3_fused_forward (include/lion_hip.h), wp from lion_conv3d_split_pack_weights;
@@ -374,32 +354,14 @@ int lion_conv3d_split_stat_tiles(int r, int Cout) {
 int lion_conv3d_k3_split_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout,
                                  int r, const float *pro_a, const float *pro_b, const float *pro_bias,
                                  const float *tconst, float *y, float *stats, int32_t *occ, lionStream_t stream) {
-  if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0) return LION_EINVAL;
-  if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
-  if (tconst && !pro_a) return LION_EINVAL;
-  if (occ && pro_a && !tconst) return LION_EINVAL;
-  if (Cin % KS != 0 || (pro_a && Cin > 256)) return LION_EUNSUPPORTED;
-  if (r != 8 && r != 16 && r != 32) return LION_EUNSUPPORTED;
-  if (occ && r == 8) return LION_EUNSUPPORTED;
-  const SplitPlan p = split_plan(r, Cout);
-  if (!p.cb) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const u4 *w4 = reinterpret_cast<const u4 *>(wp);
-  const float *wtail = reinterpret_cast<const float *>(wp + split_piece_halfs(Cout, Cin));
-  if (r == 8) {
-    if (tconst) return LION_EUNSUPPORTED;
-    return launch_split_pipe<8>(x, w4, wtail, bias, y, B, Cin, Cout, pro_a, pro_b, stats, st);
-  }
-#define LION_SPLIT_TILE(R_, VB_, CB_, TD_, TH_, TW_, OCC_)                                                  \
-  if (r == R_ && p.vb == VB_ && p.cb == CB_)                                                                \
-    return launch_split_t<TD_, TH_, TW_, CB_, VB_, OCC_, 2>(x, w4, wtail, bias, y, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, \
-                                                   stats, occ, st);
-  LION_SPLIT_TILE(32, 2, 2, 2, 4, 32, 2)
-  LION_SPLIT_TILE(32, 2, 1, 2, 4, 32, 2)
-  LION_SPLIT_TILE(16, 2, 2, 4, 4, 16, 2)
-  LION_SPLIT_TILE(16, 2, 1, 4, 4, 16, 2)
-#undef LION_SPLIT_TILE
-  return LION_EUNSUPPORTED;
+  const int e = split_tile_forward<2>(x, wp, bias, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, y, stats, occ, st);
+  if (e != LION_SPLIT_NO_TILE) return e;
+  // r = 8: the pipelined half-sample kernel, which has no work queue and no constant + delta form
+  if (r != 8 || Cin % KS != 0 || (pro_a && Cin > 256) || Cout % 32 != 0 || occ || tconst) return LION_EUNSUPPORTED;
+  return launch_split_pipe<8>(x, reinterpret_cast<const u4 *>(wp),
+                              reinterpret_cast<const float *>(wp + split_piece_halfs(Cout, Cin)), bias, y, B, Cin, Cout,
+                              pro_a, pro_b, stats, st);
 }
 
 } // extern "C"

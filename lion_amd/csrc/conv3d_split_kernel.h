@@ -26,7 +26,6 @@ namespace {
 // Evidence: profiles/r05a_conv_ab_variants_one_box.txt, r05a_conv_ab_r04_vs_fill_items_in_kernel.txt,
 // r05b_conv_epilogue_phases.txt (where a launch's cycles go).  What was adopted instead is below: empty tiles nobody reads are
 // not stored at all (aware levels), and the work queue re-arms itself.
-template <int N> struct IntC { static constexpr int value = N; }; // compile-time count for generic lambdas
 
 template <int TD, int TH, int TW, int CB, int VB, bool PRO, bool STATS, int OCC, int P>
 __global__ __launch_bounds__(256, OCC) void conv3d_split_kernel(const float *__restrict__ x, const u4 *__restrict__ wp,
@@ -554,23 +553,39 @@ static int launch_split_t(const float *x, const u4 *wp, const float *wtail, cons
   const bool pro_inst = pa != nullptr || (P == 2 && stats != nullptr && CB == 2 && Cin <= 256);
   const size_t LDS = (size_t)(2 * P * HP + 2 * 3 * 2 * P * COT) * 16 + // planes + two groups of 3 taps of weight slices
                      (size_t)(COT + (pro_inst ? 3 * ((Cin + 63) & ~63) : 0) + 4 * COT * 2) * 4;
-#define LION_SPLIT_GO(PRO_, ST_)                                                                             \
-  {                                                                                                          \
-    static LionLdsLimit cfg = {};                                                                            \
-    if (int e = lion_dynamic_lds(&conv3d_split_kernel<TD, TH, TW, CB, VB, PRO_, ST_, OCC, P>, LDS, cfg)) return e; \
-    conv3d_split_kernel<TD, TH, TW, CB, VB, PRO_, ST_, OCC, P><<<grid, 256, LDS, st>>>(x, wp, wtail, bias, y, Cin, Cout, r, pa, pb, \
-                                                                              pbias, tconst, stats, occ, B, tiles); \
-  }
-  if (pro_inst && stats) LION_SPLIT_GO(true, true)
-  else if (pa) LION_SPLIT_GO(true, false)
-  else if (stats) LION_SPLIT_GO(false, true)
-  else LION_SPLIT_GO(false, false)
-#undef LION_SPLIT_GO
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(pro_inst, stats != nullptr, [&](auto PRO, auto ST) {
+    return lion_launch<conv3d_split_kernel<TD, TH, TW, CB, VB, decltype(PRO)::value, decltype(ST)::value, OCC, P>>(
+        grid, 256, LDS, st, x, wp, wtail, bias, y, Cin, Cout, r, pa, pb, pbias, tconst, stats, occ, B, tiles);
+  });
 }
 
 // uint16 in the pieces of the packed weights, in front of their tail: (Cin/16) * 27 * [2 pieces][2 halves] * Cout * 8
 static size_t split_piece_halfs(int Cout, int Cin) { return (size_t)(Cin / KS) * 27 * 4 * Cout * 8; }
+
+// What lion_conv3d_k3_split_forward (P = 2) and lion_conv3d_k3_half_forward (P = 1) share: the argument validation and the
+// tile table.  LION_SPLIT_NO_TILE: the tile kernel has no form for this (r, Cin, Cout) -- each entry point answers that
+// with its own code (the split one first tries its r = 8 kernel).
+constexpr int LION_SPLIT_NO_TILE = -1000;
+template <int P>
+static int split_tile_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout, int r,
+                              const float *pro_a, const float *pro_b, const float *pro_bias, const float *tconst, float *y,
+                              float *stats, int32_t *occ, hipStream_t st) {
+  if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0) return LION_EINVAL;
+  if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
+  if (tconst && !pro_a) return LION_EINVAL;
+  if (occ && pro_a && !tconst) return LION_EINVAL;
+  if ((r != 16 && r != 32) || Cin % KS != 0 || Cout % 32 != 0) return LION_SPLIT_NO_TILE;
+  if (pro_a && Cin > 256) return LION_EUNSUPPORTED;
+  const u4 *w4 = reinterpret_cast<const u4 *>(wp);
+  const float *wtail = reinterpret_cast<const float *>(wp + split_piece_halfs(Cout, Cin));
+  // always the 4 waves x 2 column blocks (VB = 2) geometry of the fp32 kernel's sparse plan, so that the occupancy lists of
+  // lion_conv3d_tile_occupancy apply unchanged: tile (TD, 4, r), 32 * CB channels, two workgroups per CU
+  auto go = [&](auto TD, auto TW, auto CB) {
+    return launch_split_t<decltype(TD)::value, 4, decltype(TW)::value, decltype(CB)::value, 2, 2, P>(
+        x, w4, wtail, bias, y, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, stats, occ, st);
+  };
+  if (r == 32) return Cout % 64 == 0 ? go(IntC<2>{}, IntC<32>{}, IntC<2>{}) : go(IntC<2>{}, IntC<32>{}, IntC<1>{});
+  return Cout % 64 == 0 ? go(IntC<4>{}, IntC<16>{}, IntC<2>{}) : go(IntC<4>{}, IntC<16>{}, IntC<1>{});
+}
 
 } // namespace

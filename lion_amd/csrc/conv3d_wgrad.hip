@@ -464,12 +464,8 @@ static int launch_wgrad(const float *x, const float *gy, int B, int Cin, int Cou
                         hipStream_t st) {
   constexpr int HALO = (TD + 2) * (TH + 2) * (TW + 2);
   const size_t lds = (size_t)(32 * 257 + CIT * HALO) * 4;
-  static LionLdsLimit cfg = {};
-  if (int e = lion_dynamic_lds(&conv3d_wgrad_kernel<TD, TH, TW, CIT>, lds, cfg)) return e;
-  conv3d_wgrad_kernel<TD, TH, TW, CIT><<<dim3(B * TS, Cin / CIT, Cout / 32), 256, lds, st>>>(x, gy, Cin, Cout, r, TS,
-                                                                                           partial);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv3d_wgrad_kernel<TD, TH, TW, CIT>>(dim3(B * TS, Cin / CIT, Cout / 32), 256, lds, st, x, gy, Cin,
+                                                           Cout, r, TS, partial);
 }
 
 template <int TD, int TH, int TW, int CIT>
@@ -478,13 +474,10 @@ static int launch_wgrad_split(const float *x, const float *gy, int B, int Cin, i
   constexpr int HALO = (TD + 2) * (TH + 2) * (TW + 2);
   size_t lds = (size_t)(32 * WG_GS + CIT * HALO) * 4;
   if (lds < (size_t)4 * 16 * 64 * 4) lds = (size_t)4 * 16 * 64 * 4; // the epilogue's [4][16][64] reduction buffer
-  static LionLdsLimit cfg = {};
-  if (int e = lion_dynamic_lds(&conv3d_wgrad_split_kernel<TD, TH, TW, CIT>, lds, cfg)) return e;
   const int units = B * TS * (Cout / 32), nci = Cin / CIT;
-  conv3d_wgrad_split_kernel<TD, TH, TW, CIT><<<dim3((unsigned)(((units + 7) / 8) * 8 * nci)), 256, lds, st>>>(
-      x, gy, Cin, Cout, r, TS, units, skip, partial);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv3d_wgrad_split_kernel<TD, TH, TW, CIT>>(dim3((unsigned)(((units + 7) / 8) * 8 * nci)), 256,
+                                                                 lds, st, x, gy, Cin, Cout, r, TS, units, skip,
+                                                                 partial);
 }
 
 } // namespace
@@ -522,9 +515,7 @@ int lion_conv3d_k3_wgrad(const float *x, const float *gy, int B, int Cin, int Co
   else rc = c8 ? launch_wgrad<4, 8, 8, 8>(x, gy, B, Cin, Cout, r, TS, ws, st) : launch_wgrad<4, 8, 8, 4>(x, gy, B, Cin, Cout, r, TS, ws, st);
   if (rc) return rc;
   const size_t n = (size_t)Cout * Cin * 27;
-  conv3d_wgrad_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(ws, B * TS, n, gw);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv3d_wgrad_reduce_kernel>((unsigned)((n + 255) / 256), 256, 0, st, ws, B * TS, n, gw);
 }
 
 // The same gradient on the 16-bit matrix pipe at fp32 accuracy (conv3d_wgrad_split_kernel above): same arguments and
@@ -545,16 +536,14 @@ static int wgrad_split_impl(const float *x, const float *gy, const int32_t *cnt,
     const size_t used = (size_t)B * TS * n;
     if (ws_floats < used + ((size_t)B * ntiles + 3) / 4) return LION_EWORKSPACE;
     skip = reinterpret_cast<unsigned char *>(ws + used);
-    wgrad_tile_skip_kernel<<<B, 256, 0, st>>>(cnt, r, td, th, skip);
+    if (int e = lion_launch<wgrad_tile_skip_kernel>(B, 256, 0, st, cnt, r, td, th, skip)) return e;
   }
   int rc;
   if (r == 32) rc = launch_wgrad_split<2, 4, 32, 8>(x, gy, B, Cin, Cout, r, TS, skip, ws, st);
   else if (r == 16) rc = launch_wgrad_split<4, 4, 16, 8>(x, gy, B, Cin, Cout, r, TS, skip, ws, st);
   else rc = launch_wgrad_split<4, 8, 8, 8>(x, gy, B, Cin, Cout, r, TS, skip, ws, st);
   if (rc) return rc;
-  conv3d_wgrad_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(ws, B * TS, n, gw);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<conv3d_wgrad_reduce_kernel>((unsigned)((n + 255) / 256), 256, 0, st, ws, B * TS, n, gw);
 }
 
 int lion_conv3d_k3_wgrad_split(const float *x, const float *gy, int B, int Cin, int Cout, int r, float *gw, float *ws,

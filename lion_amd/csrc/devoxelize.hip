@@ -20,8 +20,6 @@
 
 namespace {
 
-template <bool V> struct BoolT { static constexpr bool value = V; };
-
 struct Corners {
   int ix[8];
   float w[8];
@@ -604,7 +602,7 @@ __global__ __launch_bounds__(DVR_NT) void devox_ring_kernel(const float *__restr
         a4[p] = a;
       }
     };
-    if (wave_generic) gather(BoolT<true>{}); else gather(BoolT<false>{});
+    if (wave_generic) gather(BoolC<true>{}); else gather(BoolC<false>{});
     // one store per (point slot, channel) from every wave: the counted waits above rely on it
 #pragma unroll
     for (int p = 0; p < PP; ++p) {
@@ -720,6 +718,21 @@ static int devox_ring_depth() { // LION_DEVOX_RING: A/B switch (2 = one channel 
   return d < 2 ? 2 : d;
 }
 
+// The ring kernel's gather (MODE 0: corners from the coordinates, MODE 1: from a stored plan), with the one choice of
+// its channels per workgroup and grid.
+template <int MODE>
+static int devox_ring_launch(const float *coords, const float *feat, int B, int C, int N, int training, float *out,
+                             int32_t *inds, float *wgts, const float *scale, const float *shift, unsigned char *plan,
+                             hipStream_t st) {
+  int CT = 8; // one workgroup per CU: the per-cloud setup is amortised over CT channels
+  while (CT > 1 && (long)B * lion_cdiv(C, CT) < 256) CT >>= 1;
+  return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
+    return lion_launch<devox_ring_kernel<decltype(AFFINE)::value, DVR_G, MODE>>(
+        dim3(lion_cdiv(C, CT), B), DVR_NT, DVR_LDS, st, coords, feat, C, N, CT, training, out, inds, wgts, scale, shift,
+        devox_ring_depth(), plan);
+  });
+}
+
 extern "C" {
 
 static int devox_launch(const float *coords, const float *feat, int B, int C, int N, int r,
@@ -728,19 +741,7 @@ static int devox_launch(const float *coords, const float *feat, int B, int C, in
   const int r2 = r * r;
   // r = 32 (the large calls): compacted needed pieces of rows through a ring of LDS buffers
   if (r == DVR_R && N <= 2048 && (((uintptr_t)feat) & 15) == 0) {
-    int CT = 8; // one workgroup per CU: the per-cloud setup is amortised over CT channels
-    while (CT > 1 && (long)B * lion_cdiv(C, CT) < 256) CT >>= 1;
-    dim3 grid(lion_cdiv(C, CT), B);
-    static LionLdsLimit cfgr0 = {}, cfgr1 = {};
-    if (scale) {
-      if (int e = lion_dynamic_lds(&devox_ring_kernel<true, DVR_G, 0>, DVR_LDS, cfgr1)) return e;
-      devox_ring_kernel<true, DVR_G, 0><<<grid, DVR_NT, DVR_LDS, st>>>(coords, feat, C, N, CT, training, out, inds, wgts, scale, shift, devox_ring_depth(), nullptr);
-    } else {
-      if (int e = lion_dynamic_lds(&devox_ring_kernel<false, DVR_G, 0>, DVR_LDS, cfgr0)) return e;
-      devox_ring_kernel<false, DVR_G, 0><<<grid, DVR_NT, DVR_LDS, st>>>(coords, feat, C, N, CT, training, out, inds, wgts, scale, shift, devox_ring_depth(), nullptr);
-    }
-    LION_LAUNCH_CHECK();
-    return 0;
+    return devox_ring_launch<0>(coords, feat, B, C, N, training, out, inds, wgts, scale, shift, nullptr, st);
   }
   // LDS-staged path: slabs of <= 9216 floats (36 KiB), two buffers
   if ((r2 % 4) == 0 && N <= 2048 && r2 <= 4608 && (((uintptr_t)feat) & 15) == 0) {
@@ -758,44 +759,31 @@ static int devox_launch(const float *coords, const float *feat, int B, int C, in
     int CT = 4 * CI;
     while (CT > CI && (long)B * lion_cdiv(C, CT) < 512) CT >>= 1;
     dim3 grid(lion_cdiv(C, CT), B);
-#define DEVOX_SLAB(LD_)                                                                                    \
-  {                                                                                                        \
-    static LionLdsLimit cfg0 = {}, cfg1 = {};                                                              \
-    if (scale) {                                                                                           \
-      if (int e = lion_dynamic_lds(&devox_slab_kernel<LD_, true>, lds, cfg1)) return e;                    \
-      devox_slab_kernel<LD_, true><<<grid, 256, lds, st>>>(coords, feat, C, N, r, PX, XS, CT, CI, slab_floats, \
-                                                           training, out, inds, wgts, scale, shift);       \
-    } else {                                                                                               \
-      if (int e = lion_dynamic_lds(&devox_slab_kernel<LD_, false>, lds, cfg0)) return e;                   \
-      devox_slab_kernel<LD_, false><<<grid, 256, lds, st>>>(coords, feat, C, N, r, PX, XS, CT, CI, slab_floats, \
-                                                            training, out, inds, wgts, scale, shift);      \
-    }                                                                                                      \
-  }
-    if (ld <= 1) DEVOX_SLAB(1)
-    else if (ld <= 2) DEVOX_SLAB(2)
-    else if (ld <= 4) DEVOX_SLAB(4)
-    else DEVOX_SLAB(9)
-#undef DEVOX_SLAB
-    LION_LAUNCH_CHECK();
-    return 0;
+    auto slab = [&](auto LD) {
+      return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
+        return lion_launch<devox_slab_kernel<decltype(LD)::value, decltype(AFFINE)::value>>(
+            grid, 256, lds, st, coords, feat, C, N, r, PX, XS, CT, CI, slab_floats, training, out, inds, wgts, scale, shift);
+      });
+    };
+    return ld <= 1 ? slab(IntC<1>{}) : ld <= 2 ? slab(IntC<2>{}) : ld <= 4 ? slab(IntC<4>{}) : slab(IntC<9>{});
   }
   const int pt = lion_cdiv(N, 256);
   // channel tile: keep >= ~2048 workgroups in flight, amortise the corner computation
   int ct = 16;
   while (ct > 2 && (long)B * pt * lion_cdiv(C, ct) < 2048) ct >>= 1;
   dim3 grid(pt, lion_cdiv(C, ct), B);
-#define DEVOX_CASE(CT_)                                                                                   \
-  if (scale) devox_fwd_kernel<CT_, true><<<grid, 256, 0, st>>>(coords, feat, C, N, r, training, out, inds, wgts, scale, shift); \
-  else devox_fwd_kernel<CT_, false><<<grid, 256, 0, st>>>(coords, feat, C, N, r, training, out, inds, wgts, scale, shift)
+  auto fwd = [&](auto CT) {
+    return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
+      return lion_launch<devox_fwd_kernel<decltype(CT)::value, decltype(AFFINE)::value>>(
+          grid, 256, 0, st, coords, feat, C, N, r, training, out, inds, wgts, scale, shift);
+    });
+  };
   switch (ct) {
-  case 16: DEVOX_CASE(16); break;
-  case 8:  DEVOX_CASE(8); break;
-  case 4:  DEVOX_CASE(4); break;
-  default: DEVOX_CASE(2); break;
+  case 16: return fwd(IntC<16>{});
+  case 8:  return fwd(IntC<8>{});
+  case 4:  return fwd(IntC<4>{});
+  default: return fwd(IntC<2>{});
   }
-#undef DEVOX_CASE
-  LION_LAUNCH_CHECK();
-  return 0;
 }
 
 int lion_trilinear_devoxelize_forward(const float *coords, const float *feat, int B, int C, int N,
@@ -830,13 +818,10 @@ int lion_trilinear_devoxelize_plan(const float *coords, int B, int N, int r, voi
   const size_t need = lion_devoxelize_plan_bytes(B, N, r);
   if (!need || (((uintptr_t)plan) & 15) != 0) return LION_EUNSUPPORTED;
   if (plan_bytes < need) return LION_EWORKSPACE;
-  static LionLdsLimit cfg = {};
-  if (int e = lion_dynamic_lds(&devox_ring_kernel<false, DVR_G, 2>, DVR_LDS, cfg)) return e;
-  devox_ring_kernel<false, DVR_G, 2><<<dim3(1, B), DVR_NT, DVR_LDS, static_cast<hipStream_t>(stream)>>>(
-      coords, nullptr, 1, N, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, devox_ring_depth(),
-      static_cast<unsigned char *>(plan));
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<devox_ring_kernel<false, DVR_G, 2>>(dim3(1, B), DVR_NT, DVR_LDS, static_cast<hipStream_t>(stream),
+                                                         coords, nullptr, 1, N, 1, 0, nullptr, nullptr, nullptr,
+                                                         nullptr, nullptr, devox_ring_depth(),
+                                                         static_cast<unsigned char *>(plan));
 }
 
 // trilinear_devoxelize (eval) of feat f32[B,C,32^3] at the plan's coordinates (the SAME coords the plan was made from);
@@ -850,20 +835,8 @@ int lion_trilinear_devoxelize_planned_forward(const void *plan, size_t plan_byte
   if (!need || (((uintptr_t)plan) & 15) != 0 || (((uintptr_t)feat) & 15) != 0) return LION_EUNSUPPORTED;
   if (plan_bytes < need) return LION_EWORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int CT = 8;
-  while (CT > 1 && (long)B * lion_cdiv(C, CT) < 256) CT >>= 1;
-  dim3 grid(lion_cdiv(C, CT), B);
   unsigned char *pl = const_cast<unsigned char *>(static_cast<const unsigned char *>(plan));
-  static LionLdsLimit cfg0 = {}, cfg1 = {};
-  if (scale) {
-    if (int e = lion_dynamic_lds(&devox_ring_kernel<true, DVR_G, 1>, DVR_LDS, cfg1)) return e;
-    devox_ring_kernel<true, DVR_G, 1><<<grid, DVR_NT, DVR_LDS, st>>>(coords, feat, C, N, CT, 0, out, nullptr, nullptr, scale, shift, devox_ring_depth(), pl);
-  } else {
-    if (int e = lion_dynamic_lds(&devox_ring_kernel<false, DVR_G, 1>, DVR_LDS, cfg0)) return e;
-    devox_ring_kernel<false, DVR_G, 1><<<grid, DVR_NT, DVR_LDS, st>>>(coords, feat, C, N, CT, 0, out, nullptr, nullptr, nullptr, nullptr, devox_ring_depth(), pl);
-  }
-  LION_LAUNCH_CHECK();
-  return 0;
+  return devox_ring_launch<1>(coords, feat, B, C, N, 0, out, nullptr, nullptr, scale, shift, pl, st);
 }
 
 int lion_trilinear_devoxelize_backward(const float *gy, const int32_t *inds, const float *wgts,
@@ -877,20 +850,14 @@ int lion_trilinear_devoxelize_backward(const float *gy, const int32_t *inds, con
     int parts = (size_t)r3 * 4 > 64 * 1024 ? 2 : 1;
     if (r3 % (4 * parts) != 0) parts = 1;
     const size_t lds = (size_t)(r3 / parts) * 4;
-    static LionLdsLimit configured = {};
-    if (int e = lion_dynamic_lds(&devox_bwd_lds_kernel, lds, configured)) return e;
     const int nt = r3 >= 16384 ? 1024 : 256;
-    devox_bwd_lds_kernel<<<dim3(C, B, parts), nt, lds, st>>>(gy, inds, wgts, C, N, r3, gx);
-    LION_LAUNCH_CHECK();
-    return 0;
+    return lion_launch<devox_bwd_lds_kernel>(dim3(C, B, parts), nt, lds, st, gy, inds, wgts, C, N, r3, gx);
   }
   hipError_t e = hipMemsetAsync(gx, 0, (size_t)B * C * r3 * 4, st);
   if (e != hipSuccess) return (int)e;
   const int CT = 8;
-  devox_bwd_atomic_kernel<<<dim3(lion_cdiv(N, 256), lion_cdiv(C, CT), B), 256, 0, st>>>(
-      gy, inds, wgts, C, N, r3, CT, gx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<devox_bwd_atomic_kernel>(dim3(lion_cdiv(N, 256), lion_cdiv(C, CT), B), 256, 0, st, gy, inds, wgts,
+                                              C, N, r3, CT, gx);
 }
 
 // dx f32[B,C,r3] = A' scatter(gy) + Q + R x  (see devox_bwd_affine_kernel); x f32[B,C,r3] 16-byte aligned, r3 * 4 <= 128 KiB, r3 % 8 == 0
@@ -902,12 +869,9 @@ int lion_trilinear_devoxelize_backward_affine(const float *gy, const int32_t *in
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int parts = (size_t)r3 * 4 > 64 * 1024 ? 2 : 1;
   const size_t lds = (size_t)(r3 / parts) * 4;
-  static LionLdsLimit configured = {};
-  if (int e = lion_dynamic_lds(&devox_bwd_affine_kernel, lds, configured)) return e;
   const int nt = r3 >= 16384 ? 1024 : 256;
-  devox_bwd_affine_kernel<<<dim3(C, B, parts), nt, lds, st>>>(gy, inds, wgts, x, Ap, Q, R, C, N, r3, dx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<devox_bwd_affine_kernel>(dim3(C, B, parts), nt, lds, st, gy, inds, wgts, x, Ap, Q, R, C, N, r3,
+                                              dx);
 }
 
 } // extern "C"

@@ -141,6 +141,15 @@ __global__ void update_noise_kernel(const float *__restrict__ x, const float *__
   }
 }
 
+static int update_noise_launch(int mode, unsigned blocks, hipStream_t st, const float *x, const float *eps, size_t numel,
+                               const float *cur, const uint32_t *seed, uint32_t stream_id, float *out, float *z_out,
+                               int cm_points) {
+  return mode == 0 ? lion_launch<update_noise_kernel<0>>(blocks, 256, 0, st, x, eps, numel, cur, seed, stream_id, out, z_out,
+                                                         cm_points)
+                   : lion_launch<update_noise_kernel<1>>(blocks, 256, 0, st, x, eps, numel, cur, seed, stream_id, out, z_out,
+                                                         cm_points);
+}
+
 } // namespace
 
 extern "C" {
@@ -152,10 +161,8 @@ int lion_ddim_update(const float *x, const float *eps, const float *z, size_t nu
   const bool aligned = ((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)z)) & 15) == 0;
   if (!aligned) return LION_EINVAL; // torch allocations are 256-byte aligned
   const size_t quads = (numel + 3) / 4;
-  ddim_kernel<<<(unsigned)((quads + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      x, eps, z, numel, s, c, sigma, out);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<ddim_kernel>((unsigned)((quads + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), x, eps, z,
+                                  numel, s, c, sigma, out);
 }
 
 int lion_ddpm_update(const float *x, const float *eps, const float *z, size_t numel, int t_is_zero,
@@ -163,29 +170,23 @@ int lion_ddpm_update(const float *x, const float *eps, const float *z, size_t nu
                      lionStream_t stream) {
   if (!x || !eps || !out || numel == 0) return LION_EINVAL;
   if (!t_is_zero && !z) return LION_EINVAL;
-  ddpm_kernel<<<(unsigned)((numel + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      x, eps, z, numel, t_is_zero, k_outer, k_a, k_b, scale, temp, out);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<ddpm_kernel>((unsigned)((numel + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), x, eps, z,
+                                  numel, t_is_zero, k_outer, k_a, k_b, scale, temp, out);
 }
 
 int lion_chain_begin_step(const float *table, int n_steps, int32_t *counter, float *t_out, int B, float *cur,
                           lionStream_t stream) {
   if (!table || !counter || !t_out || !cur || n_steps <= 0 || B <= 0) return LION_EINVAL;
-  begin_step_kernel<<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(table, n_steps, counter, t_out, B, cur, nullptr, 0,
-                                                                    nullptr);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<begin_step_kernel>(1, 64, 0, static_cast<hipStream_t>(stream), table, n_steps, counter, t_out, B,
+                                        cur, nullptr, 0, nullptr);
 }
 
 int lion_chain_begin_step_temb(const float *table, int n_steps, int32_t *counter, float *t_out, int B, float *cur,
                                const float *temb_table, int temb_width, float *temb_out, lionStream_t stream) {
   if (!table || !counter || !t_out || !cur || n_steps <= 0 || B <= 0) return LION_EINVAL;
   if (!temb_table || !temb_out || temb_width <= 0) return LION_EINVAL;
-  begin_step_kernel<<<1, 64, 0, static_cast<hipStream_t>(stream)>>>(table, n_steps, counter, t_out, B, cur, temb_table,
-                                                                    temb_width, temb_out);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<begin_step_kernel>(1, 64, 0, static_cast<hipStream_t>(stream), table, n_steps, counter, t_out, B,
+                                        cur, temb_table, temb_width, temb_out);
 }
 
 int lion_chain_update_noise(int mode, const float *x, const float *eps, size_t numel, const float *cur,
@@ -196,10 +197,7 @@ int lion_chain_update_noise(int mode, const float *x, const float *eps, size_t n
   const size_t quads = (numel + 3) / 4;
   const unsigned blocks = (unsigned)((quads + 255) / 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (mode == 0) update_noise_kernel<0><<<blocks, 256, 0, st>>>(x, eps, numel, cur, seed, stream_id, out, z_out, 0);
-  else update_noise_kernel<1><<<blocks, 256, 0, st>>>(x, eps, numel, cur, seed, stream_id, out, z_out, 0);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return update_noise_launch(mode, blocks, st, x, eps, numel, cur, seed, stream_id, out, z_out, 0);
 }
 
 int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
@@ -209,10 +207,7 @@ int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, in
   const size_t numel = (size_t)B * N * 4, quads = (size_t)B * N;
   const unsigned blocks = (unsigned)((quads + 255) / 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (mode == 0) update_noise_kernel<0><<<blocks, 256, 0, st>>>(x, eps_cm, numel, cur, seed, stream_id, out, z_out, N);
-  else update_noise_kernel<1><<<blocks, 256, 0, st>>>(x, eps_cm, numel, cur, seed, stream_id, out, z_out, N);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return update_noise_launch(mode, blocks, st, x, eps_cm, numel, cur, seed, stream_id, out, z_out, N);
 }
 
 } // extern "C"

@@ -541,19 +541,23 @@ int lion_emd_approxmatch(const float *xyz1, const float *xyz2, int B, int N, int
   if (N >= M) { multiL = 1.f; multiR = (float)(N / M); }
   else { multiL = (float)(M / N); multiR = 1.f; }
   const int nmax = N > M ? N : M;
-  emd_init_kernel<<<dim3(lion_cdiv(nmax, 256), B), 256, 0, st>>>(N, M, multiL, multiR, remainL, remainR);
+  if (int e = lion_launch<emd_init_kernel>(dim3(lion_cdiv(nmax, 256), B), 256, 0, st, N, M, multiL, multiR, remainL,
+                                           remainR))
+    return e;
   const dim3 gn(lion_cdiv(N, EMD_ROWS), B), gm(lion_cdiv(M, EMD_ROWS), B);
   for (int j = 7; j >= -2; --j) {
     float level = -powf(4.0f, (float)j); // :45-48
     if (j == -2) level = 0.f;
-    emd_pass1_kernel<<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, level, remainL, remainR, ratioL);
-    emd_pass2_kernel<<<gm, 256, 0, st>>>(xyz1, xyz2, N, M, level, ratioL, remainR, ratioR);
-    if (j == 7)
-      emd_pass3_kernel<true><<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, level, ratioL, ratioR, remainL, match);
-    else
-      emd_pass3_kernel<false><<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, level, ratioL, ratioR, remainL, match);
+    if (int e = lion_launch<emd_pass1_kernel>(gn, 256, 0, st, xyz1, xyz2, N, M, level, remainL, remainR, ratioL))
+      return e;
+    if (int e = lion_launch<emd_pass2_kernel>(gm, 256, 0, st, xyz1, xyz2, N, M, level, ratioL, remainR, ratioR))
+      return e;
+    const int e3 = lion_with_flags(j == 7, [&](auto FIRST) {
+      return lion_launch<emd_pass3_kernel<decltype(FIRST)::value>>(gn, 256, 0, st, xyz1, xyz2, N, M, level, ratioL, ratioR,
+                                                                   remainL, match);
+    });
+    if (e3) return e3;
   }
-  LION_LAUNCH_CHECK();
   return 0;
 }
 
@@ -572,33 +576,33 @@ int lion_emd_cost(const float *xyz1, const float *xyz2, int B, int N, int M, flo
   if (N >= M) { multiL = 1.f; multiR = (float)(N / M); }
   else { multiL = (float)(M / N); multiR = 1.f; }
   const int nmax = N > M ? N : M;
-  emd_init_kernel<<<dim3(lion_cdiv(nmax, 256), B), 256, 0, st>>>(N, M, multiL, multiR, remainL, remainR);
+  if (int e = lion_launch<emd_init_kernel>(dim3(lion_cdiv(nmax, 256), B), 256, 0, st, N, M, multiL, multiR, remainL,
+                                           remainR))
+    return e;
   const dim3 gn(lion_cdiv(N, EMD_FROWS), B), gm(lion_cdiv(M, EMD_FROWS), B);
   // round 6 (see emd_fast_*): pass 1 of the first level, then per level [pass 2, pass 3 + pass 1 of the next level]
   const float LOG2E = 1.4426950408889634f;
   auto level_of = [](int j) { return j == -2 ? 0.f : -powf(4.0f, (float)j); };   // :45-48
   auto scale_of = [&](float level) { return level < 0.f ? sqrtf(-level * LOG2E) : 0.f; };
-  emd_fast_pass1_kernel<<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, scale_of(level_of(7)), remainL, remainR, ratioL);
+  if (int e = lion_launch<emd_fast_pass1_kernel>(gn, 256, 0, st, xyz1, xyz2, N, M, scale_of(level_of(7)), remainL,
+                                                 remainR, ratioL))
+    return e;
   for (int j = 7; j >= -2; --j) {
     const float level = level_of(j), sc = scale_of(level);
     const float inv_s2 = sc > 0.f ? 1.0f / (sc * sc) : 1.f;
-    emd_fast_pass2_kernel<<<gm, 256, 0, st>>>(xyz1, xyz2, N, M, sc, ratioL, remainR, ratioR);
-    if (j == -2) {
-      emd_fast_pass31_kernel<false, false><<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, sc, inv_s2, 0.f, ratioL, ratioR, remainR,
-                                                                remainL, costrow);
-    } else {
-      const float next_ratio = level_of(j - 1) / level;     // 0.25; 0 for the step onto level 0
-      if (j == 7)
-        emd_fast_pass31_kernel<true, true><<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, sc, inv_s2, next_ratio, ratioL, ratioR,
-                                                               remainR, remainL, costrow);
-      else
-        emd_fast_pass31_kernel<false, true><<<gn, 256, 0, st>>>(xyz1, xyz2, N, M, sc, inv_s2, next_ratio, ratioL, ratioR,
-                                                                remainR, remainL, costrow);
-    }
+    if (int e = lion_launch<emd_fast_pass2_kernel>(gm, 256, 0, st, xyz1, xyz2, N, M, sc, ratioL, remainR, ratioR))
+      return e;
+    auto pass31 = [&](auto FIRST, auto NEXT, float next_ratio) {
+      return lion_launch<emd_fast_pass31_kernel<decltype(FIRST)::value, decltype(NEXT)::value>>(
+          gn, 256, 0, st, xyz1, xyz2, N, M, sc, inv_s2, next_ratio, ratioL, ratioR, remainR, remainL, costrow);
+    };
+    const float next_ratio = j == -2 ? 0.f : level_of(j - 1) / level; // 0.25; 0 for the step onto level 0
+    const int e31 = j == -2  ? pass31(BoolC<false>{}, BoolC<false>{}, 0.f) // the last level prepares no next one
+                    : j == 7 ? pass31(BoolC<true>{}, BoolC<true>{}, next_ratio)
+                             : pass31(BoolC<false>{}, BoolC<true>{}, next_ratio);
+    if (e31) return e31;
   }
-  emd_costrow_sum_kernel<<<B, 256, 0, st>>>(costrow, N, cost);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<emd_costrow_sum_kernel>(B, 256, 0, st, costrow, N, cost);
 }
 
 int lion_emd_matchcost(const float *xyz1, const float *xyz2, const float *match, int B, int N, int M,
@@ -608,10 +612,8 @@ int lion_emd_matchcost(const float *xyz1, const float *xyz2, const float *match,
   hipStream_t st = static_cast<hipStream_t>(stream);
   float *partial = static_cast<float *>(ws) + (size_t)B * (2 * (size_t)N + 2 * (size_t)M);
   const int nb = lion_cdiv(N, 256);
-  emd_cost_partial_kernel<<<dim3(nb, B), 256, 0, st>>>(xyz1, xyz2, match, N, M, partial);
-  emd_cost_final_kernel<<<lion_cdiv(B, 64), 64, 0, st>>>(partial, nb, B, cost);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<emd_cost_partial_kernel>(dim3(nb, B), 256, 0, st, xyz1, xyz2, match, N, M, partial)) return e;
+  return lion_launch<emd_cost_final_kernel>(lion_cdiv(B, 64), 64, 0, st, partial, nb, B, cost);
 }
 
 int lion_emd_matchcost_backward(const float *grad_cost, const float *xyz1, const float *xyz2,
@@ -620,10 +622,10 @@ int lion_emd_matchcost_backward(const float *grad_cost, const float *xyz1, const
   if (!grad_cost || !xyz1 || !xyz2 || !match || !grad1 || !grad2 || B <= 0 || N <= 0 || M <= 0)
     return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  emd_grad1_kernel<<<dim3(lion_cdiv(N, 256), B), 256, 0, st>>>(grad_cost, xyz1, xyz2, match, N, M, grad1);
-  emd_grad2_kernel<<<dim3(lion_cdiv(M, 4), B), 256, 0, st>>>(grad_cost, xyz1, xyz2, match, N, M, grad2);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<emd_grad1_kernel>(dim3(lion_cdiv(N, 256), B), 256, 0, st, grad_cost, xyz1, xyz2, match, N, M,
+                                            grad1))
+    return e;
+  return lion_launch<emd_grad2_kernel>(dim3(lion_cdiv(M, 4), B), 256, 0, st, grad_cost, xyz1, xyz2, match, N, M, grad2);
 }
 
 } // extern "C"

@@ -95,15 +95,11 @@ static int scatter_rows(const float *gy, const int32_t *idx, int B, int C, int N
     if (CT > C) CT = C;
     while (CT > 1 && (long)B * lion_cdiv(C, CT) < 1024) CT >>= 1;
     const size_t lds = (size_t)CT * N * 4;
-    scatter_rows_lds_kernel<<<dim3(lion_cdiv(C, CT), B), 512, lds, st>>>(gy, idx, C, N, MU, CT, gx);
-    LION_LAUNCH_CHECK();
-    return 0;
+    return lion_launch<scatter_rows_lds_kernel>(dim3(lion_cdiv(C, CT), B), 512, lds, st, gy, idx, C, N, MU, CT, gx);
   }
   hipError_t e = hipMemsetAsync(gx, 0, (size_t)B * C * N * 4, st);
   if (e != hipSuccess) return (int)e;
-  scatter_rows_atomic_kernel<<<dim3(lion_cdiv(MU, 256), C, B), 256, 0, st>>>(gy, idx, C, N, MU, gx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<scatter_rows_atomic_kernel>(dim3(lion_cdiv(MU, 256), C, B), 256, 0, st, gy, idx, C, N, MU, gx);
 }
 
 } // namespace
@@ -138,15 +134,16 @@ static int grouping_launch(const float *feat, const int32_t *idx, int B, int C, 
   while (ct > 1 && (long)B * et * lion_cdiv(C, ct) < 2048) ct >>= 1;
   dim3 grid(et, lion_cdiv(C, ct), B);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  auto go = [&](auto CT) {
+    return lion_launch<grouping_fwd_kernel<decltype(CT)::value>>(grid, 256, 0, st, feat, idx, C, N, MU, Ctot, U, centers, out);
+  };
   switch (ct) {
-  case 16: grouping_fwd_kernel<16><<<grid, 256, 0, st>>>(feat, idx, C, N, MU, Ctot, U, centers, out); break;
-  case 8:  grouping_fwd_kernel<8><<<grid, 256, 0, st>>>(feat, idx, C, N, MU, Ctot, U, centers, out); break;
-  case 4:  grouping_fwd_kernel<4><<<grid, 256, 0, st>>>(feat, idx, C, N, MU, Ctot, U, centers, out); break;
-  case 2:  grouping_fwd_kernel<2><<<grid, 256, 0, st>>>(feat, idx, C, N, MU, Ctot, U, centers, out); break;
-  default: grouping_fwd_kernel<1><<<grid, 256, 0, st>>>(feat, idx, C, N, MU, Ctot, U, centers, out); break;
+  case 16: return go(IntC<16>{});
+  case 8:  return go(IntC<8>{});
+  case 4:  return go(IntC<4>{});
+  case 2:  return go(IntC<2>{});
+  default: return go(IntC<1>{});
   }
-  LION_LAUNCH_CHECK();
-  return 0;
 }
 
 int lion_grouping_backward(const float *gy, const int32_t *idx, int B, int C, int N, int M, int U,

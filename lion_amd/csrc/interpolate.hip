@@ -196,6 +196,16 @@ __global__ void three_nn_interp_grad_atomic_kernel(const float *__restrict__ gy,
   }
 }
 
+// channels per workgroup of the interpolation kernels, ct in {16, 8, 4, 2} -> f(IntC<ct>)
+template <typename F> static int nn_channel_tile(int ct, F f) {
+  switch (ct) {
+  case 16: return f(IntC<16>{});
+  case 8:  return f(IntC<8>{});
+  case 4:  return f(IntC<4>{});
+  default: return f(IntC<2>{});
+  }
+}
+
 } // namespace
 
 extern "C" {
@@ -206,21 +216,17 @@ int lion_three_nn_interpolate_forward(const float *points, const float *centers,
   if (!points || !centers || !idx || !wgt || B <= 0 || N <= 0 || M <= 0) return LION_EINVAL;
   if (cfeat && (!out || C <= 0)) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  three_nn_kernel<<<dim3(lion_cdiv(N, 256 / NN_SPLIT), B), 256, 0, st>>>(points, centers, N, M, idx, wgt);
-  LION_LAUNCH_CHECK();
+  if (int e = lion_launch<three_nn_kernel>(dim3(lion_cdiv(N, 256 / NN_SPLIT), B), 256, 0, st, points, centers, N, M,
+                                           idx, wgt))
+    return e;
   if (!cfeat) return 0;
   const int pt = lion_cdiv(N, 256);
   int ct = 16;
   while (ct > 2 && (long)B * pt * lion_cdiv(C, ct) < 2048) ct >>= 1;
   dim3 grid(pt, lion_cdiv(C, ct), B);
-  switch (ct) {
-  case 16: three_nn_interp_kernel<16><<<grid, 256, 0, st>>>(cfeat, idx, wgt, C, N, M, out); break;
-  case 8:  three_nn_interp_kernel<8><<<grid, 256, 0, st>>>(cfeat, idx, wgt, C, N, M, out); break;
-  case 4:  three_nn_interp_kernel<4><<<grid, 256, 0, st>>>(cfeat, idx, wgt, C, N, M, out); break;
-  default: three_nn_interp_kernel<2><<<grid, 256, 0, st>>>(cfeat, idx, wgt, C, N, M, out); break;
-  }
-  LION_LAUNCH_CHECK();
-  return 0;
+  return nn_channel_tile(ct, [&](auto CT) {
+    return lion_launch<three_nn_interp_kernel<decltype(CT)::value>>(grid, 256, 0, st, cfeat, idx, wgt, C, N, M, out);
+  });
 }
 
 int lion_three_nn_interpolate_cat_forward(const float *points, const float *centers, const float *cfeat, const float *temb,
@@ -229,22 +235,17 @@ int lion_three_nn_interpolate_cat_forward(const float *points, const float *cent
   if (!points || !centers || !cfeat || !out || !idx || !wgt || B <= 0 || N <= 0 || M <= 0 || C1 <= 0) return LION_EINVAL;
   if (C2 < 0 || C3 < 0 || (C2 > 0 && !temb) || (C3 > 0 && !skip) || ld_t < 0) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  three_nn_kernel<<<dim3(lion_cdiv(N, 256 / NN_SPLIT), B), 256, 0, st>>>(points, centers, N, M, idx, wgt);
-  LION_LAUNCH_CHECK();
+  if (int e = lion_launch<three_nn_kernel>(dim3(lion_cdiv(N, 256 / NN_SPLIT), B), 256, 0, st, points, centers, N, M,
+                                           idx, wgt))
+    return e;
   const int C = C1 + C2 + C3, pt = lion_cdiv(N, 256);
   int ct = 16;
   while (ct > 2 && (long)B * pt * lion_cdiv(C, ct) < 2048) ct >>= 1;
   dim3 grid(pt, lion_cdiv(C, ct), B);
-#define LION_NN_CAT(CT_) three_nn_interp_cat_kernel<CT_><<<grid, 256, 0, st>>>(cfeat, temb, ld_t, skip, idx, wgt, C1, C2, C3, N, M, out)
-  switch (ct) {
-  case 16: LION_NN_CAT(16); break;
-  case 8:  LION_NN_CAT(8); break;
-  case 4:  LION_NN_CAT(4); break;
-  default: LION_NN_CAT(2); break;
-  }
-#undef LION_NN_CAT
-  LION_LAUNCH_CHECK();
-  return 0;
+  return nn_channel_tile(ct, [&](auto CT) {
+    return lion_launch<three_nn_interp_cat_kernel<decltype(CT)::value>>(grid, 256, 0, st, cfeat, temb, ld_t, skip, idx, wgt, C1,
+                                                                        C2, C3, N, M, out);
+  });
 }
 
 int lion_three_nn_interpolate_backward(const float *gy, const int32_t *idx, const float *wgt, int B,
@@ -256,17 +257,13 @@ int lion_three_nn_interpolate_backward(const float *gy, const int32_t *idx, cons
     if (CT > 8) CT = 8;
     if (CT > C) CT = C;
     while (CT > 1 && (long)B * lion_cdiv(C, CT) < 1024) CT >>= 1;
-    three_nn_interp_grad_kernel<<<dim3(lion_cdiv(C, CT), B), 512, (size_t)CT * M * 4, st>>>(
-        gy, idx, wgt, C, N, M, CT, gx);
-    LION_LAUNCH_CHECK();
-    return 0;
+    return lion_launch<three_nn_interp_grad_kernel>(dim3(lion_cdiv(C, CT), B), 512, (size_t)CT * M * 4, st, gy, idx,
+                                                    wgt, C, N, M, CT, gx);
   }
   hipError_t e = hipMemsetAsync(gx, 0, (size_t)B * C * M * 4, st);
   if (e != hipSuccess) return (int)e;
-  three_nn_interp_grad_atomic_kernel<<<dim3(lion_cdiv(N, 256), C, B), 256, 0, st>>>(gy, idx, wgt, C,
-                                                                                  N, M, gx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<three_nn_interp_grad_atomic_kernel>(dim3(lion_cdiv(N, 256), C, B), 256, 0, st, gy, idx, wgt, C, N,
+                                                         M, gx);
 }
 
 } // extern "C"

@@ -508,6 +508,17 @@ __global__ __launch_bounds__(256) void se_gate_wgrad_kernel(const float *__restr
   (blockIdx.y == 0 ? dw2 : dw1)[i] = acc;
 }
 
+// the affine_act_max kernels' template argument: U in {8, 16, 32, 64} -> f(IntC<U / 4>)
+template <typename F> static int aam_dispatch(int U, F f) {
+  switch (U) {
+  case 8:  return f(IntC<2>{});
+  case 16: return f(IntC<4>{});
+  case 32: return f(IntC<8>{});
+  case 64: return f(IntC<16>{});
+  default: return LION_EUNSUPPORTED;
+  }
+}
+
 extern "C" {
 
 int lion_gn_train_fold(const float *stats, const float *gw, const float *gb, const float *fac, int fac_stride,
@@ -516,19 +527,16 @@ int lion_gn_train_fold(const float *stats, const float *gw, const float *gb, con
   if (!stats || !gw || !gb || !A || !Bs || !mean || !rstd || B <= 0 || C <= 0 || G <= 0 || C % G || L <= 0) return LION_EINVAL;
   if (C > 1024) return LION_EUNSUPPORTED;
   const int T = (C + 63) / 64 * 64;
-  gn_train_fold_kernel<float><<<B, T, (size_t)2 * C * sizeof(double), static_cast<hipStream_t>(stream)>>>(
-      stats, gw, gb, fac, fac_stride, bias, bias_stride, C, G, L, eps, A, Bs, mean, rstd);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<gn_train_fold_kernel<float>>(B, T, (size_t)2 * C * sizeof(double),
+                                                  static_cast<hipStream_t>(stream), stats, gw, gb, fac, fac_stride,
+                                                  bias, bias_stride, C, G, L, eps, A, Bs, mean, rstd);
 }
 
 // the training path's statistics: row sums carried out on shifted values and handed over in double (see
 // row_stats64_kernel); lion_gn_train_fold64 = lion_gn_train_fold on those
 int lion_row_stats64(const float *x, int rows, int L, double *stats, lionStream_t stream) {
   if (!x || !stats || rows <= 0 || L <= 0) return LION_EINVAL;
-  row_stats64_kernel<<<rows, 256, 0, static_cast<hipStream_t>(stream)>>>(x, L, stats);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<row_stats64_kernel>(rows, 256, 0, static_cast<hipStream_t>(stream), x, L, stats);
 }
 
 int lion_gn_train_fold64(const double *stats, const float *gw, const float *gb, const float *fac, int fac_stride,
@@ -537,10 +545,9 @@ int lion_gn_train_fold64(const double *stats, const float *gw, const float *gb, 
   if (!stats || !gw || !gb || !A || !Bs || !mean || !rstd || B <= 0 || C <= 0 || G <= 0 || C % G || L <= 0) return LION_EINVAL;
   if (C > 1024) return LION_EUNSUPPORTED;
   const int T = (C + 63) / 64 * 64;
-  gn_train_fold_kernel<double><<<B, T, (size_t)2 * C * sizeof(double), static_cast<hipStream_t>(stream)>>>(
-      stats, gw, gb, fac, fac_stride, bias, bias_stride, C, G, L, eps, A, Bs, mean, rstd);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<gn_train_fold_kernel<double>>(B, T, (size_t)2 * C * sizeof(double),
+                                                   static_cast<hipStream_t>(stream), stats, gw, gb, fac, fac_stride,
+                                                   bias, bias_stride, C, G, L, eps, A, Bs, mean, rstd);
 }
 
 int lion_gn_train_bwd_fold(const float *S, const float *mean, const float *rstd, const float *gw, const float *gb,
@@ -552,10 +559,9 @@ int lion_gn_train_bwd_fold(const float *S, const float *mean, const float *rstd,
   if ((gate != nullptr) != (qse != nullptr) || (gate && (!A || !Aout))) return LION_EINVAL;
   if (C > 1024) return LION_EUNSUPPORTED;
   const int T = (C + 63) / 64 * 64;
-  gn_train_bwd_fold_kernel<<<B, T, (size_t)2 * C * sizeof(double), static_cast<hipStream_t>(stream)>>>(
-      S, mean, rstd, gw, gb, fac, fac_stride, C, G, L, Q, R, dfac, dbias, d_stride, pw, A, xstats, gate, qse, Aout);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<gn_train_bwd_fold_kernel>(B, T, (size_t)2 * C * sizeof(double), static_cast<hipStream_t>(stream),
+                                               S, mean, rstd, gw, gb, fac, fac_stride, C, G, L, Q, R, dfac, dbias,
+                                               d_stride, pw, A, xstats, gate, qse, Aout);
 }
 
 
@@ -574,19 +580,18 @@ static int affine_act_launch(const float *x, const float *A, const float *Bs, in
   if ((long)rows * lion_cdiv(lion_cdiv(L, 4), 256) > 0x7fffffffL) return LION_EUNSUPPORTED;
   const unsigned grid = (unsigned)(rows * lion_cdiv(lion_cdiv(L, 4), 256));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (seed) affine_act_kernel<true><<<grid, 256, 0, st>>>(x, A, Bs, L, act, y, seed, thr, scale);
-  else affine_act_kernel<false><<<grid, 256, 0, st>>>(x, A, Bs, L, act, y, nullptr, 0u, 1.f);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(seed != nullptr, [&](auto DROP) { // without a seed the callers pass thr = 0, scale = 1
+    return lion_launch<affine_act_kernel<decltype(DROP)::value>>(grid, 256, 0, st, x, A, Bs, L, act, y, seed, thr, scale);
+  });
 }
 static int affine_act_bwd_stats_launch(const float *x, const float *gy, const float *A, const float *Bs, int rows, int L, int act,
                                        float *S, const unsigned long long *seed, unsigned thr, float scale, lionStream_t stream) {
   if (!x || !gy || !A || !Bs || !S || rows <= 0 || L <= 0 || (act != 0 && act != 1)) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (seed) affine_act_bwd_stats_kernel<true><<<rows, 256, 0, st>>>(x, gy, A, Bs, L, act, S, seed, thr, scale);
-  else affine_act_bwd_stats_kernel<false><<<rows, 256, 0, st>>>(x, gy, A, Bs, L, act, S, nullptr, 0u, 1.f);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(seed != nullptr, [&](auto DROP) {
+    return lion_launch<affine_act_bwd_stats_kernel<decltype(DROP)::value>>(rows, 256, 0, st, x, gy, A, Bs, L, act, S, seed,
+                                                                           thr, scale);
+  });
 }
 static int affine_act_bwd_apply_launch(const float *x, const float *gy, const float *A, const float *Bs, const float *Q,
                                        const float *R, int rows, int L, int act, float *dx, const unsigned long long *seed,
@@ -595,10 +600,10 @@ static int affine_act_bwd_apply_launch(const float *x, const float *gy, const fl
   if ((long)rows * lion_cdiv(lion_cdiv(L, 4), 256) > 0x7fffffffL) return LION_EUNSUPPORTED;
   const unsigned grid = (unsigned)(rows * lion_cdiv(lion_cdiv(L, 4), 256));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (seed) affine_act_bwd_apply_kernel<true><<<grid, 256, 0, st>>>(x, gy, A, Bs, Q, R, L, act, dx, seed, thr, scale);
-  else affine_act_bwd_apply_kernel<false><<<grid, 256, 0, st>>>(x, gy, A, Bs, Q, R, L, act, dx, nullptr, 0u, 1.f);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(seed != nullptr, [&](auto DROP) {
+    return lion_launch<affine_act_bwd_apply_kernel<decltype(DROP)::value>>(grid, 256, 0, st, x, gy, A, Bs, Q, R, L, act, dx,
+                                                                           seed, thr, scale);
+  });
 }
 
 int lion_affine_act(const float *x, const float *A, const float *Bs, int rows, int L, int act, float *y,
@@ -635,22 +640,15 @@ int lion_affine_act_dropout_bwd_apply(const float *x, const float *gy, const flo
 }
 
 // U in {8, 16, 32, 64}; x f32[rows, M, U] 16-byte aligned
-#define LION_AAM_DISPATCH(KERNEL, GRID, ...)                                                       \
-  switch (U) {                                                                                     \
-  case 8:  KERNEL<2><<<GRID, 256, 0, st>>>(__VA_ARGS__); break;                                    \
-  case 16: KERNEL<4><<<GRID, 256, 0, st>>>(__VA_ARGS__); break;                                    \
-  case 32: KERNEL<8><<<GRID, 256, 0, st>>>(__VA_ARGS__); break;                                    \
-  case 64: KERNEL<16><<<GRID, 256, 0, st>>>(__VA_ARGS__); break;                                   \
-  default: return LION_EUNSUPPORTED;                                                               \
-  }
 int lion_affine_act_max(const float *x, const float *A, const float *Bs, int rows, int M, int U, int act, float *y,
                         lionStream_t stream) {
   if (!x || !A || !Bs || !y || rows <= 0 || M <= 0 || (act != 0 && act != 1)) return LION_EINVAL;
   if ((((uintptr_t)x) & 15) != 0 || rows > 65535) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  LION_AAM_DISPATCH(affine_act_max_kernel, dim3(lion_cdiv(M, 256), rows), x, A, Bs, M, act, y)
-  LION_LAUNCH_CHECK();
-  return 0;
+  return aam_dispatch(U, [&](auto Q4) {
+    return lion_launch<affine_act_max_kernel<decltype(Q4)::value>>(dim3(lion_cdiv(M, 256), rows), 256, 0, st, x, A, Bs, M, act,
+                                                                   y);
+  });
 }
 
 int lion_affine_act_max_bwd_stats(const float *x, const float *gy, const float *A, const float *Bs, int rows, int M, int U,
@@ -658,9 +656,9 @@ int lion_affine_act_max_bwd_stats(const float *x, const float *gy, const float *
   if (!x || !gy || !A || !Bs || !S || rows <= 0 || M <= 0 || (act != 0 && act != 1)) return LION_EINVAL;
   if ((((uintptr_t)x) & 15) != 0) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  LION_AAM_DISPATCH(affine_act_max_bwd_stats_kernel, rows, x, gy, A, Bs, M, act, S)
-  LION_LAUNCH_CHECK();
-  return 0;
+  return aam_dispatch(U, [&](auto Q4) {
+    return lion_launch<affine_act_max_bwd_stats_kernel<decltype(Q4)::value>>(rows, 256, 0, st, x, gy, A, Bs, M, act, S);
+  });
 }
 
 int lion_affine_act_max_bwd_apply(const float *x, const float *gy, const float *A, const float *Bs, const float *Q,
@@ -668,35 +666,32 @@ int lion_affine_act_max_bwd_apply(const float *x, const float *gy, const float *
   if (!x || !gy || !A || !Bs || !Q || !R || !dx || rows <= 0 || M <= 0 || (act != 0 && act != 1)) return LION_EINVAL;
   if (((((uintptr_t)x) | ((uintptr_t)dx)) & 15) != 0 || rows > 65535) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  LION_AAM_DISPATCH(affine_act_max_bwd_apply_kernel, dim3(lion_cdiv(M, 256), rows), x, gy, A, Bs, Q, R, M, act, dx)
-  LION_LAUNCH_CHECK();
-  return 0;
+  return aam_dispatch(U, [&](auto Q4) {
+    return lion_launch<affine_act_max_bwd_apply_kernel<decltype(Q4)::value>>(dim3(lion_cdiv(M, 256), rows), 256, 0, st, x, gy,
+                                                                             A, Bs, Q, R, M, act, dx);
+  });
 }
-#undef LION_AAM_DISPATCH
 
 int lion_gn_train_param_grads(const float *pw, int B, int C, float *dgw, float *dgb, float *dxs, lionStream_t stream) {
   if (!pw || !dgw || !dgb || B <= 0 || C <= 0) return LION_EINVAL;
-  pw_batch_sum_kernel<<<lion_cdiv(C, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(pw, B, C, dgw, dgb, dxs);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<pw_batch_sum_kernel>(lion_cdiv(C, 256), 256, 0, static_cast<hipStream_t>(stream), pw, B, C, dgw,
+                                          dgb, dxs);
 }
 
 int lion_rows_dot2(const float *g, const float *v, const float *ws, int B, int C, int N, float *S, lionStream_t stream) {
   if (!g || !v || !ws || !S || B <= 0 || C <= 0 || N <= 0) return LION_EINVAL;
   const int rows = B * C;
-  rows_dot2_kernel<<<lion_cdiv(rows, 4), 256, 0, static_cast<hipStream_t>(stream)>>>(g, v, ws, rows, C, N, S);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<rows_dot2_kernel>(lion_cdiv(rows, 4), 256, 0, static_cast<hipStream_t>(stream), g, v, ws, rows, C,
+                                       N, S);
 }
 
 int lion_se_gate_fwd(const float *stats, const float *w1, const float *w2, int B, int C, int Cr, int L, float *mean, float *h,
                      float *g, float *zero, lionStream_t stream) {
   if (!stats || !w1 || !w2 || !mean || !h || !g || !zero || B <= 0 || C <= 0 || Cr <= 0 || L <= 0) return LION_EINVAL;
   if (C > 1024 || Cr > 128) return LION_EUNSUPPORTED;
-  se_gate_fwd_kernel<false><<<B, 256, 0, static_cast<hipStream_t>(stream)>>>(stats, w1, w2, C, Cr, (float)L, mean, h, g, zero,
-                                                                             nullptr, nullptr, nullptr, nullptr, nullptr);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<se_gate_fwd_kernel<false>>(B, 256, 0, static_cast<hipStream_t>(stream), stats, w1, w2, C, Cr,
+                                                (float)L, mean, h, g, zero, nullptr, nullptr, nullptr, nullptr,
+                                                nullptr);
 }
 // the gate directly behind an AdaGN without activation (see se_gate_fwd_kernel<true>): xstats f64[B*C,2] (lion_row_stats64 of x),
 // A / Bs f32[B,C] of the AdaGN fold -> mean (of u = A x + Bs), h, g, and A2 = g A, B2 = g Bs for ONE lion_affine_act pass over x
@@ -704,10 +699,8 @@ int lion_gn_se_gate_fwd(const double *xstats, const float *A, const float *Bs, c
                         int L, float *mean, float *h, float *g, float *A2, float *B2, lionStream_t stream) {
   if (!xstats || !A || !Bs || !w1 || !w2 || !mean || !h || !g || !A2 || !B2 || B <= 0 || C <= 0 || Cr <= 0 || L <= 0) return LION_EINVAL;
   if (C > 1024 || Cr > 128) return LION_EUNSUPPORTED;
-  se_gate_fwd_kernel<true><<<B, 256, 0, static_cast<hipStream_t>(stream)>>>(nullptr, w1, w2, C, Cr, (float)L, mean, h, g, nullptr,
-                                                                            xstats, A, Bs, A2, B2);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<se_gate_fwd_kernel<true>>(B, 256, 0, static_cast<hipStream_t>(stream), nullptr, w1, w2, C, Cr,
+                                               (float)L, mean, h, g, nullptr, xstats, A, Bs, A2, B2);
 }
 
 int lion_se_gate_bwd(const float *S, const float *g, const float *h, const float *mean, const float *w1, const float *w2, int B,
@@ -716,11 +709,11 @@ int lion_se_gate_bwd(const float *S, const float *g, const float *h, const float
     return LION_EINVAL;
   if (C > 1024 || Cr > 128) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  se_gate_bwd_kernel<false><<<B, 256, 0, st>>>(S, g, h, w1, w2, C, Cr, (float)L, dpre2, dpre1, Q, nullptr, nullptr, nullptr, nullptr);
-  LION_LAUNCH_CHECK();
-  se_gate_wgrad_kernel<<<dim3(lion_cdiv(C * Cr, 256), 2), 256, 0, st>>>(dpre2, dpre1, h, mean, B, C, Cr, dw1, dw2);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<se_gate_bwd_kernel<false>>(B, 256, 0, st, S, g, h, w1, w2, C, Cr, (float)L, dpre2, dpre1, Q,
+                                                     nullptr, nullptr, nullptr, nullptr))
+    return e;
+  return lion_launch<se_gate_wgrad_kernel>(dim3(lion_cdiv(C * Cr, 256), 2), 256, 0, st, dpre2, dpre1, h, mean, B, C, Cr,
+                                           dw1, dw2);
 }
 // backward of the same pair: S f32[B*C,2] = {sum gy, sum gy x} (lion_affine_act_bwd_stats with act = 0) -> Qse (the gate's
 // contribution to du, per row), Sp f32[B*C,2] = the row sums {sum du, sum du x} lion_gn_train_bwd_fold needs, dw1 / dw2
@@ -732,11 +725,11 @@ int lion_gn_se_gate_bwd(const float *S, const double *xstats, const float *A, co
     return LION_EINVAL;
   if (C > 1024 || Cr > 128) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  se_gate_bwd_kernel<true><<<B, 256, 0, st>>>(S, g, h, w1, w2, C, Cr, (float)L, dpre2, dpre1, Qse, xstats, A, Bs, Sp);
-  LION_LAUNCH_CHECK();
-  se_gate_wgrad_kernel<<<dim3(lion_cdiv(C * Cr, 256), 2), 256, 0, st>>>(dpre2, dpre1, h, mean, B, C, Cr, dw1, dw2);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<se_gate_bwd_kernel<true>>(B, 256, 0, st, S, g, h, w1, w2, C, Cr, (float)L, dpre2, dpre1, Qse,
+                                                    xstats, A, Bs, Sp))
+    return e;
+  return lion_launch<se_gate_wgrad_kernel>(dim3(lion_cdiv(C * Cr, 256), 2), 256, 0, st, dpre2, dpre1, h, mean, B, C, Cr,
+                                           dw1, dw2);
 }
 
 } // extern "C"

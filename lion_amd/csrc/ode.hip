@@ -277,9 +277,8 @@ int lion_ode_stage(double *Y, const double *K, size_t n, lion_ode_ctrl *ctrl, fl
                    lionStream_t stream) {
   if (!Y || !K || !ctrl || !x32 || !t_model || n == 0 || B <= 0) return LION_EINVAL;
   const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
-  stage_kernel<<<blocks, kThreads, 0, static_cast<hipStream_t>(stream)>>>(Y, K, n, ctrl, x32, t_model, B);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<stage_kernel>(blocks, kThreads, 0, static_cast<hipStream_t>(stream), Y, K, n, ctrl, x32, t_model,
+                                   B);
 }
 
 int lion_ode_drift(const float *eps, int cm_points, const float *x32, size_t n, const float *t_model, float beta_start,
@@ -291,26 +290,21 @@ int lion_ode_drift(const float *eps, int cm_points, const float *x32, size_t n, 
   if ((mix_a == nullptr) != (mix_b == nullptr) || (mix_a && (mix_len <= 0 || n % (size_t)mix_len != 0)))
     return LION_EINVAL;
   const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
-  drift_kernel<<<blocks, kThreads, 0, static_cast<hipStream_t>(stream)>>>(
-      eps, cm_points, x32, n, t_model, beta_start, beta_delta, neg_beta_start, half_beta_delta, one_minus_sigma2_0, mix_a,
-      mix_b, mix_len, K, ctrl);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<drift_kernel>(blocks, kThreads, 0, static_cast<hipStream_t>(stream), eps, cm_points, x32, n,
+                                   t_model, beta_start, beta_delta, neg_beta_start, half_beta_delta, one_minus_sigma2_0,
+                                   mix_a, mix_b, mix_len, K, ctrl);
 }
 
 int lion_ode_error_partials(const double *Y, const double *K, size_t n, const lion_ode_ctrl *ctrl, double *partials,
                             lionStream_t stream) {
   if (!Y || !K || !ctrl || !partials || n == 0) return LION_EINVAL;
-  partials_kernel<<<partial_blocks(n), kThreads, 0, static_cast<hipStream_t>(stream)>>>(Y, K, n, ctrl, partials);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<partials_kernel>(partial_blocks(n), kThreads, 0, static_cast<hipStream_t>(stream), Y, K, n, ctrl,
+                                      partials);
 }
 
 int lion_ode_control(const double *partials, size_t n, lion_ode_ctrl *ctrl, lionStream_t stream) {
   if (!partials || !ctrl || n == 0) return LION_EINVAL;
-  control_kernel<<<1, kThreads, 0, static_cast<hipStream_t>(stream)>>>(partials, n, ctrl);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<control_kernel>(1, kThreads, 0, static_cast<hipStream_t>(stream), partials, n, ctrl);
 }
 
 } // extern "C"

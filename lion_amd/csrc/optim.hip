@@ -176,13 +176,11 @@ int lion_adam_step_scaled(const uint64_t *table, const int32_t *numel, const int
   if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weight_decay >= 0.f)) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned long long *tb = reinterpret_cast<const unsigned long long *>(table);
-  adam_tick_kernel<<<lion_cdiv(tensors, 256), 256, 0, st>>>(tb, tensors);
-  if (grad_scale)
-    adam_multi_kernel<true><<<blocks, 256, 0, st>>>(tb, numel, blockmap, lr, beta1, beta2, eps, weight_decay, ema_decay, grad_scale);
-  else
-    adam_multi_kernel<false><<<blocks, 256, 0, st>>>(tb, numel, blockmap, lr, beta1, beta2, eps, weight_decay, ema_decay, nullptr);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<adam_tick_kernel>(lion_cdiv(tensors, 256), 256, 0, st, tb, tensors)) return e;
+  return lion_with_flags(grad_scale != nullptr, [&](auto SCALED) {
+    return lion_launch<adam_multi_kernel<decltype(SCALED)::value>>(blocks, 256, 0, st, tb, numel, blockmap, lr, beta1, beta2,
+                                                                   eps, weight_decay, ema_decay, grad_scale);
+  });
 }
 
 int lion_adam_step(const uint64_t *table, const int32_t *numel, const int32_t *blockmap, int blocks, int tensors, const float *lr,
@@ -194,17 +192,15 @@ int lion_adam_step(const uint64_t *table, const int32_t *numel, const int32_t *b
 int lion_grad_sqnorm_partials(const uint64_t *table, const int32_t *numel, const int32_t *blockmap, int blocks, float *partials,
                               lionStream_t stream) {
   if (!table || !numel || !blockmap || !partials || blocks <= 0) return LION_EINVAL;
-  grad_sqnorm_kernel<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(reinterpret_cast<const unsigned long long *>(table), numel,
-                                                                           blockmap, partials);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<grad_sqnorm_kernel>(blocks, 256, 0, static_cast<hipStream_t>(stream),
+                                         reinterpret_cast<const unsigned long long *>(table), numel, blockmap,
+                                         partials);
 }
 
 int lion_grad_clip_coef(const float *partials, int n, float max_norm, float *out2, lionStream_t stream) {
   if (!partials || !out2 || n <= 0 || !(max_norm > 0.f)) return LION_EINVAL;
-  grad_clip_coef_kernel<<<1, CLIP_THREADS, 0, static_cast<hipStream_t>(stream)>>>(partials, n, max_norm, out2);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<grad_clip_coef_kernel>(1, CLIP_THREADS, 0, static_cast<hipStream_t>(stream), partials, n, max_norm,
+                                            out2);
 }
 
 } // extern "C"

@@ -227,9 +227,7 @@ extern "C" {
 // x f32[rows, L] (rows = B*C) -> stats f32[rows, 2] (== the [B,C,T=1,2] layout of lion_groupnorm_fold)
 int lion_row_stats(const float *x, int rows, int L, float *stats, lionStream_t stream) {
   if (!x || !stats || rows <= 0 || L <= 0) return LION_EINVAL;
-  row_stats_kernel<<<rows, 256, 0, static_cast<hipStream_t>(stream)>>>(x, L, stats);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<row_stats_kernel>(rows, 256, 0, static_cast<hipStream_t>(stream), x, L, stats);
 }
 
 int lion_affine_swish(const float *x, const float *A, const float *Bs, int rows, int L, float *y,
@@ -238,9 +236,10 @@ int lion_affine_swish(const float *x, const float *A, const float *Bs, int rows,
   for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
     const int nr = rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY;
     const size_t off = (size_t)r0 * L;
-    affine_swish_kernel<<<dim3(lion_cdiv(lion_cdiv(L, 4), 256), nr), 256, 0, static_cast<hipStream_t>(stream)>>>(
-        x + off, A + r0, Bs + r0, L, y + off);
-    LION_LAUNCH_CHECK();
+    if (int e = lion_launch<affine_swish_kernel>(dim3(lion_cdiv(lion_cdiv(L, 4), 256), nr), 256, 0,
+                                                 static_cast<hipStream_t>(stream), x + off, A + r0, Bs + r0, L,
+                                                 y + off))
+      return e;
   }
   return 0;
 }
@@ -248,9 +247,8 @@ int lion_affine_swish(const float *x, const float *A, const float *Bs, int rows,
 int lion_timestep_embedding(const float *t, const float *row, float scale, int B, int half, int D, float *emb,
                             lionStream_t stream) {
   if (!t || !row || !emb || B <= 0 || half <= 0 || D < 2 * half) return LION_EINVAL;
-  timestep_embedding_kernel<<<lion_cdiv(B * D, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(t, row, scale, B, half, D, emb);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<timestep_embedding_kernel>(lion_cdiv(B * D, 256), 256, 0, static_cast<hipStream_t>(stream), t, row,
+                                                scale, B, half, D, emb);
 }
 
 int lion_affine_swish_add(const float *x, const float *A, const float *Bs, const float *addend, int rows, int L, float *y,
@@ -259,9 +257,10 @@ int lion_affine_swish_add(const float *x, const float *A, const float *Bs, const
   for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
     const int nr = rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY;
     const size_t off = (size_t)r0 * L;
-    affine_swish_add_kernel<<<dim3(lion_cdiv(lion_cdiv(L, 4), 256), nr), 256, 0, static_cast<hipStream_t>(stream)>>>(
-        x + off, A + r0, Bs + r0, addend + off, L, y + off);
-    LION_LAUNCH_CHECK();
+    if (int e = lion_launch<affine_swish_add_kernel>(dim3(lion_cdiv(lion_cdiv(L, 4), 256), nr), 256, 0,
+                                                     static_cast<hipStream_t>(stream), x + off, A + r0, Bs + r0,
+                                                     addend + off, L, y + off))
+      return e;
   }
   return 0;
 }
@@ -271,19 +270,22 @@ int lion_affine_swish_max(const float *x, const float *A, const float *Bs, int r
   if (!x || !A || !Bs || !y || rows <= 0 || M <= 0 || U <= 0) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool al = (((uintptr_t)x) & 15) == 0; // a chunk starts 65535 * M * U floats on: 16-byte aligned when U % 4 == 0
-#define LION_ASM_COOP(LPM_)                                                                                  \
-  affine_swish_max_coop_kernel<LPM_><<<dim3(lion_cdiv(M, 4 * (64 / LPM_) * 8), nr), 256, 0, st>>>(xc, A + r0, Bs + r0, M, yc)
   for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
     const int nr = rows - r0 < kMaxGridY ? rows - r0 : kMaxGridY;
     const float *xc = x + (size_t)r0 * M * U;
     float *yc = y + (size_t)r0 * M;
-    if (al && U == 32) LION_ASM_COOP(8);
-    else if (al && U == 16) LION_ASM_COOP(4);
-    else if (al && U == 64) LION_ASM_COOP(16);
-    else affine_swish_max_kernel<<<dim3(lion_cdiv(M, 256), nr), 256, 0, st>>>(xc, A + r0, Bs + r0, M, U, yc);
-    LION_LAUNCH_CHECK();
+    auto coop = [&](auto LPM) { // LPM = U / 4 lanes share a row's maximum
+      constexpr int lpm = decltype(LPM)::value;
+      return lion_launch<affine_swish_max_coop_kernel<lpm>>(dim3(lion_cdiv(M, 4 * (64 / lpm) * 8), nr), 256, 0, st, xc, A + r0,
+                                                            Bs + r0, M, yc);
+    };
+    const int e = al && U == 32   ? coop(IntC<8>{})
+                  : al && U == 16 ? coop(IntC<4>{})
+                  : al && U == 64 ? coop(IntC<16>{})
+                                  : lion_launch<affine_swish_max_kernel>(dim3(lion_cdiv(M, 256), nr), 256, 0, st, xc, A + r0,
+                                                                         Bs + r0, M, U, yc);
+    if (e) return e;
   }
-#undef LION_ASM_COOP
   return 0;
 }
 
@@ -292,17 +294,14 @@ int lion_se_gate(const float *chmean, const float *w1, const float *w2, int B, i
                  float *Bs, lionStream_t stream) {
   if (!chmean || !w1 || !w2 || !A || !Bs || B <= 0 || C <= 0 || H <= 0) return LION_EINVAL;
   if (C > 1024 || H > 128) return LION_EUNSUPPORTED;
-  se_gate_kernel<<<B, 256, 0, static_cast<hipStream_t>(stream)>>>(chmean, w1, w2, C, H, A, Bs);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<se_gate_kernel>(B, 256, 0, static_cast<hipStream_t>(stream), chmean, w1, w2, C, H, A, Bs);
 }
 
 int lion_latent_unpack(const float *x, int B, int N, int D, float *all, float *coords, float *rest, lionStream_t stream) {
   if (!x || B <= 0 || N <= 0 || D < 3 || D > 8 || (!all && !coords && !rest)) return LION_EINVAL;
   if (rest && D == 3) return LION_EINVAL;
-  latent_unpack_kernel<<<dim3(lion_cdiv(N, 256), B), 256, 0, static_cast<hipStream_t>(stream)>>>(x, N, D, all, coords, rest);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<latent_unpack_kernel>(dim3(lion_cdiv(N, 256), B), 256, 0, static_cast<hipStream_t>(stream), x, N,
+                                           D, all, coords, rest);
 }
 
 int lion_concat_broadcast(const float *a, const float *t, int B, int Ca, int Ct, int N, int ld_t, float *out,
@@ -311,10 +310,9 @@ int lion_concat_broadcast(const float *a, const float *t, int B, int Ca, int Ct,
   if (N % 4 != 0 || ((((uintptr_t)a) | ((uintptr_t)out)) & 15) != 0) return LION_EUNSUPPORTED;
   if ((long)B * (Ca + Ct) > 65535) return LION_EUNSUPPORTED;   // one grid row per (sample, channel)
   const int N4 = N / 4;
-  concat_broadcast_kernel<<<dim3(lion_cdiv(N4, 256) > 4 ? 4 : lion_cdiv(N4, 256), B * (Ca + Ct)), 256, 0,
-                            static_cast<hipStream_t>(stream)>>>(a, t, Ca, Ct, N4, ld_t, reinterpret_cast<float4 *>(out));
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<concat_broadcast_kernel>(dim3(lion_cdiv(N4, 256) > 4 ? 4 : lion_cdiv(N4, 256), B * (Ca + Ct)), 256,
+                                              0, static_cast<hipStream_t>(stream), a, t, Ca, Ct, N4, ld_t,
+                                              reinterpret_cast<float4 *>(out));
 }
 
 } // extern "C"

@@ -377,24 +377,12 @@ static int launch_pw(const float *x, const float *wp, const float *bias, float *
   // weights through LDS only when a workgroup's column tile is one of many (the staging is then amortised by the L2)
   const bool wlds = (long)grid.x * B >= 2048;
   const size_t lds = pw_lds(CB, Cin, pa != nullptr, wlds);
-#define LION_PW_GO(PRO_, ST_)                                                                              \
-  {                                                                                                        \
-    static LionLdsLimit cfg = {}, cfg_g = {};                                                              \
-    if (wlds) {                                                                                            \
-      if (int e = lion_dynamic_lds(&pwconv_kernel<CB, VB, PRO_, ST_, true>, lds, cfg)) return e;           \
-      pwconv_kernel<CB, VB, PRO_, ST_, true><<<grid, 256, lds, st>>>(x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pa, pb, stats); \
-    } else {                                                                                               \
-      if (int e = lion_dynamic_lds(&pwconv_kernel<CB, VB, PRO_, ST_, false>, lds, cfg_g)) return e;        \
-      pwconv_kernel<CB, VB, PRO_, ST_, false><<<grid, 256, lds, st>>>(x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pa, pb, stats); \
-    }                                                                                                      \
-  }
-  if (pa && stats) LION_PW_GO(true, true)
-  else if (pa) LION_PW_GO(true, false)
-  else if (stats) LION_PW_GO(false, true)
-  else LION_PW_GO(false, false)
-#undef LION_PW_GO
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
+    return lion_with_flags(wlds, [&](auto WLDS) {
+      return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, decltype(WLDS)::value>>(
+          grid, 256, lds, st, x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, nullptr, nullptr);
+    });
+  });
 }
 
 // the two passes of the "activated maximum without the layer's output" form (OUT = 1, OUT = 2): large activations only
@@ -406,20 +394,12 @@ static int launch_pw_max(const float *x, const float *wp, const float *bias, flo
   const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
   if ((long)grid.x * B < 2048) return LION_EUNSUPPORTED;
   const size_t lds = pw_lds(CB, Cin, pa != nullptr, true);
-#define LION_PWM_GO(PRO_, ST_, OUT_)                                                                      \
-  {                                                                                                        \
-    static LionLdsLimit cfg = {};                                                                          \
-    if (int e = lion_dynamic_lds(&pwconv_kernel<CB, VB, PRO_, ST_, true, OUT_>, lds, cfg)) return e;       \
-    pwconv_kernel<CB, VB, PRO_, ST_, true, OUT_><<<grid, 256, lds, st>>>(x, wp, bias, ymax, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, oa, ob); \
-  }
-  if (oa) {
-    if (pa) LION_PWM_GO(true, false, 2) else LION_PWM_GO(false, false, 2)
-  } else {
-    if (pa) LION_PWM_GO(true, true, 1) else LION_PWM_GO(false, true, 1)
-  }
-#undef LION_PWM_GO
-  LION_LAUNCH_CHECK();
-  return 0;
+  // first pass (no out_a): OUT = 1 with the statistics; second pass: OUT = 2 without them
+  return lion_with_flags(pa != nullptr, oa != nullptr, [&](auto PRO, auto SECOND) {
+    constexpr bool second = decltype(SECOND)::value;
+    return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, !second, true, second ? 2 : 1>>(
+        grid, 256, lds, st, x, wp, bias, ymax, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, oa, ob);
+  });
 }
 
 } // namespace
@@ -454,10 +434,8 @@ size_t lion_pwconv_packed_floats(int Cout, int Cin) { return (size_t)((Cin + 1) 
 int lion_pwconv_pack_weights(const float *w, int Cout, int Cin, float *wp, lionStream_t stream) {
   if (!w || !wp || Cout <= 0 || Cin <= 0) return LION_EINVAL;
   const int Cin_pad = (Cin + 1) / 2 * 2, Cout_pad = pw_stride(Cout);
-  pwconv_pack_kernel<<<lion_cdiv(Cin_pad * Cout_pad, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(w, Cout, Cout_pad, Cin,
-                                                                                                       Cin_pad, wp);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<pwconv_pack_kernel>(lion_cdiv(Cin_pad * Cout_pad, 256), 256, 0, static_cast<hipStream_t>(stream),
+                                         w, Cout, Cout_pad, Cin, Cin_pad, wp);
 }
 
 // column tiles per batch element = rows of the stats tensor per channel (0: shape not supported)
@@ -481,12 +459,10 @@ int lion_pwconv_forward(const float *x, const float *wp, const float *bias, int 
     const dim3 grid(lion_cdiv(L, 32), pw_stride(Cout) / 64, B);
     const size_t lds = pro_a ? (size_t)2 * Cin * 4 : 0;
     if (lds > 64 * 1024) return LION_EUNSUPPORTED;
-    if (pro_a && stats) pwconv_small_kernel<true, true><<<grid, 256, lds, st>>>(x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pro_a, pro_b, stats);
-    else if (pro_a) pwconv_small_kernel<true, false><<<grid, 256, lds, st>>>(x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pro_a, pro_b, stats);
-    else if (stats) pwconv_small_kernel<false, true><<<grid, 256, lds, st>>>(x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pro_a, pro_b, stats);
-    else pwconv_small_kernel<false, false><<<grid, 256, lds, st>>>(x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pro_a, pro_b, stats);
-    LION_LAUNCH_CHECK();
-    return 0;
+    return lion_with_flags(pro_a != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
+      return lion_launch<pwconv_small_kernel<decltype(PRO)::value, decltype(ST)::value>>(
+          grid, 256, lds, st, x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pro_a, pro_b, stats);
+    });
   }
   const PwPlan p = pw_plan(Cout, Cin);
   if (!p.cb) return LION_EUNSUPPORTED;
@@ -504,10 +480,8 @@ int lion_linear_forward(const float *x, const float *wp, const float *bias, int 
                         float *y, lionStream_t stream) {
   if (!x || !wp || !y || B <= 0 || K <= 0 || O <= 0 || act < 0 || act > 2) return LION_EINVAL;
   const int Opad = pw_stride(O);
-  linear_rows_kernel<<<dim3(pw_pad(O) / 32, lion_cdiv(B, 32)), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      x, wp, bias, B, K, O, Opad, act, slope, y);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<linear_rows_kernel>(dim3(pw_pad(O) / 32, lion_cdiv(B, 32)), 256, 0,
+                                         static_cast<hipStream_t>(stream), x, wp, bias, B, K, O, Opad, act, slope, y);
 }
 
 } // extern "C"

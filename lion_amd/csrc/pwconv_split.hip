@@ -417,19 +417,10 @@ static int launch_pws(const float *x, const u4 *wp, const float *wtail, const fl
   const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
   const size_t ring = (size_t)NR * (4 * CB * 32 * 16 + (WIDE ? KS * 128 * VB * 4 : 0)), tile = (size_t)4 * 32 * 36 * 4; // weight ring, reused by the statistics
   const size_t lds = (ring > tile ? ring : tile) + (size_t)((pa ? 2 * nchunks * KS : 0) + CB * 32 + 8 * CB * 32 * 2) * 4;
-#define LION_PWS_GO(PRO_, ST_)                                                                             \
-  {                                                                                                        \
-    static LionLdsLimit cfg = {};                                                                          \
-    if (int e = lion_dynamic_lds(&pwconv_split_kernel<CB, VB, PRO_, ST_, NR, WIDE>, lds, cfg)) return e;             \
-    pwconv_split_kernel<CB, VB, PRO_, ST_, NR, WIDE><<<grid, 256, lds, st>>>(x, wp, wtail, bias, y, Cin, Cpad, Cout, L, pa, pb, stats); \
-  }
-  if (pa && stats) LION_PWS_GO(true, true)
-  else if (pa) LION_PWS_GO(true, false)
-  else if (stats) LION_PWS_GO(false, true)
-  else LION_PWS_GO(false, false)
-#undef LION_PWS_GO
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
+    return lion_launch<pwconv_split_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, NR, WIDE>>(
+        grid, 256, lds, st, x, wp, wtail, bias, y, Cin, Cpad, Cout, L, pa, pb, stats);
+  });
 }
 
 } // namespace
@@ -452,10 +443,9 @@ int lion_pwconv_split_pack_weights(const float *w, int Cout, int Cin, uint16_t *
   unsigned *tail = reinterpret_cast<unsigned *>(wp + pws_halfs(Cout, Cin));
   const int n = Cout * Cin, nchunks = (Cin + KS - 1) / KS, Cpad = pws_pad(Cout);
   if (hipMemsetAsync(tail, 0, 16, st) != hipSuccess) return LION_EINVAL;
-  split_wmax_kernel<<<min(lion_cdiv(n, 2048), 128), 256, 0, st>>>(w, n, tail);
-  pw_split_pack_kernel<false><<<lion_cdiv(nchunks * KS * Cpad, 256), 256, 0, st>>>(w, Cout, Cpad, Cin, nchunks, wp, tail, nullptr);
-  LION_LAUNCH_CHECK();
-  return 0;
+  if (int e = lion_launch<split_wmax_kernel>(min(lion_cdiv(n, 2048), 128), 256, 0, st, w, n, tail)) return e;
+  return lion_launch<pw_split_pack_kernel<false>>(lion_cdiv(nchunks * KS * Cpad, 256), 256, 0, st, w, Cout, Cpad, Cin,
+                                                  nchunks, wp, tail, nullptr);
 }
 
 // The packed form of W^T f32[Cin][Cout] (what the data gradient multiplies by) from W f32[Cout][Cin] as stored and W's own
@@ -468,9 +458,8 @@ int lion_pwconv_split_pack_weights_t(const float *w, int Cout, int Cin, const ui
   unsigned *tail = reinterpret_cast<unsigned *>(wpt + pws_halfs(Cin, Cout));
   // the transposed matrix has Cin rows ("output channels") and Cout columns
   const int nchunks = (Cout + KS - 1) / KS, Cpad = pws_pad(Cin);
-  pw_split_pack_kernel<true><<<lion_cdiv(nchunks * KS * Cpad, 256), 256, 0, st>>>(w, Cin, Cpad, Cout, nchunks, wpt, tail, tail_src);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<pw_split_pack_kernel<true>>(lion_cdiv(nchunks * KS * Cpad, 256), 256, 0, st, w, Cin, Cpad, Cout,
+                                                 nchunks, wpt, tail, tail_src);
 }
 
 // column tiles per batch element = rows of the stats tensor per channel

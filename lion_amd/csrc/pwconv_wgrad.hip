@@ -173,12 +173,12 @@ int lion_pwconv_wgrad(const float *x, const float *gy, int B, int Cin, int Cout,
   hipStream_t st = static_cast<hipStream_t>(stream);
   float *part = static_cast<float *>(ws);
   float *bpart = gb ? part + (size_t)p.slices * Cout * Cin : nullptr;
-  pwconv_wgrad_kernel<<<dim3(p.slices, lion_cdiv(Cout, PWG_T), lion_cdiv(Cin, PWG_T)), 256, 0, st>>>(
-      x, gy, Cin, Cout, L, p.LK, p.spb, part, bpart);
+  if (int e = lion_launch<pwconv_wgrad_kernel>(dim3(p.slices, lion_cdiv(Cout, PWG_T), lion_cdiv(Cin, PWG_T)), 256, 0,
+                                               st, x, gy, Cin, Cout, L, p.LK, p.spb, part, bpart))
+    return e;
   const int n = Cout * Cin, nb = gb ? Cout : 0;
-  pwconv_wgrad_reduce_kernel<<<lion_cdiv(n + nb, 16), 256, 0, st>>>(part, n, p.slices, gw, bpart, nb, gb);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<pwconv_wgrad_reduce_kernel>(lion_cdiv(n + nb, 16), 256, 0, st, part, n, p.slices, gw, bpart, nb,
+                                                 gb);
 }
 
 } // extern "C"

@@ -167,11 +167,7 @@ static int launch_fps_reg(const float *coords, int B, int N, int M, int32_t *idx
   // The library is compiled with -fno-slp-vectorize (csrc/build.sh, tests/test_isa_cpu.py), the kernel asks for the
   // N * 16 bytes it uses, and it shares its CUs again (tests/test_concurrency_gpu.py replays it beside the convolution).
   const size_t lds = (size_t)N * 16;
-  static LionLdsLimit configured = {};
-  if (int e = lion_dynamic_lds(&fps_reg_kernel<PPT, NW>, lds, configured)) return e;
-  fps_reg_kernel<PPT, NW><<<B, 64 * NW, lds, st>>>(coords, N, M, idx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<fps_reg_kernel<PPT, NW>>(B, 64 * NW, lds, st, coords, N, M, idx);
 }
 
 } // namespace
@@ -189,11 +185,7 @@ extern "C" int lion_furthest_point_sampling(const float *coords, int B, int N, i
   if (N <= 4096) return launch_fps_reg<16, 4>(coords, B, N, M, idx, st);
   if (N <= 32768) {
     const size_t lds = (size_t)N * 4;
-    static LionLdsLimit configured = {};
-    if (int e = lion_dynamic_lds(&fps_lds_kernel, lds, configured)) return e;
-    fps_lds_kernel<<<B, 1024, lds, st>>>(coords, N, M, idx);
-    LION_LAUNCH_CHECK();
-    return 0;
+    return lion_launch<fps_lds_kernel>(B, 1024, lds, st, coords, N, M, idx);
   }
   return LION_EUNSUPPORTED;
 }

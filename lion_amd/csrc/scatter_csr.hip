@@ -215,7 +215,9 @@ int lion_scatter_csr(const float *gy, const int32_t *idx, const float *w, int B,
   if ((size_t)span * 4 > 60 * 1024) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   int32_t *start = static_cast<int32_t *>(ws), *count = start + (size_t)B * bins, *perm = count + (size_t)B * bins;
-  csr_build_kernel<<<dim3(CSR_P, B), CSR_NT, (size_t)span * 4, st>>>(idx, E, bins, span, start, count, perm);
+  if (int e = lion_launch<csr_build_kernel>(dim3(CSR_P, B), CSR_NT, (size_t)span * 4, st, idx, E, bins, span, start, count,
+                                            perm))
+    return e;
   // channels per workgroup: as many gy rows as fit 128 KiB of LDS, fewer while that leaves CUs without a workgroup
   int CT = (int)((128 * 1024) / ((size_t)S * 4));
   if (CT < 1) return LION_EUNSUPPORTED;
@@ -224,17 +226,10 @@ int lion_scatter_csr(const float *gy, const int32_t *idx, const float *w, int B,
   while (CT > 1 && (long)B * lion_cdiv(C, CT) < 256) CT >>= 1;
   const size_t lds = (size_t)CT * S * 4;
   const dim3 grid(lion_cdiv(C, CT), B);
-  if (w) {
-    static LionLdsLimit cfg = {};
-    if (int e = lion_dynamic_lds(&csr_apply_kernel<true>, lds, cfg)) return e;
-    csr_apply_kernel<true><<<grid, 1024, lds, st>>>(gy, w, start, count, perm, C, S, E, bins, span, CT, gx);
-  } else {
-    static LionLdsLimit cfg = {};
-    if (int e = lion_dynamic_lds(&csr_apply_kernel<false>, lds, cfg)) return e;
-    csr_apply_kernel<false><<<grid, 1024, lds, st>>>(gy, w, start, count, perm, C, S, E, bins, span, CT, gx);
-  }
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(w != nullptr, [&](auto W) {
+    return lion_launch<csr_apply_kernel<decltype(W)::value>>(grid, 1024, lds, st, gy, w, start, count, perm, C, S, E, bins,
+                                                             span, CT, gx);
+  });
 }
 
 } // extern "C"

@@ -209,9 +209,8 @@ int lion_skinny_pack_weights(const float *w, int Cout, int Cin, float *wp, lionS
   if (!w || !wp || Cout <= 0 || Cin <= 0) return LION_EINVAL;
   if (Cout % 32 != 0) return LION_EUNSUPPORTED;
   const int ksteps4 = ((Cin + 1) / 2 + 3) / 4, total = Cout * ksteps4 * 8;
-  skinny_pack_kernel<<<lion_cdiv(total, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(w, Cout, Cin, ksteps4, wp);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<skinny_pack_kernel>(lion_cdiv(total, 256), 256, 0, static_cast<hipStream_t>(stream), w, Cout, Cin,
+                                         ksteps4, wp);
 }
 
 // k-splits of a layer: ~256 workgroups, at least 8 k-steps per wave
@@ -232,12 +231,9 @@ int lion_skinny_gemm(const float *pin, int ks_in, const float *bias_in, int act_
     return LION_EINVAL;
   if (Cout % 32 != 0) return LION_EUNSUPPORTED;
   const size_t lds = (size_t)16 * 1024 * 4;
-  static LionLdsLimit cfg = {};
-  if (int e = lion_dynamic_lds(&skinny_gemm_kernel<false>, lds, cfg)) return e;
-  skinny_gemm_kernel<false><<<dim3(Cout / 32, lion_skinny_splits(Cin, Cout), nb), 1024, lds, static_cast<hipStream_t>(stream)>>>(
-      pin, ks_in, bias_in, act_in, addT, wp, Cin, Cout, pout, nullptr, 0, nullptr, nullptr);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<skinny_gemm_kernel<false>>(dim3(Cout / 32, lion_skinny_splits(Cin, Cout), nb), 1024, lds,
+                                                static_cast<hipStream_t>(stream), pin, ks_in, bias_in, act_in, addT, wp,
+                                                Cin, Cout, pout, nullptr, 0, nullptr, nullptr);
 }
 
 // The block's last GEMM with its tail: y f32[nb][Cout][32] = resid + relu(sum_q A[q] + bias_a) * sigmoid(W act_in(sum pin + bias_in)),
@@ -250,12 +246,9 @@ int lion_skinny_gemm_se_finish(const float *pin, int ks_in, const float *bias_in
     return LION_EINVAL;
   if (Cout % 32 != 0 || lion_skinny_splits(Cin, Cout) != 1) return LION_EUNSUPPORTED;
   const size_t lds = (size_t)16 * 1024 * 4;
-  static LionLdsLimit cfg = {};
-  if (int e = lion_dynamic_lds(&skinny_gemm_kernel<true>, lds, cfg)) return e;
-  skinny_gemm_kernel<true><<<dim3(Cout / 32, 1, nb), 1024, lds, static_cast<hipStream_t>(stream)>>>(
-      pin, ks_in, bias_in, act_in, nullptr, wp, Cin, Cout, y, A, ks_a, bias_a, resid);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<skinny_gemm_kernel<true>>(dim3(Cout / 32, 1, nb), 1024, lds, static_cast<hipStream_t>(stream), pin,
+                                               ks_in, bias_in, act_in, nullptr, wp, Cin, Cout, y, A, ks_a, bias_a,
+                                               resid);
 }
 
 // y f32[nb][C][32] from partials: mode 0: sum_q A[q] + bias_a; mode 1: resid + relu(sum_q A[q] + bias_a) *
@@ -265,27 +258,22 @@ int lion_skinny_finish(const float *A, int ks_a, const float *bias_a, const floa
   if (!A || !y || nb <= 0 || C <= 0 || ks_a < 1 || (mode != 0 && mode != 1)) return LION_EINVAL;
   if (mode == 1 && (!Bp || !resid || ks_b < 1)) return LION_EINVAL;
   const int n = nb * C * 32;
-  skinny_finish_kernel<<<lion_cdiv(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(A, ks_a, bias_a, Bp, ks_b,
-                                                                                        resid, n, C, mode, y);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<skinny_finish_kernel>(lion_cdiv(n, 256), 256, 0, static_cast<hipStream_t>(stream), A, ks_a, bias_a,
+                                           Bp, ks_b, resid, n, C, mode, y);
 }
 
 int lion_to_channel_major(const float *a, int lda, int Ca, float *oa, const float *b, int ldb, int Cb, float *ob, int B,
                           lionStream_t stream) {
   if (B <= 0 || (!a && !b) || (a && (!oa || Ca <= 0 || lda < 0)) || (b && (!ob || Cb <= 0 || ldb < 0))) return LION_EINVAL;
   const int nb = (B + 31) / 32, total = nb * 32 * ((a ? Ca : 0) + (b ? Cb : 0));
-  to_channel_major_kernel<<<lion_cdiv(total, 256) > 64 ? 64 : lion_cdiv(total, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      a, lda, Ca, oa, b, ldb, Cb, ob, B, nb);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<to_channel_major_kernel>(lion_cdiv(total, 256) > 64 ? 64 : lion_cdiv(total, 256), 256, 0,
+                                              static_cast<hipStream_t>(stream), a, lda, Ca, oa, b, ldb, Cb, ob, B, nb);
 }
 
 int lion_from_channel_major(const float *x, int B, int C, float *y, lionStream_t stream) {
   if (!x || !y || B <= 0 || C <= 0) return LION_EINVAL;
-  from_channel_major_kernel<<<lion_cdiv(B * C, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(x, B, C, y);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<from_channel_major_kernel>(lion_cdiv(B * C, 256), 256, 0, static_cast<hipStream_t>(stream), x, B,
+                                                C, y);
 }
 
 } // extern "C"

@@ -725,6 +725,16 @@ static VoxPlan make_plan(int B, int C, int N, int r) {
   return p;
 }
 
+// the plan's NP in {1, 2, 4, 8} -> f(IntC<NP>), the fused and the scatter kernel's template argument
+template <typename F> static int vox_np_dispatch(int NP, F f) {
+  switch (NP) {
+  case 1: return f(IntC<1>{});
+  case 2: return f(IntC<2>{});
+  case 4: return f(IntC<4>{});
+  default: return f(IntC<8>{});
+  }
+}
+
 static int voxelize_impl(const float *feat, const int32_t *coords_i, const float *coords_f, int B,
                          int C, int N, int r, int normalize, float eps, float *out,
                          float *norm_coords, int32_t *ind, int32_t *cnt, void *ws, size_t ws_bytes,
@@ -744,46 +754,32 @@ static int voxelize_impl(const float *feat, const int32_t *coords_i, const float
   if (p.fast && aligned) {
     const int grid = ((B + 7) / 8) * 8 * p.S * p.CS;
     const int ch_cap = 64; // channel chunk (as many as the arena holds).  Round 3 sweep at (64,2048,32), us with / without P1: 8: 77.5 / 75.3, 16: 72.9 / 67.6, 24: 65.9 / 63.4, 32: 66.7 / 64.0, 64: 64.3 / 62.1
-#define LION_VOX_LAUNCH(P1, NPV)                                                                       \
-  {                                                                                                    \
-    static LionLdsLimit cfg = {};                                                                      \
-    if (int e = lion_dynamic_lds(&vox_fused_kernel<P1, NPV>, p.lds, cfg)) return e;                    \
-    vox_fused_kernel<P1, NPV><<<grid, VT, p.lds, st>>>(feat, coords_i, coords_f, B, C, N, r, p.S, p.CS, p.SV, \
-                                                       p.n_words, p.arena_words, ch_cap, normalize, eps, out, \
-                                                       norm_coords, ind, cnt, plan);                   \
-  }
-#define LION_VOX_NP(P1)                                                                                \
-  switch (p.NP) {                                                                                      \
-  case 1: LION_VOX_LAUNCH(P1, 1) break;                                                                \
-  case 2: LION_VOX_LAUNCH(P1, 2) break;                                                                \
-  case 4: LION_VOX_LAUNCH(P1, 4) break;                                                                \
-  default: LION_VOX_LAUNCH(P1, 8) break;                                                               \
-  }
-    if (coords_f) { LION_VOX_NP(true) } else { LION_VOX_NP(false) }
-#undef LION_VOX_NP
-#undef LION_VOX_LAUNCH
-    LION_LAUNCH_CHECK();
-    return 0;
+    return lion_with_flags(coords_f != nullptr, [&](auto P1) {
+      return vox_np_dispatch(p.NP, [&](auto NPV) {
+        return lion_launch<vox_fused_kernel<decltype(P1)::value, decltype(NPV)::value>>(
+            grid, VT, p.lds, st, feat, coords_i, coords_f, B, C, N, r, p.S, p.CS, p.SV, p.n_words, p.arena_words, ch_cap,
+            normalize, eps, out, norm_coords, ind, cnt, plan);
+      });
+    });
   }
   // fallback
   const int32_t *ci = coords_i;
   if (coords_f) {
     int32_t *vox = reinterpret_cast<int32_t *>(w + p.off_vox);
-    p1_kernel<<<B, VT, 0, st>>>(coords_f, N, r, normalize, eps, norm_coords, vox);
-    LION_LAUNCH_CHECK();
+    if (int e = lion_launch<p1_kernel>(B, VT, 0, st, coords_f, N, r, normalize, eps, norm_coords, vox)) return e;
     ci = vox;
   }
   hipError_t e = hipMemsetAsync(cnt, 0, (size_t)B * r3 * 4, st);
   if (e != hipSuccess) return (int)e;
-  vox_index_atomic_kernel<<<dim3(lion_cdiv(N, 256), B), 256, 0, st>>>(ci, N, r, ind, cnt);
-  LION_LAUNCH_CHECK();
+  if (int e = lion_launch<vox_index_atomic_kernel>(dim3(lion_cdiv(N, 256), B), 256, 0, st, ci, N, r, ind, cnt))
+    return e;
   if (feat) {
     e = hipMemsetAsync(out, 0, (size_t)B * C * r3 * 4, st);
     if (e != hipSuccess) return (int)e;
     const int CT = 16;
-    vox_scatter_atomic_kernel<<<dim3(lion_cdiv(N, 256), lion_cdiv(C, CT), B), 256, 0, st>>>(
-        feat, ind, cnt, C, N, r3, CT, out);
-    LION_LAUNCH_CHECK();
+    if (int e = lion_launch<vox_scatter_atomic_kernel>(dim3(lion_cdiv(N, 256), lion_cdiv(C, CT), B), 256, 0, st, feat,
+                                                       ind, cnt, C, N, r3, CT, out))
+      return e;
   }
   return 0;
 }
@@ -887,37 +883,21 @@ static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_b
   int occ_td = 0, occ_th = 0;   // the tile geometry of the flags: the sparse convolution's own choice (csrc/conv3d.hip)
   if (occ_flags)
     if (int e = lion_internal_sparse_tile_dims(r, &occ_td, &occ_th)) return e;
-#define LION_VOXS_LAUNCH(NPV)                                                                          \
-  if (occ_flags) {                                                                                     \
-    static LionLdsLimit cfg = {};                                                                      \
-    if (int e = lion_dynamic_lds(&vox_scatter_kernel<NPV, true>, lds, cfg)) return e;                  \
-    vox_scatter_kernel<NPV, true><<<grid, VT, lds, st>>>(feat, plan, B, C, N, r3, p.S, p.CS, p.SV, p.n_words, \
-                                                         (int)(arena / 4), 64, out, occ_flags, r, occ_td, occ_th); \
-  } else {                                                                                             \
-    static LionLdsLimit cfg = {};                                                                      \
-    if (int e = lion_dynamic_lds(&vox_scatter_kernel<NPV, false>, lds, cfg)) return e;                 \
-    vox_scatter_kernel<NPV, false><<<grid, VT, lds, st>>>(feat, plan, B, C, N, r3, p.S, p.CS, p.SV, p.n_words, \
-                                                          (int)(arena / 4), 64, out, nullptr, r, 0, 0); \
-  }
-  switch (p.NP) {
-  case 1: LION_VOXS_LAUNCH(1) break;
-  case 2: LION_VOXS_LAUNCH(2) break;
-  case 4: LION_VOXS_LAUNCH(4) break;
-  default: LION_VOXS_LAUNCH(8) break;
-  }
-#undef LION_VOXS_LAUNCH
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_with_flags(occ_flags != nullptr, [&](auto READ) { // without flags occ_td = occ_th = 0
+    return vox_np_dispatch(p.NP, [&](auto NPV) {
+      return lion_launch<vox_scatter_kernel<decltype(NPV)::value, decltype(READ)::value>>(
+          grid, VT, lds, st, feat, plan, B, C, N, r3, p.S, p.CS, p.SV, p.n_words, (int)(arena / 4), 64, out, occ_flags, r,
+          occ_td, occ_th);
+    });
+  });
 }
 
 int lion_avg_voxelize_backward(const float *gy, const int32_t *ind, const int32_t *cnt, int B,
                                int C, int N, int r3, float *gx, lionStream_t stream) {
   if (!gy || !ind || !cnt || !gx || B <= 0 || C <= 0 || N <= 0 || r3 <= 0) return LION_EINVAL;
   const int CT = 8;
-  vox_grad_kernel<<<dim3(lion_cdiv(N, 256), lion_cdiv(C, CT), B), 256, 0,
-                    static_cast<hipStream_t>(stream)>>>(gy, ind, cnt, C, N, r3, CT, gx);
-  LION_LAUNCH_CHECK();
-  return 0;
+  return lion_launch<vox_grad_kernel>(dim3(lion_cdiv(N, 256), lion_cdiv(C, CT), B), 256, 0,
+                                      static_cast<hipStream_t>(stream), gy, ind, cnt, C, N, r3, CT, gx);
 }
 
 } // extern "C"

@@ -50,7 +50,7 @@ __global__ void split_pack_kernel(const float *__restrict__ w, int Cout, int Cin
 // instrumented COPY of this file (0 item prologue, 1 waits at the chunk's two plane barriers, 2 load issue + wait + activate +
 // max, 3 max barrier, 4 cut + LDS write, 5 wait for the next weight group + group barrier, 6 taps, 7 epilogue); the product build carries no instrumentation and no switches.
 
-template <int N> struct IntC { static constexpr int value = N; }; // compile-time count for generic lambdas
+// (IntC: csrc/common.h)
 
 // Compile-time switches of the round-5 sparse-plan experiments.  BOTH ARE OFF in the product: built, bit-exact, measured on
 // one box against the round-4 kernel inside the sampling step (profiles/archive/r05a_conv_ab_variants_one_box.txt) and not adopted:
