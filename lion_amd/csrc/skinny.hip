@@ -28,6 +28,9 @@ __device__ __forceinline__ float4 ld_stream(const float4 *p) { // read-once weig
   const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
   return make_float4(v.x, v.y, v.z, v.w);
 }
+// ReLU that keeps a NaN, as torch's: v > 0 ? v : 0 turns it into 0 and a diverged sample into a finite one.  Every other
+// value, the sign of a zero included, comes out as from v > 0 ? v : 0.
+__device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
 
 // operand element k of batch column b: act_in( sum_q Pin[q][k][b] + bias_in[k] ) + addT[k][b]
 //
@@ -97,14 +100,14 @@ __global__ __launch_bounds__(1024) void skinny_gemm_kernel(const float *__restri
       float4 v = make_float4(bq[sl], bq[sl], bq[sl], bq[sl]);
 #pragma unroll
       for (int q = 0; q < 4; ++q) { v.x += x4[sl][q].x; v.y += x4[sl][q].y; v.z += x4[sl][q].z; v.w += x4[sl][q].w; } // fixed order
-      if (ks_in > 4) { // more input partials than the unrolled four (not produced by lion_skinny_splits today)
+      if (ks_in > 4) { // more input partials than the unrolled four: the eight of SE.fc[0] (2048 -> 256) of the released model
         const size_t off = (size_t)min(k, Cin - 1) * 32 + (lane & 7) * 4;
         for (int q = 4; q < ks_in; ++q) {
           const float4 t = *reinterpret_cast<const float4 *>(xb + q * in_stride + off);
           v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
         }
       }
-      if (act_in == 1) { v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f; }
+      if (act_in == 1) { v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w); }
       v.x += t4[sl].x; v.y += t4[sl].y; v.z += t4[sl].z; v.w += t4[sl].w;
       const bool live = k < Cin && (k >> 1) < s_hi;
       if (!live) v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(1024) void skinny_gemm_kernel(const float *__restri
     for (int q = 0; q < ks_a; ++q) a += fa[(size_t)q * n + i];
     float g = 0.f;
     g += s;
-    pout[i] = resid[i] + (a > 0.f ? a : 0.f) * (1.0f / (1.0f + expf(-g)));
+    pout[i] = resid[i] + relu_keep_nan(a) * (1.0f / (1.0f + expf(-g)));
     return;
   }
   pout[((size_t)(ks * NB + nb) * Cout + o0 + (tid >> 5)) * 32 + (tid & 31)] = s;
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(256) void skinny_finish_kernel(const float *__restr
   if (mode == 1) {
     float g = 0.f;
     for (int q = 0; q < ks_b; ++q) g += Bp[(size_t)q * n + i];
-    a = resid[i] + (a > 0.f ? a : 0.f) * (1.0f / (1.0f + expf(-g)));
+    a = resid[i] + relu_keep_nan(a) * (1.0f / (1.0f + expf(-g)));
   }
   y[i] = a;
 }

@@ -155,12 +155,22 @@ class Prior(nn.Module):
         return self.output_layer(x)
 
     def _skinny_ok(self, x):
-        """inference on the GPU with ResBlockSEDrop blocks: every layer is a 32-row GEMM -> csrc/skinny.hip."""
+        """inference on the GPU with ResBlockSEDrop blocks: every layer is a 32-row GEMM -> csrc/skinny.hip, whose output
+        tile is 32 channels: a model with another width anywhere (an SE hidden width nf / 8 of 8 or 12, a style width of
+        100) stays on the layer-by-layer formulation of forward()."""
         from .. import pvcnn2_ada
         return (pvcnn2_ada.FUSE_INFERENCE and not self.training and not torch.is_grad_enabled() and x.is_cuda
                 and x.dtype == torch.float32 and not torch.is_autocast_enabled() and not self.clip_forge_enable
                 and all(type(m) is ResBlockSEDrop for m in self.all_modules)
-                and x.dim() == 4 and x.shape[2] == 1 and x.shape[3] == 1)
+                and x.dim() == 4 and x.shape[2] == 1 and x.shape[3] == 1
+                and all(conv.out_channels % 32 == 0 for conv in self._skinny_convs()))
+
+    def _skinny_convs(self):
+        """the convolutions that _forward_skinny hands to the skinny GEMM"""
+        yield self.input_layer
+        for blk in self.all_modules:
+            yield from (blk.conv1, blk.conv2, blk.SE.fc[0], blk.SE.fc[2])
+        yield self.output_layer
 
     def _forward_skinny(self, x, temb):
         """4 launches per residual block (round 6; 5 before) instead of ~15 (channel-major [C, 32] activations throughout):
