@@ -222,6 +222,21 @@ int lion_chain_begin_step_temb(const float *table, int n_steps, int32_t *counter
                                const float *temb_table, int temb_width, float *temb_out, lionStream_t stream);
 int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
                                const uint32_t *seed, uint32_t stream_id, float *out, float *z_out, lionStream_t stream);
+/* The forward-process draw that starts a chain at an intermediate step (diffuse-denoise; sample_q of
+ * utils/diffusion_pvd.py:105-113 with the scalars of iw_quantities_t :44-103):
+ *   out = (m*x0) + (s*z)        two products and one sum, each rounded once (no fma)
+ * over numel floats, any numel.  z = z_in where z_in != NULL (the given-noise path); else z ~ N(0,1) is drawn in the kernel
+ * with the chain's generator (Philox4x32-10 keyed by the 64-bit seed in device memory, Box-Muller: the device function of
+ * lion_chain_update_noise) at counter = (element/4, LION_DIFFUSE_STEP_WORD, stream_id).  A chain step's counter holds its
+ * index into the schedule table there, 0 <= i < n_steps <= INT_MAX, so no step of any chain can have this word and a draw
+ * never coincides with a step's noise under the same seed and stream_id.  The counter goes by element: a call on n elements
+ * draws the prefix of a call on more.  z_out (may be NULL) receives the z that was used; out may alias x0.  Pointers that are
+ * all 16-byte aligned take one 16-byte access per operand and lane, others and the last partial quad go element by element.
+ * LION_EINVAL before any launch: x0 or out NULL, numel == 0, z_in and seed both NULL. */
+#define LION_DIFFUSE_STEP_WORD 0xFFFFFFFFu
+int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s,
+                       const uint32_t *seed /* device u32[2]: lo, hi; may be NULL with z_in */, uint32_t stream_id,
+                       float *out, float *z_out, lionStream_t stream);
 /* x f32[B][N][D] (point-major latent; 3 <= D <= 8) -> channel-major all f32[B][D][N], coords f32[B][3][N] (rows 0-2),
  * rest f32[B][D-3][N]; each output may be NULL: the view / permute / slice / contiguous head of
  * models/latent_points_ada_localprior.py:72-84 + models/latent_points_ada.py:118-121 in one launch. */

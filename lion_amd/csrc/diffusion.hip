@@ -150,6 +150,45 @@ static int update_noise_launch(int mode, unsigned blocks, hipStream_t st, const 
                                                          cm_points);
 }
 
+// Forward-process draw out = m*x0 + s*z (sample_q, utils/diffusion_pvd.py:105-113) with the chain's generator: quad q of the
+// flat tensor takes Philox counter (q, LION_DIFFUSE_STEP_WORD, stream_id), whatever the pointers' alignment.  VEC: every pointer
+// is 16-byte aligned -> one 16-byte access per operand and full quad; else (and in the tail quad) element by element.
+// The tensors are not __restrict__: out may alias x0 (a lane reads its quad before it writes it, no lane reads another's).
+template <bool VEC>
+__global__ void diffuse_kernel(const float *x0, const float *z_in, size_t numel, float m, float s,
+                               const uint32_t *__restrict__ seed_words, uint32_t stream_id, float *out, float *z_out) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = q * 4;
+  if (i >= numel) return;
+  const bool full = VEC && i + 3 < numel;
+  float xv[4], z[4], o[4];
+  if (z_in) {
+    if (full) {
+      const float4 t = *reinterpret_cast<const float4 *>(z_in + i);
+      z[0] = t.x; z[1] = t.y; z[2] = t.z; z[3] = t.w;
+    } else {
+      for (int j = 0; j < 4; ++j) z[j] = i + j < numel ? z_in[i + j] : 0.f;
+    }
+  } else {
+    const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
+    normal4(q, LION_DIFFUSE_STEP_WORD, stream_id, seed, z);
+  }
+  if (full) {
+    const float4 t = *reinterpret_cast<const float4 *>(x0 + i);
+    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+  } else {
+    for (int j = 0; j < 4; ++j) xv[j] = i + j < numel ? x0[i + j] : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(m, xv[j]), mul_rn(s, z[j]));
+  if (full) {
+    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
+    if (z_out) *reinterpret_cast<float4 *>(z_out + i) = make_float4(z[0], z[1], z[2], z[3]);
+  } else {
+    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; if (z_out) z_out[i + j] = z[j]; }
+  }
+}
+
 } // namespace
 
 extern "C" {
@@ -208,6 +247,18 @@ int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, in
   const unsigned blocks = (unsigned)((quads + 255) / 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return update_noise_launch(mode, blocks, st, x, eps_cm, numel, cur, seed, stream_id, out, z_out, N);
+}
+
+int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s, const uint32_t *seed,
+                       uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
+  if (!x0 || !out || numel == 0 || (!z_in && !seed)) return LION_EINVAL;
+  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
+  if (blocks > 0x7fffffffu) return LION_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool vec = ((((uintptr_t)x0) | ((uintptr_t)z_in) | ((uintptr_t)out) | ((uintptr_t)z_out)) & 15) == 0;
+  return vec ? lion_launch<diffuse_kernel<true>>((unsigned)blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out, z_out)
+             : lion_launch<diffuse_kernel<false>>((unsigned)blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out,
+                                                  z_out);
 }
 
 } // extern "C"

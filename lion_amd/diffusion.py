@@ -1,6 +1,6 @@
 """Discrete diffusion process -- mirror of the reference's ``utils/diffusion_pvd.py``
 (``DiffusionDiscretized`` :17; constants :118-142; ``run_denoising_diffusion`` :224-303;
-``run_ddim`` :390-473; ``get_q_posterior_mean`` :475-486) and ``utils/diffusion.py:28-65``
+``run_ddim`` :390-473; ``get_q_posterior_mean`` :475-486; ``run_denoising_diffusion_from_t`` :504-563) and ``utils/diffusion.py:28-65``
 (``make_beta_schedule``).
 
 What changes on MI355X: by default (``graph=True``, GPU tensors, eval) a chain is S replays of ONE captured
@@ -183,6 +183,21 @@ class DiffusionDiscretized(object):
             table[i, :4] = (t + 1, s_, c_, sigma_)
         return table
 
+    def ddpm_table(self, t_from, temp=1.0, noise_scale=None):
+        """[t_from, 8] float32 rows {t_model, k_outer, k_a, k_b, scale, temp, t == 0, 0} of the ancestral steps
+        t = t_from-1 ... 0: the whole chain for t_from = T, its tail otherwise.  ``noise_scale(t)`` overrides sqrt(beta_t) at
+        t > 0.  Host arithmetic only."""
+        t_from = int(t_from)
+        if not 1 <= t_from <= self._diffusion_steps:
+            raise ValueError(f"ddpm_table: t_from = {t_from} outside [1, {self._diffusion_steps}]")
+        table = np.zeros((t_from, 8), np.float32)
+        for i, t in enumerate(reversed(range(t_from))):
+            is0, k_outer, k_a, k_b, scale = self.ddpm_coefficients(t)
+            if noise_scale is not None and not is0:
+                scale = float(noise_scale(t))
+            table[i] = (t + 1, k_outer, k_a, k_b, scale, temp, 1.0 if is0 else 0.0, 0.0)
+        return table
+
     def _noise(self, size, source, device):
         if source == 'cpu':  # the reference's stream: torch.randn(size).to(device), :465-466
             return torch.randn(size).to(device)
@@ -216,12 +231,7 @@ class DiffusionDiscretized(object):
         x_image = None
         if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
             T = self._diffusion_steps
-            table = np.zeros((T, 8), np.float32)
-            for i, t in enumerate(reversed(range(T))):
-                is0, k_outer, k_a, k_b, scale = self.ddpm_coefficients(t)
-                if noise_scale is not None and not is0:
-                    scale = float(noise_scale(t))
-                table[i] = (t + 1, k_outer, k_a, k_b, scale, temp, 1.0 if is0 else 0.0, 0.0)
+            table = self.ddpm_table(T, temp, noise_scale)
             ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DDPM, T)
             x_image = ch.run(x_noisy, table, _chain.draw_seed(), condition_input, clip_feat,
                              trajectory=output_list['pred_x'] if keep_trajectory else None,
@@ -230,7 +240,21 @@ class DiffusionDiscretized(object):
                 x_image = (x_image.clamp(min=-1., max=1.) + 1.0) / 2.0
             model.train()
             return x_image, output_list
-        for t in reversed(range(0, self._diffusion_steps)):
+        x_image = self._ancestral_steps(model, x_noisy, self._diffusion_steps, temp, enable_autocast, condition_input,
+                                        given_noise, clip_feat, kwargs, output_list['pred_x'])
+        if is_image:
+            x_image = (x_image.clamp(min=-1., max=1.) + 1.0) / 2.0
+        model.train()
+        return x_image, output_list
+
+    def _ancestral_steps(self, model, x_noisy, t_from, temp, enable_autocast, condition_input, given_noise, clip_feat, kwargs,
+                         states, generator=None):
+        """the eager ancestral steps t = t_from-1 ... 0 from x_noisy; returns the posterior mean of the step at t = 0.  The noise
+        of step t is given_noise[1][t] where given, else a device draw (from `generator` if one is passed).  `states` (a list,
+        or None) receives the state after every step -- for t = 0 the state BEFORE it once more, as the reference reports it."""
+        dev, size, num_samples = self.device, list(x_noisy.shape), x_noisy.shape[0]
+        x_image = None
+        for t in reversed(range(0, t_from)):
             timestep = torch.full((num_samples,), t + 1, dtype=torch.int64, device=dev)
             mixing = self.get_mixing_component(x_noisy, timestep, enabled=getattr(model, 'mixed_prediction', False))
             with torch.autocast("cuda", enabled=enable_autocast):
@@ -241,14 +265,77 @@ class DiffusionDiscretized(object):
             if is0:
                 x_image = diffusion_ops.ddpm_update(x_noisy, eps_hat, None, True, k_outer, k_a, k_b, scale, temp)
             else:
-                z = (torch.randn(size=size, device=dev) if given_noise is None
+                z = (torch.randn(size=size, device=dev, generator=generator) if given_noise is None
                      else given_noise[1][t].to(dev)).contiguous()
                 x_noisy = diffusion_ops.ddpm_update(x_noisy, eps_hat, z, False, k_outer, k_a, k_b, scale, temp)
-            output_list['pred_x'].append(x_noisy)
-        if is_image:
-            x_image = (x_image.clamp(min=-1., max=1.) + 1.0) / 2.0
+            if states is not None:
+                states.append(x_noisy)
+        return x_image
+
+    # ---- diffuse-denoise: the forward draw at an index, and the reverse chain from there -----------------------------------
+    def diffuse(self, x0, t, noise=None, seed=None, return_noise=False):
+        """x_t = sqrt(alpha_bar_t) * x0 + sqrt(1 - alpha_bar_t) * z at the schedule INDEX t, 0 <= t <= T-1: what
+        ``sample_q`` gives on the quantities of ``iw_quantities_t(B, full(t))`` (reference :44-113; the model's timestep there
+        is t + 1).  The two scalars are those expressions on the host copy of the float32 schedule, each operation rounded
+        once -- no device synchronisation; a device library's sqrt may differ from them in the last bit -- and the
+        draw is one kernel (lion_chain_diffuse): z = ``noise`` if given, else N(0, 1) from the chain's Philox generator under
+        ``seed`` (None: one is drawn with chain.draw_seed(), so torch.manual_seed governs it), on a stream of its own, so that
+        a chain run under the same seed repeats none of it.  return_noise: (x_t, z)."""
+        if not isinstance(t, (int, np.integer)) or isinstance(t, bool) or not 0 <= t <= self._diffusion_steps - 1:
+            raise ValueError(f"diffuse: t = {t!r} is not an index in [0, {self._diffusion_steps - 1}]")
+        ab = self._h_alpha_bars[int(t)]
+        m, s = float(torch.sqrt(ab)), float(torch.sqrt(1.0 - ab))
+        if noise is None and seed is None:
+            seed = _chain.draw_seed()
+        return diffusion_ops.diffuse(x0.contiguous(), m, s, noise=None if noise is None else noise.contiguous(), seed=seed,
+                                     return_noise=return_noise)
+
+    @torch.no_grad()
+    def run_denoising_diffusion_from_t(self, model, num_samples, shape, time_start, x_noisy, temp=1.0, enable_autocast=False,
+                                       is_image=False, prior_var=1.0, condition_input=None, given_noise=None, clip_feat=None,
+                                       graph=True, keep_trajectory=True, conv_precision="fp32"):
+        """The tail of the ancestral chain from ``x_noisy`` (reference :504-563): the steps t = time_start-1 ... 0, the last of
+        which returns the posterior mean; 1 <= time_start <= T, and time_start = T is the whole chain from a given start.
+        Returns (x, output_list): output_list is the reference's plain list of the state after every step, whose last entry
+        repeats the state before the final update (the reference appends x_noisy there, not the mean); empty with
+        keep_trajectory=False.  given_noise = (unused, z) with z indexed by t, as in the reference: step t adds z[t].
+        time_start = 0 returns (x_noisy, []) unchanged, where the reference would raise (its x_image is never assigned).
+        is_image and prior_var are accepted and unused, as in the reference.
+        graph=True: the tail is replayed on the captured chain of run_denoising_diffusion for this model and batch shape --
+        the same cache entry, so a model that has sampled is not captured again -- with the schedule table's last
+        time_start rows; the per-step noise is then the chain's Philox stream (key from chain.draw_seed())."""
+        with conv_ops.requested_precision(conv_precision):
+            return self._denoise_from_t(model, num_samples, shape, time_start, x_noisy, temp, enable_autocast, condition_input,
+                                        given_noise, clip_feat, graph, keep_trajectory, None)
+
+    def _denoise_from_t(self, model, num_samples, shape, time_start, x_noisy, temp, enable_autocast, condition_input,
+                        given_noise, clip_feat, graph, keep_trajectory, seed):
+        """seed (editing.diffuse_denoise): the 64-bit key of the tail's noise, in place of a draw from torch's global generator"""
+        if isinstance(time_start, bool) or not isinstance(time_start, (int, np.integer)) \
+                or not 0 <= time_start <= self._diffusion_steps:
+            raise ValueError(f"run_denoising_diffusion_from_t: time_start = {time_start!r} outside [0, {self._diffusion_steps}]")
+        output_list = []
+        if time_start == 0:
+            return x_noisy, output_list
+        if not x_noisy.is_cuda:
+            raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
+        if list(x_noisy.shape) != [num_samples] + list(shape):
+            raise ValueError(f"run_denoising_diffusion_from_t: x_noisy {tuple(x_noisy.shape)} for {[num_samples] + list(shape)}")
+        model.eval()
+        dev = self.device
+        x_noisy = x_noisy.to(dev).contiguous()
+        states = output_list if keep_trajectory else None
+        if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, {}):
+            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DDPM,
+                                  self._diffusion_steps)
+            x = ch.run(x_noisy, self.ddpm_table(int(time_start), temp), _chain.draw_seed() if seed is None else seed,
+                       condition_input, clip_feat, trajectory=states, trajectory_before_last=True)
+        else:
+            gen = None if seed is None else torch.Generator(device=dev).manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
+            x = self._ancestral_steps(model, x_noisy, int(time_start), temp, enable_autocast, condition_input, given_noise,
+                                      clip_feat, {}, states, generator=gen)
         model.train()
-        return x_image, output_list
+        return x, output_list
 
     @torch.no_grad()
     def run_ddim(self, model, num_samples, shape, temp=1.0, enable_autocast=False, is_image=True,

@@ -1,9 +1,11 @@
-"""Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update."""
+"""Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, and the forward-process
+draw lion_chain_diffuse."""
+import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["ddim_update", "ddpm_update"]
+__all__ = ["ddim_update", "ddpm_update", "diffuse"]
 
 
 def ddim_update(x, eps, z, s, c, sigma, out=None):
@@ -12,6 +14,28 @@ def ddim_update(x, eps, z, s, c, sigma, out=None):
     out = torch.empty_like(x) if out is None else out
     _lib.call("lion_ddim_update", x, eps, z, x.numel(), float(s), float(c), float(sigma), out)
     return out
+
+
+def seed_words(seed, device):
+    """the 64-bit Philox key as the two 32-bit words (lo, hi) the chain kernels read from device memory"""
+    words = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
+    return torch.from_numpy(words).to(device)
+
+
+def diffuse(x0, m, s, noise=None, seed=None, stream_id=1, out=None, return_noise=False):
+    """out = m*x0 + s*z, the forward-process draw (utils/diffusion_pvd.py:105-113).  z = `noise` if given, else N(0, 1) drawn
+    in the kernel by the chain's Philox generator under the 64-bit `seed` (lion_chain_diffuse; stream_id 1 keeps the draw apart
+    from every step's noise of a chain run under the same seed, which uses stream 0).  out may be x0."""
+    _lib.require_cuda(x0, noise, out)
+    if noise is None and seed is None:
+        raise ValueError("diffuse: either noise or seed")
+    if noise is not None and noise.shape != x0.shape:
+        raise ValueError(f"diffuse: noise {tuple(noise.shape)} for x0 {tuple(x0.shape)}")
+    out = torch.empty_like(x0) if out is None else out
+    z_out = torch.empty_like(x0) if return_noise else None
+    _lib.call("lion_chain_diffuse", x0, noise, x0.numel(), float(m), float(s),
+              None if noise is not None else seed_words(int(seed), x0.device), int(stream_id), out, z_out)
+    return (out, z_out) if return_noise else out
 
 
 def ddpm_update(x, eps, z, t_is_zero, k_outer, k_a, k_b, scale, temp, out=None):

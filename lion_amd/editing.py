@@ -1,0 +1,100 @@
+"""Diffuse-denoise -- the two-latent recipe of the reference's ``trainers/denoise_pts.py:101-156``: encode a shape, push
+its latents part of the way into the forward process, run the reverse chain from there, decode.  Shape variation, denoising
+of noisy or voxelised inputs, editing.
+
+Per latent the device work is one forward draw (``DiffusionDiscretized.diffuse``: lion_chain_diffuse, noise on the chip) and
+``time_start`` replays of the prior's captured ancestral step (``run_denoising_diffusion_from_t``) -- the chain a sampling
+call of the same batch shape captured is the one replayed here.  One ``time_start`` per latent for the whole batch, as in the
+reference.
+"""
+from __future__ import annotations
+
+import numbers
+
+import torch
+
+from . import chain as _chain
+from . import conv_ops
+
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _split_seed(seed: int, n: int):
+    """n 64-bit keys from one (SplitMix64, Steele et al. 2014): one call's seed -> a key per draw"""
+    out, state = [], seed & _MASK64
+    for _ in range(n):
+        state = (state + 0x9E3779B97F4A7C15) & _MASK64
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+        out.append(z ^ (z >> 31))
+    return out
+
+
+@torch.no_grad()
+def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=None, keep_first=False, graph=True,
+                    conv_precision="fp32", seed=None):
+    """x [B, N, 3] -> (points [B, N, 3], info).  vae: models.vae_adain.Model (in the mode the caller wants: eval() for
+    inference); dae: [global prior, local prior]; diffusion: DiffusionDiscretized.
+
+    Sequence (denoise_pts.py:101-156): encode_global -> sample -> [diffuse -> denoise on dae[0]] -> global2style ->
+    encode_local(x, style) -> sample -> [diffuse -> denoise on dae[1], conditioned on the edited global latent] -> decode.
+
+    time_start: an int, or a (global, local) pair, each in 0 ... T-1.  As in the reference, the latent is diffused with the
+    schedule INDEX time_start (alpha_bar[time_start], the marginal of the model's timestep time_start + 1) while denoising
+    begins with the step at index time_start - 1: the chain runs time_start steps and treats its start as one step less noisy
+    than it was drawn.  That off-by-one is the reference's and is kept.  0 skips diffusion for that latent; with both at 0
+    the result is the VAE's reconstruction from its sampled latents.
+    keep_first: sample 0 keeps its own latents (the reference's ``eps[0:1] = eps_ori[0:1]``), so the batch shows the input's
+    reconstruction next to its variations.
+    seed: makes the whole call repeatable and leaves torch's global generators alone; None draws one from torch's CPU
+    generator (chain.draw_seed), so torch.manual_seed governs the call.
+    The local prior's condition_input is vae.global2style(edited global latent), as the samplers and the training of this
+    package pass it; the reference's recipe passes the latent itself, which is the same tensor whenever style_mlp is '' (every
+    released configuration).
+    info: 'global_original', 'global_edited', 'local_original', 'local_edited' (the four latents, [B] + latent_shape()),
+    'condition_input' (what the local prior was conditioned on), 'time_start' (the pair) and 'seeds' (the call's seed and the
+    key of every draw derived from it)."""
+    T = diffusion._diffusion_steps
+    pair = tuple(time_start) if isinstance(time_start, (tuple, list)) else (time_start, time_start)
+    if len(pair) != 2 or any(isinstance(t, bool) or not isinstance(t, numbers.Integral) or not 0 <= t <= T - 1 for t in pair):
+        raise ValueError(f"diffuse_denoise: time_start = {time_start!r}: an int or a (global, local) pair in [0, {T - 1}]")
+    pair = (int(pair[0]), int(pair[1]))
+    if not x.is_cuda:
+        raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
+    base = _chain.draw_seed() if seed is None else int(seed) & _MASK64
+    names = ("vae", "diffuse_global", "chain_global", "diffuse_local", "chain_local")
+    seeds = dict(zip(names, _split_seed(base, len(names))), seed=base)
+    gen = torch.Generator(device=x.device).manual_seed(seeds["vae"] & 0x7FFFFFFFFFFFFFFF)
+    B, shapes = x.shape[0], vae.latent_shape()
+
+    def sample(dist):   # Normal.sample() on a generator of this call
+        return dist.sample_given_rho(torch.randn(dist.mu.shape, device=dist.mu.device, dtype=dist.mu.dtype, generator=gen))
+
+    def edit(i, eps_ori, condition_input):
+        if pair[i] == 0:
+            return eps_ori
+        which = ("global", "local")[i]
+        eps_t = diffusion.diffuse(eps_ori, pair[i], seed=seeds["diffuse_" + which])
+        with conv_ops.requested_precision(conv_precision):
+            eps, _ = diffusion._denoise_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp, False, condition_input, None,
+                                               clip_feat, graph, False, seeds["chain_" + which])
+        if keep_first:
+            eps[0:1] = eps_ori[0:1]
+        return eps.contiguous()
+
+    eps = sample(vae.encode_global(x))
+    flat_shape = eps.shape
+    global_ori = eps.view([B] + shapes[0]).contiguous()
+    global_new = edit(0, global_ori, None)
+    style = vae.global2style(global_new.view(flat_shape))
+    condition_input = vae.global2style(global_new)
+
+    eps = sample(vae.encode_local(x, style))
+    flat_shape = eps.shape
+    local_ori = eps.view([B] + shapes[1]).contiguous()
+    local_new = edit(1, local_ori, condition_input)
+    points = vae.decoder(None, beta=None, context=local_new.view(flat_shape), style=style)
+    info = {"global_original": global_ori, "global_edited": global_new, "local_original": local_ori,
+            "local_edited": local_new, "condition_input": condition_input, "time_start": pair, "seeds": seeds}
+    return points, info
