@@ -499,7 +499,8 @@ int lion_gn_train_fold(const float *stats, const float *gw, const float *gb, con
                        const float *bias, int bias_stride, int B, int C, int G, int L, float eps, float *A, float *Bs,
                        float *mean, float *rstd, lionStream_t stream);
 /* the same with the row sums taken on shifted values and carried in double (|mean| >> std rows keep their variance):
- * what lion_amd/train_ops.py uses */
+ * what lion_amd/train_ops.py uses.  The shift is the fp32 mean of the row's first min(L, 256) elements, so that no
+ * single element -- an outlier in front -- decides it. */
 int lion_row_stats64(const float *x, int rows, int L, double *stats, lionStream_t stream);
 int lion_gn_train_fold64(const double *stats, const float *gw, const float *gb, const float *fac, int fac_stride,
                          const float *bias, int bias_stride, int B, int C, int G, int L, float eps, float *A,

@@ -69,14 +69,26 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float *__restrict
   }
 }
 
-// one workgroup per row: stats[row] = {sum x, sum x^2} as DOUBLES.  The sums run over x - x0 (x0 = the row's first
-// element) in fp32 and are moved back in double: E[x^2] - E[x]^2 from plain fp32 sums loses (mean / std)^2 x 1e-7 of the
-// variance, i.e. everything once |mean| >> std (round-3 advisor finding; ATen's group_norm does not).
+// one workgroup per row: stats[row] = {sum x, sum x^2} as DOUBLES.  The sums run over x - x0 in fp32 and are moved
+// back in double: E[x^2] - E[x]^2 from plain fp32 sums loses (mean / std)^2 x 1e-7 of the variance, i.e. everything once
+// |mean| >> std (round-3 advisor finding; ATen's group_norm does not).  The pivot x0 is the fp32 mean of the row's first
+// min(L, 256) elements (one per thread, one workgroup reduction; the elements are read again from cache by the pass):
+// the shifted sums lose (1 + (x0 - mean)^2 / var) x 1e-7 of the variance, and a pivot taken from ONE element -- the
+// row's first, until the position-independence test of tests/test_train_norm_numerics_gpu.py -- is as far from the mean
+// as that element happens to be (measured: an outlier of 1000 std in front of an N(0, 1) row cost 3e-5 of the variance
+// at L = 1001, 1.7e-4 at 4096, 1.6e-3 at 32768; with this pivot under 3e-7 wherever it sits).
 __global__ __launch_bounds__(256) void row_stats64_kernel(const float *__restrict__ x, int L, double *__restrict__ stats) {
-  __shared__ float r1[4], r2[4];
+  __shared__ float r0[4], r1[4], r2[4];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float *p = x + (size_t)row * L;
-  const float x0 = p[0];
+  const int n0 = min(L, 256);
+  float s0 = tid < n0 ? p[tid] : 0.f;
+  s0 = row16_sum_rn(s0);
+#pragma unroll
+  for (int m = 16; m < 64; m <<= 1) s0 += __shfl_xor(s0, m, 64);
+  if (lane == 0) r0[wave] = s0;
+  __syncthreads();
+  const float x0 = ((r0[0] + r0[1]) + (r0[2] + r0[3])) / (float)n0;
   float s1 = 0.f, s2 = 0.f;
   if ((L & 3) == 0) {
     for (int i = tid * 4; i < L; i += 1024) {

@@ -13,6 +13,10 @@
 //          every entry ranks itself inside its bin (ascending entry order);  start / count per bin, entry lists per (sample, range).
 //   apply: workgroup = (sample, CT channels): the gy rows streamed into LDS once, thread = bin gathers its entries from
 //          LDS (the entry list is read once per CT channels), gx written coalesced.
+// LIMIT: with more than CSR_EPT * CSR_NT = 32768 entries per sample the long bins are not ranked by their entries but
+// keep the thread-per-bin insertion sort, O(c^2) dependent global steps in ONE thread for a bin of c entries: right for
+// any c, but a bin of thousands of entries runs for minutes there.  A caller with E > 32768 has to keep every bin at a
+// few hundred entries (tests/test_scatter_csr_gpu.py stays at or below 300).
 #include "common.h"
 
 namespace {
