@@ -439,6 +439,19 @@ int lion_pwconv_split_pack_weights_t(const float *w, int Cout, int Cin, const ui
 int lion_pwconv_split_stat_tiles(int Cout, int Cin, int L);
 int lion_pwconv_split_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout, int L,
                               const float *pro_a, const float *pro_b, float *y, float *stats, lionStream_t stream);
+/* The FIRST layer of a set-abstraction MLP straight from the ungrouped tensors: lion_group_points_forward followed by
+ * lion_pwconv_forward / lion_pwconv_split_forward (no prologue) without the [B, 3 + C, M, U] tensor between them.
+ * coords f32[B,3,N], centers f32[B,3,M], feat f32[B,C,N] (NULL with C = 0), idx i32[B,M,U] (clamped to [0, N) as the
+ * grouping kernel clamps it); Cin = 3 + C, L = M * U.  The operand of column (m, u) and channel k is
+ * coords[b,k,idx[b,m,u]] - centers[b,k,m] for k < 3 (one IEEE subtraction) and feat[b,k-3,idx[b,m,u]] beyond.  wp, bias,
+ * y f32[B,Cout,M,U] and stats (sized by lion_pwconv_stat_tiles / lion_pwconv_split_stat_tiles for (Cout, Cin, L)) as in
+ * the ungrouped call; same kernels, tiles and k order: y and stats are bit-identical to the two calls. */
+int lion_pwconv_grouped_forward(const float *coords, const float *centers, const float *feat, const int32_t *idx,
+                                const float *wp, const float *bias, int B, int C, int N, int M, int U, int Cout, float *y,
+                                float *stats, lionStream_t stream);
+int lion_pwconv_split_grouped_forward(const float *coords, const float *centers, const float *feat, const int32_t *idx,
+                                      const uint16_t *wp, const float *bias, int B, int C, int N, int M, int U, int Cout,
+                                      float *y, float *stats, lionStream_t stream);
 /* ---- P5: LinearAttention (models/pvcnn2_ada.py:43-71) between its two 1x1 convolutions ---------------------
  * qkv f32[B, 3*H*D, N] (to_qkv's output, channel order (qkv, head, d)) -> out f32[B, H*D, N] (to_out's input):
  * softmax over the N points of every k row, ctx = softmax(k) v^T (D x D), out = ctx^T q.  D = 32 (every

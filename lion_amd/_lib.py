@@ -92,6 +92,8 @@ SIGNATURES = {
     "lion_pwconv_split_pack_weights_t": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "lion_pwconv_split_stat_tiles": (_i, [_i, _i, _i]),
     "lion_pwconv_split_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lion_pwconv_grouped_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "lion_pwconv_split_grouped_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lion_linear_attention_core": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "lion_linear_attention_core_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lion_linear_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),

@@ -88,6 +88,14 @@ template <typename F> static inline int lion_with_flags(bool a, bool b, F f) {
   return lion_with_flags(a, [&](auto A) { return lion_with_flags(b, [&](auto B) { return f(A, B); }); });
 }
 
+// The operand of a 1x1 convolution given as a neighbourhood gather instead of a tensor (pwconv.hip / pwconv_split.hip, the
+// *_grouped_forward entry points): what lion_group_points_forward would have written into [B, 3 + C, M, U].
+struct PwGather {
+  const float *coords, *centers, *feat; // f32[B,3,N], f32[B,3,M], f32[B,C,N] or NULL (C = 0)
+  const int32_t *idx;                   // i32[B,M,U]
+  int C, N, U;
+};
+
 // Parity-critical float arithmetic: one IEEE rounding per operation, never contracted into
 // an FMA, exactly like the -ffp-contract=off oracle.  (The whole library is also compiled with
 // -ffp-contract=off; the intrinsics make the intent explicit at the call sites that matter.)

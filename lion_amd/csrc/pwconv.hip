@@ -32,14 +32,30 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // ymax f32[B, CoutY, L / 32] (passed as y).  The last layer of a set-abstraction MLP is evaluated twice this way (sums,
 // fold, then activated maximum) and its [B, 64, 1024, 32] = 268 MB output never exists: 134 MB read twice instead of
 // 134 MB read + 268 MB written + 268 MB read.
-template <int CB, int VB, bool PRO, bool STATS, bool WLDS, int OUT = 0>
+// GRP (the first layer of a set-abstraction MLP, lion_pwconv_grouped_forward): the activation is not a tensor but the
+// neighbourhood gather BallQuery.forward would have materialised -- column (m, u) of channel k is
+// coords[b, k, idx[b, m, u]] - centers[b, k, m] for k < 3 (ONE IEEE subtraction, as grouping_fwd_kernel) and
+// feat[b, k - 3, idx[b, m, u]] beyond.  A lane reads the (clamped) index of each of its columns once, before the k loop,
+// and the operand loads become gathers from rows of N floats that stay in L2; the [B, 3 + C, M, U] tensor (147 MB at SA-0)
+// is neither written nor read.  Same tiles, same k order, same epilogue: y and the sums are those of the two-kernel path,
+// bit for bit.  The flag is a trailing parameter pack -- empty for the plain kernels, which keep their names, parameters
+// and code (tools/isa_identical.py), PwGather (common.h) for the gathered form.  The pack is copied into a local `g` at
+// the top of both kernels: here that leaves the plain instantiations' code as it was.  In pwconv_split.hip the same local
+// changed their code (the LDS transposition of the epilogue was scheduled differently), so that kernel names the pack
+// only inside its `if constexpr (GRP)` block.
+__device__ __forceinline__ PwGather pw_gather() { return PwGather{}; }
+__device__ __forceinline__ PwGather pw_gather(const PwGather &g) { return g; }
+template <int CB, int VB, bool PRO, bool STATS, bool WLDS, int OUT = 0, typename... G>
 __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict__ x, const float *__restrict__ wp,
                                                         const float *__restrict__ bias, float *__restrict__ y,
                                                         int Cin, int Cout, int CoutY, int L,
                                                         const float *__restrict__ pro_a,
                                                         const float *__restrict__ pro_b, float *__restrict__ stats,
                                                         const float *__restrict__ out_a = nullptr,
-                                                        const float *__restrict__ out_b = nullptr) {
+                                                        const float *__restrict__ out_b = nullptr, G... gather) {
+  constexpr bool GRP = sizeof...(G) > 0; // pwconv_kernel<..., PwGather>: x is not read
+  static_assert(!(GRP && (PRO || OUT)), "the gathered operand is a first layer: no prologue, stored output");
+  [[maybe_unused]] const PwGather g = pw_gather(gather...);
   // Cout: channels of the packed weights (a multiple of 32, zero rows beyond CoutY); CoutY: channels of y / bias / stats
   constexpr int COUT = CB * 32; // output channels of this workgroup: [co0, co0 + COUT)
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -89,6 +105,25 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
       for (int i = 0; i < 16; ++i) acc[cb][vb][i] = 0.f;
 
   const float *xb = x + (size_t)b * Cin * L;
+  // GRP: index and centre of every column of this lane (the centre rows a lane meets are row kh in k-step 0 and, for
+  // kh = 0, row 2 in k-step 1); the clamped column keeps all three reads inside their tensors
+  int gi[GRP ? VB : 1];
+  float gc0[GRP ? VB : 1], gc1[GRP ? VB : 1];
+  const float *gcb = nullptr, *gfb = nullptr;
+  int gfr = 0;
+  if constexpr (GRP) {
+    const int M = L / g.U;
+    gcb = g.coords + (size_t)b * 3 * g.N;
+    gfb = g.feat ? g.feat + (size_t)b * g.C * g.N : gcb; // no features: the (masked) rows past Cin read coordinates
+    gfr = g.feat ? g.C - 1 : 0;
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) {
+      const int m = col[vb] / g.U;
+      gc0[vb] = g.centers[((size_t)b * 3 + kh) * M + m];
+      gc1[vb] = g.centers[((size_t)b * 3 + 2) * M + m];
+      gi[vb] = min(max(g.idx[(size_t)b * L + col[vb]], 0), g.N - 1);
+    }
+  }
   // The activation operand of a whole group of UN k-steps (all of K when Cin <= 2 UN) is requested
   // before the first MFMA: these layers are bound by the activation bytes, so what matters is bytes in
   // flight per CU (UN x VB x 256 B per wave), not MFMA issue.  Weights come from LDS just in time.
@@ -98,8 +133,15 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int kc = min(2 * (s0 + u) + kh, Cin - 1);
+      if constexpr (GRP) { // rows 0..2 (k-steps 0 and 1 only) are coordinates, the rest features
+        const float *row = gfb + (size_t)min(max(kc - 3, 0), gfr) * g.N;
+        if (u < 2) row = kc < 3 ? gcb + (size_t)kc * g.N : row;
 #pragma unroll
-      for (int vb = 0; vb < VB; ++vb) bv[u][vb] = xb[(size_t)kc * L + col[vb]];
+        for (int vb = 0; vb < VB; ++vb) bv[u][vb] = row[gi[vb]];
+      } else {
+#pragma unroll
+        for (int vb = 0; vb < VB; ++vb) bv[u][vb] = xb[(size_t)kc * L + col[vb]];
+      }
     }
     // Round 4: the prologue of the WHOLE group first, the MFMAs afterwards.  Interleaved per operand (rounds 1-3) every
     // pair of MFMAs sat behind its own dependent chain -- LDS read of the scalars, fma, v_exp, v_rcp, mul, select (the
@@ -115,6 +157,12 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
         const float pa_ = spa[kc], pb_ = spb[kc];
 #pragma unroll
         for (int vb = 0; vb < VB; ++vb) bv[u][vb] = swish_fast(bv[u][vb] * pa_ + pb_);
+      }
+      if constexpr (GRP) {
+        if (u < 2) {
+#pragma unroll
+          for (int vb = 0; vb < VB; ++vb) bv[u][vb] = k < 3 ? sub_rn(bv[u][vb], u == 0 ? gc0[vb] : gc1[vb]) : bv[u][vb];
+        }
       }
 #pragma unroll
       for (int vb = 0; vb < VB; ++vb) {
@@ -217,12 +265,16 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
 // each) before the first MFMA -- one round trip -- and the four partial tiles are combined through LDS in a fixed
 // order.  Same arithmetic (fmaf chains over k, then ((w0 + w1) + w2) + w3), prologue and GroupNorm sums as above.
 constexpr int PW_SMALL_L = 4096;
-template <bool PRO, bool STATS>
+template <bool PRO, bool STATS, typename... G>
 __global__ __launch_bounds__(256) void pwconv_small_kernel(const float *__restrict__ x, const float *__restrict__ wp,
                                                            const float *__restrict__ bias, float *__restrict__ y,
                                                            int Cin, int Cout, int CoutY, int L,
                                                            const float *__restrict__ pro_a,
-                                                           const float *__restrict__ pro_b, float *__restrict__ stats) {
+                                                           const float *__restrict__ pro_b, float *__restrict__ stats,
+                                                           G... gather) {
+  constexpr bool GRP = sizeof...(G) > 0; // as in pwconv_kernel
+  static_assert(!(GRP && PRO), "the gathered operand is a first layer: no prologue");
+  [[maybe_unused]] const PwGather g = pw_gather(gather...);
   __shared__ float part[4][2][1024];
   extern __shared__ __attribute__((aligned(16))) float smem[]; // [2][Cin] prologue scalars (PRO)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cl = lane & 31, kh = lane >> 5;
@@ -240,6 +292,19 @@ __global__ __launch_bounds__(256) void pwconv_small_kernel(const float *__restri
 #pragma unroll
   for (int j = 0; j < 8; ++j) brow[j] = (bias && co0 + (tid >> 5) + 8 * j < CoutY) ? bias[co0 + (tid >> 5) + 8 * j] : 0.f;
   const float *xb = x + (size_t)b * Cin * L;
+  int gi = 0; // GRP: as in pwconv_kernel -- index and centre of this lane's column, gathers in place of the row reads
+  float gc0 = 0.f, gc1 = 0.f;
+  const float *gcb = nullptr, *gfb = nullptr;
+  int gfr = 0;
+  if constexpr (GRP) {
+    const int M = L / g.U, m = colc / g.U;
+    gcb = g.coords + (size_t)b * 3 * g.N;
+    gfb = g.feat ? g.feat + (size_t)b * g.C * g.N : gcb;
+    gfr = g.feat ? g.C - 1 : 0;
+    gc0 = g.centers[((size_t)b * 3 + kh) * M + m];
+    gc1 = g.centers[((size_t)b * 3 + 2) * M + m];
+    gi = min(max(g.idx[(size_t)b * L + colc], 0), g.N - 1);
+  }
   f32x16 acc[2];
 #pragma unroll
   for (int cb = 0; cb < 2; ++cb)
@@ -253,7 +318,13 @@ __global__ __launch_bounds__(256) void pwconv_small_kernel(const float *__restri
       const int k = min(2 * min(s0 + u, ksteps - 1) + kh, 2 * ksteps - 1); // packed rows exist up to ceil2(Cin)
       av[u][0] = wp[(size_t)k * Cout + co0 + cl];
       av[u][1] = wp[(size_t)k * Cout + co0 + 32 + cl];
-      bv[u] = xb[(size_t)min(k, Cin - 1) * L + colc];
+      if constexpr (GRP) {
+        const int kc = min(k, Cin - 1);
+        const float *row = kc < 3 ? gcb + (size_t)kc * g.N : gfb + (size_t)min(max(kc - 3, 0), gfr) * g.N;
+        bv[u] = row[gi];
+      } else {
+        bv[u] = xb[(size_t)min(k, Cin - 1) * L + colc];
+      }
     }
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
@@ -264,6 +335,7 @@ __global__ __launch_bounds__(256) void pwconv_small_kernel(const float *__restri
         const float t = v * spa[kc] + spb[kc];
         v = swish_fast(t); // as in pwconv_kernel
       }
+      if constexpr (GRP) v = k < 3 ? sub_rn(v, k == 2 ? gc1 : gc0) : v; // rows 0 / 1 are this lane's row kh
       v = (s0 + u < s_hi && k < Cin && cok) ? v : 0.f;
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][0], v, acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][1], v, acc[1], 0, 0, 0);
@@ -385,6 +457,20 @@ static int launch_pw(const float *x, const float *wp, const float *bias, float *
   });
 }
 
+// the gathered-operand form: launch_pw's grid, LDS and weights-through-LDS choice, no prologue
+template <int CB, int VB>
+static int launch_pw_grouped(const PwGather &g, const float *wp, const float *bias, float *y, int B, int Cin, int Cout, int L,
+                             float *stats, hipStream_t st) {
+  const int Cpad = pw_pad(Cout);
+  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
+  const bool wlds = (long)grid.x * B >= 2048;
+  const size_t lds = pw_lds(CB, Cin, false, wlds);
+  return lion_with_flags(stats != nullptr, wlds, [&](auto ST, auto WLDS) {
+    return lion_launch<pwconv_kernel<CB, VB, false, decltype(ST)::value, decltype(WLDS)::value, 0, PwGather>>(
+        grid, 256, lds, st, nullptr, wp, bias, y, Cin, pw_stride(Cout), Cout, L, nullptr, nullptr, stats, nullptr, nullptr, g);
+  });
+}
+
 // the two passes of the "activated maximum without the layer's output" form (OUT = 1, OUT = 2): large activations only
 // (weights through LDS), same tiling and the same column tiles of the statistics as launch_pw
 template <int CB, int VB>
@@ -471,6 +557,36 @@ int lion_pwconv_forward(const float *x, const float *wp, const float *bias, int 
   case 2: return launch_pw<2, 4>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
   case 4: return launch_pw<4, 2>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
   default: return launch_pw<8, 1>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+  }
+}
+
+// lion_group_points_forward followed by lion_pwconv_forward (no prologue) without the [B, 3 + C, M, U] tensor between them:
+// Cin = 3 + C, L = M * U, column (m, u) of channel k = coords[b,k,idx[b,m,u]] - centers[b,k,m] (k < 3) or
+// feat[b,k-3,idx[b,m,u]]; idx is clamped to [0, N) as the grouping kernel clamps it.  wp, bias, y, stats as
+// lion_pwconv_forward for (Cin, L); same kernels by the same rules, y and stats bit-identical to the two calls.
+int lion_pwconv_grouped_forward(const float *coords, const float *centers, const float *feat, const int32_t *idx,
+                                const float *wp, const float *bias, int B, int C, int N, int M, int U, int Cout, float *y,
+                                float *stats, lionStream_t stream) {
+  if (!coords || !centers || !idx || !wp || !y || B <= 0 || C < 0 || N <= 0 || M <= 0 || U <= 0 || Cout <= 0) return LION_EINVAL;
+  if (C > 0 && !feat) return LION_EINVAL;
+  if ((long)M * U >= (1L << 31) || (long)C * N >= (1L << 31)) return LION_EUNSUPPORTED;
+  const int Cin = 3 + C, L = M * U;
+  const PwGather g{coords, centers, C > 0 ? feat : nullptr, idx, C, N, U};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (L <= PW_SMALL_L) {
+    const dim3 grid(lion_cdiv(L, 32), pw_stride(Cout) / 64, B);
+    return lion_with_flags(stats != nullptr, [&](auto ST) {
+      return lion_launch<pwconv_small_kernel<false, decltype(ST)::value, PwGather>>(
+          grid, 256, 0, st, nullptr, wp, bias, y, Cin, pw_stride(Cout), Cout, L, nullptr, nullptr, stats, g);
+    });
+  }
+  const PwPlan p = pw_plan(Cout, Cin);
+  if (!p.cb) return LION_EUNSUPPORTED;
+  switch (p.cb) {
+  case 1: return launch_pw_grouped<1, 4>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
+  case 2: return launch_pw_grouped<2, 4>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
+  case 4: return launch_pw_grouped<4, 2>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
+  default: return launch_pw_grouped<8, 1>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
   }
 }
 

@@ -38,13 +38,25 @@ __device__ unsigned long long g_pws_t[128];
 #define PWS_T(i) do { } while (0)
 #endif
 
-template <int CB, int VB, bool PRO, bool STATS, int NR, bool WIDE>
+// GRP (lion_pwconv_split_grouped_forward, the first layer of a set-abstraction MLP): the activation is the neighbourhood
+// gather of PwGather (common.h) instead of a tensor.  It rides on the 4-byte path (WIDE = false), whose row loads already
+// are one dword per (lane, k): a lane reads the clamped index and the three centre coordinates of each of its columns once,
+// before the first chunk, and row k of a column comes from feat[b, k - 3, idx] -- rows 0..2, which only the kh = 0 lanes of
+// chunk 0 meet, from coords[b, k, idx], the centre subtracted (one IEEE operation) where the chunk is cut.  Same loads per
+// chunk (the vmcnt bookkeeping below is unchanged), same values in the same registers: y and stats are bit-identical to
+// lion_group_points_forward + this kernel.  The flag is a trailing parameter pack: empty for the plain kernels, which keep
+// their names, parameters and code (tools/isa_identical.py), PwGather for the gathered form.
+__device__ __forceinline__ const PwGather &pws_gather(const PwGather &g) { return g; }
+template <int CB, int VB, bool PRO, bool STATS, int NR, bool WIDE, typename... G>
 __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__restrict__ x, const u4 *__restrict__ wp,
                                                            const float *__restrict__ wtail,
                                                            const float *__restrict__ bias, float *__restrict__ y,
                                                            int Cin, int Cpad, int CoutY, int L,
                                                            const float *__restrict__ pro_a,
-                                                           const float *__restrict__ pro_b, float *__restrict__ stats) {
+                                                           const float *__restrict__ pro_b, float *__restrict__ stats,
+                                                           G... gather) {
+  constexpr bool GRP = sizeof...(G) > 0; // pwconv_split_kernel<..., PwGather>: x is not read
+  static_assert(!(GRP && (WIDE || PRO)), "the gathered operand uses the 4-byte path and has no prologue");
   constexpr int COT = 32 * CB, WPL = 4 * COT;        // u4 per chunk slice: [piece][k-half][COT]
   constexpr int NDMA = WPL / 64, DMIN = NDMA / 4;    // wave instructions per slice; at least DMIN by every wave
   constexpr int XROW = 128 * VB;                     // WIDE: floats per activation row of a ring slot
@@ -79,8 +91,30 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
     cok[vb] = col < L;
     colc[vb] = cok[vb] ? col : L - 1; // clamped load, zeroed afterwards
   }
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(x + (size_t)b * Cin * L), 0, Cin * L * 4, 0x00020000);
+  // GRP: index and centre of every column of this lane; the clamped column keeps the reads inside idx and centers, the
+  // clamped index inside a row of coords / feat.  Requested here, ahead of the accumulator set-up and the first slices.
+  int gi[GRP ? VB : 1];
+  float gct[GRP ? VB : 1][3];
+  const float *gcb = nullptr, *gfb = nullptr;
+  int gfr = 0, gN = 0;
+  if constexpr (GRP) { // (the pack is only named here: a PwGather local as in pwconv.hip changes the plain instantiations' code)
+    const PwGather &g = pws_gather(gather...);
+    const int M = L / g.U;
+    gN = g.N;
+    gcb = g.coords + (size_t)b * 3 * g.N;
+    gfb = g.feat ? g.feat + (size_t)b * g.C * g.N : gcb; // no features: the (masked) rows past Cin read coordinates
+    gfr = g.feat ? g.C - 1 : 2;                          // last row of that slice
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) {
+      const int m = colc[vb] / g.U;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) gct[vb][j] = g.centers[((size_t)b * 3 + j) * M + m];
+      gi[vb] = min(max(g.idx[(size_t)b * L + colc[vb]], 0), g.N - 1);
+    }
+  }
+  const __amdgpu_buffer_rsrc_t xrs = GRP
+      ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(gfb), 0, (gfr + 1) * gN * 4, 0x00020000)
+      : __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x + (size_t)b * Cin * L), 0, Cin * L * 4, 0x00020000);
   typedef __attribute__((address_space(3))) unsigned char lds_byte;
   const uint32_t sw_lds = (uint32_t)(uintptr_t)(lds_byte *)reinterpret_cast<unsigned char *>(sw);
   auto weights_dma = [&](int q) { // slice of chunk q -> ring slot q % NR; lane-linear element e = (plane, channel)
@@ -127,6 +161,25 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
   auto issue_x = [&](int q, float (&v)[VB][8]) {
     // byte offset of row 16 q + 8 kh + j, column colc: rows past Cin lie past num_records of this batch entry's slice and
     // read as 0 (the range check covers the VGPR offset); one add per load
+    if constexpr (GRP) {
+      // row k of the gathered operand is row k - 3 of the feature slice (clamped to its last row past Cin: masked where
+      // the chunk is cut), still one add per load; j < 3 can be a coordinate row (chunk 0, kh = 0): a per-lane pointer
+      const int r0 = q * KS + kh * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int fo = min(max(r0 + j - 3, 0), gfr) * gN * 4;
+        if (j < 3) {
+          const float *row = r0 + j < 3 ? gcb + (size_t)(r0 + j) * gN : gfb + (fo >> 2);
+#pragma unroll
+          for (int vb = 0; vb < VB; ++vb) v[vb][j] = row[gi[vb]];
+        } else {
+#pragma unroll
+          for (int vb = 0; vb < VB; ++vb)
+            v[vb][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, fo + gi[vb] * 4, 0, 0));
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int vb = 0; vb < VB; ++vb) {
       const int off0 = ((q * KS + kh * 8) * L + colc[vb]) * 4;
@@ -200,6 +253,9 @@ __global__ __launch_bounds__(256, 2) void pwconv_split_kernel(const float *__res
       for (int j = 0; j < 8; ++j) {
         float u = v[vb][j];
         if (PRO) u = pro_act(u, pa[j], pb[j]);
+        if constexpr (GRP) {
+          if (j < 3) u = q * KS + kh * 8 + j < 3 ? sub_rn(u, gct[vb][j]) : u; // a coordinate row: relative to the centre
+        }
         u = (q * KS + kh * 8 + j < Cin && cok[vb]) ? u : 0.f;
         t[j] = u;
         const unsigned a = __float_as_uint(u) & 0x7fffffffu; // inf / nan do not set the scale, they pass through the cut
@@ -399,6 +455,14 @@ __global__ void pw_split_pack_kernel(const float *__restrict__ w, int Cout, int 
 #ifndef PWS_NR_W12
 #define PWS_NR_W12 2
 #endif
+// ring depth of the gathered-operand instantiations (4-byte path: the rows of D chunks wait in registers).  <2, 2> at
+// depth 5 spills 60 bytes per lane (ScratchSize of the -S listing); at depth 4 it takes 254 registers and none
+#ifndef PWS_NR_G
+#define PWS_NR_G PWS_NR
+#endif
+#ifndef PWS_NR_G22
+#define PWS_NR_G22 4
+#endif
 struct PwSplitPlan { int cb, vb; };
 static int pws_pad(int Cout) { return (Cout + 31) / 32 * 32; }
 static PwSplitPlan pws_plan(int Cout) {
@@ -420,6 +484,20 @@ static int launch_pws(const float *x, const u4 *wp, const float *wtail, const fl
   return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
     return lion_launch<pwconv_split_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, NR, WIDE>>(
         grid, 256, lds, st, x, wp, wtail, bias, y, Cin, Cpad, Cout, L, pa, pb, stats);
+  });
+}
+
+// the gathered-operand form: launch_pws's grid and LDS for the 4-byte path, no prologue
+template <int CB, int VB, int NR>
+static int launch_pws_grouped(const PwGather &g, const u4 *wp, const float *wtail, const float *bias, float *y, int B, int Cin,
+                              int Cout, int L, float *stats, hipStream_t st) {
+  const int Cpad = pws_pad(Cout);
+  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
+  const size_t ring = (size_t)NR * (4 * CB * 32 * 16), tile = (size_t)4 * 32 * 36 * 4;
+  const size_t lds = (ring > tile ? ring : tile) + (size_t)(CB * 32 + 8 * CB * 32 * 2) * 4;
+  return lion_with_flags(stats != nullptr, [&](auto ST) {
+    return lion_launch<pwconv_split_kernel<CB, VB, false, decltype(ST)::value, NR, false, PwGather>>(
+        grid, 256, lds, st, nullptr, wp, wtail, bias, y, Cin, Cpad, Cout, L, nullptr, nullptr, stats, g);
   });
 }
 
@@ -494,6 +572,29 @@ int lion_pwconv_split_forward(const float *x, const uint16_t *wp, const float *b
   case 4: return launch_pws<4, 1, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
   case 2: return launch_pws<2, 2, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
   case 1: return launch_pws<1, 2, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
+  default: return LION_EUNSUPPORTED;
+  }
+}
+
+// lion_group_points_forward followed by lion_pwconv_split_forward (no prologue) without the [B, 3 + C, M, U] tensor between
+// them: Cin = 3 + C, L = M * U, the operand of column (m, u) and channel k as lion_pwconv_grouped_forward defines it.  wp,
+// bias, y, stats as lion_pwconv_split_forward for (Cin, L); y and stats bit-identical to the two calls.
+int lion_pwconv_split_grouped_forward(const float *coords, const float *centers, const float *feat, const int32_t *idx,
+                                      const uint16_t *wp, const float *bias, int B, int C, int N, int M, int U, int Cout,
+                                      float *y, float *stats, lionStream_t stream) {
+  if (!coords || !centers || !idx || !wp || !y || B <= 0 || C < 0 || N <= 0 || M <= 0 || U <= 0 || Cout <= 0) return LION_EINVAL;
+  if (C > 0 && !feat) return LION_EINVAL;
+  const long Cin_l = 3L + C, L_l = (long)M * U;
+  if (Cin_l * L_l >= (1L << 29) || Cin_l > 4096 || Cin_l * N >= (1L << 29)) return LION_EUNSUPPORTED; // 32-bit byte offsets
+  const int Cin = (int)Cin_l, L = (int)L_l;
+  const PwGather g{coords, centers, C > 0 ? feat : nullptr, idx, C, N, U};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const u4 *w4 = reinterpret_cast<const u4 *>(wp);
+  const float *wtail = reinterpret_cast<const float *>(wp + pws_halfs(Cout, Cin));
+  switch (pws_plan(Cout).cb) {
+  case 4: return launch_pws_grouped<4, 1, PWS_NR_G>(g, w4, wtail, bias, y, B, Cin, Cout, L, stats, st);
+  case 2: return launch_pws_grouped<2, 2, PWS_NR_G22>(g, w4, wtail, bias, y, B, Cin, Cout, L, stats, st);
+  case 1: return launch_pws_grouped<1, 2, PWS_NR_G>(g, w4, wtail, bias, y, B, Cin, Cout, L, stats, st);
   default: return LION_EUNSUPPORTED;
   }
 }

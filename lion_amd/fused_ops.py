@@ -367,6 +367,55 @@ def group_points(coords, centers, feat, idx):
     return out
 
 
+class GroupedPoints:
+    """What BallQuery.forward groups, not yet grouped: (coords [B,3,N], centers [B,3,M], feat [B,C,N] | None, idx [B,M,U])
+    standing for the [B, 3 + C, M, U] tensor group_points would write.  The first layer of a set-abstraction MLP gathers
+    its operand from these (pwconv_grouped_fused); every other consumer calls materialize()."""
+
+    def __init__(self, coords, centers, feat, idx):
+        self.coords, self.centers, self.feat, self.idx = coords, centers, feat, idx
+        c = 0 if feat is None else feat.shape[1]
+        self.shape = (coords.shape[0], 3 + c, idx.shape[1], idx.shape[2])
+
+    def materialize(self):
+        return group_points(self.coords, self.centers, self.feat, self.idx)
+
+
+def pw_grouped_supported(conv, gp):
+    """the first layer `conv` can read the grouped view `gp` directly: pw_supported's conditions for the tensor gp stands
+    for, and fp32 features.  No shape is excluded: at B = 32 every stage of the local prior gains (us, group_points + first
+    layer -> gathered: 112.5 -> 60.9, 75.5 -> 60.9, 36.1 -> 22.1, 27.9 -> 19.9; profiles/pw_grouped_ab.txt), so there is no
+    per-stage table."""
+    b, cin, m, u = gp.shape
+    L = m * u
+    co = gp.coords
+    return (PW_ALL and conv.in_channels == cin and conv.groups == 1 and all(k == 1 for k in conv.kernel_size)
+            and all(s == 1 for s in conv.stride) and all(p == 0 for p in conv.padding)
+            and co.is_cuda and co.dtype == torch.float32 and (gp.feat is None or gp.feat.dtype == torch.float32) and L > 0
+            and cin * co.shape[2] < (1 << 29)
+            and _lib.load().lion_pwconv_stat_tiles(conv.out_channels, cin, L) > 0)
+
+
+def pwconv_grouped_fused(gp, conv, want_stats=True):
+    """pwconv_fused(gp.materialize(), conv) without the grouped tensor: the kernel gathers its operand through gp.idx
+    (lion_pwconv_grouped_forward / lion_pwconv_split_grouped_forward).  Same routing as pwconv_fused takes for this
+    (B, Cin, Cout, L), same kernels: y [B,Cout,M,U] and the tile sums are bit-identical."""
+    lib = _lib.load()
+    b, cin, m, u = gp.shape
+    L = m * u
+    cout = conv.out_channels
+    use_split = pw_use_split(None, b, cin, cout, L)
+    wp = _PW_SPLIT_CACHE.get(conv.weight) if use_split else pw_packed_weight(conv.weight)
+    y = torch.empty((b, cout, m, u), device=gp.coords.device, dtype=torch.float32)
+    tiles = (lib.lion_pwconv_split_stat_tiles if use_split else lib.lion_pwconv_stat_tiles)(cout, cin, L)
+    stats = torch.empty((b, cout, tiles, 2), device=y.device, dtype=torch.float32) if want_stats else None
+    bias = conv.bias.detach().contiguous() if conv.bias is not None else None
+    _lib.call("lion_pwconv_split_grouped_forward" if use_split else "lion_pwconv_grouped_forward",
+              gp.coords.contiguous(), gp.centers.contiguous(), None if gp.feat is None else gp.feat.contiguous(),
+              gp.idx.contiguous(), wp, bias, b, cin - 3, gp.coords.shape[2], m, u, cout, y, stats)
+    return y, stats
+
+
 def linear_rows(x, weight, bias=None, act=0, slope=0.0):
     """nn.Linear on [B, K]: act(x W^T + b) in ONE launch on the fp32 MFMA kernel (lion_linear_forward);
     act 0 none / 1 relu / 2 leaky-relu(slope)."""
@@ -426,6 +475,14 @@ def shared_mlp(x, convs, adagns, style, reduce_max=False, add=None):
     apply pass (optionally with the max over the neighbourhood)."""
     pro = None
     for li, (conv, gn) in enumerate(zip(convs, adagns)):
+        if isinstance(x, GroupedPoints):   # BallQuery's view (pvcnn2_ada.SA_GATHER): the first layer gathers, or nobody does
+            if li == 0 and pw_grouped_supported(conv, x) and not (MAX_RECOMPUTE and len(convs) == 1):
+                x, st = pwconv_grouped_fused(x, conv)
+                f, g = gn.affine(style)
+                A, Bs, _ = groupnorm_fold(st, gn.norm, f, g, x[0, 0].numel())
+                pro = (A, Bs)
+                continue
+            x = x.materialize()
         if (MAX_RECOMPUTE and reduce_max and add is None and li == len(convs) - 1 and x.dim() == 4 and x.shape[3] == 32
                 and pw_supported(conv, x)
                 and not pw_use_split(None, x.shape[0], x.shape[1], conv.out_channels, x[0, 0].numel())):

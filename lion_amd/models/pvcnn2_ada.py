@@ -44,6 +44,9 @@ SKIP_UNREAD = os.environ.get("LION_CONV_SKIP_UNREAD", "1") != "0"
 SKIP_UNREAD_LEVEL2 = os.environ.get("LION_CONV_SKIP_UNREAD_LEVEL2", "1") != "0"   # A/B: 0 = conv1 still stores the empty tiles conv2's halos touch
 OCC_CLONE = os.environ.get("LION_OCC_CLONE", "0") != "0"     # A/B switch: 1 = a copy of the occupancy buffers per convolution (libraries before round 5)
 DEVOX_PLAN = os.environ.get("LION_DEVOX_PLAN", "1") != "0"   # A/B switch: 0 = every r = 32 devoxelisation redoes its per-cloud setup
+# the first layer of a set-abstraction MLP gathers its neighbourhoods itself (fused_ops.pwconv_grouped_fused): BallQuery hands
+# it a view (fused_ops.GroupedPoints) and the [B, 3 + C, M, U] tensor is neither written nor read back; 0 = group_points
+SA_GATHER = os.environ.get("LION_SA_GATHER", "1") != "0"
 
 
 @contextlib.contextmanager
@@ -174,14 +177,18 @@ class BallQuery(nn.Module):
         self.num_neighbors = num_neighbors
         self.include_coordinates = include_coordinates
 
-    def forward(self, points_coords, centers_coords, points_features=None):
+    def forward(self, points_coords, centers_coords, points_features=None, grouped_view=False):
+        """grouped_view (a caller that hands the result to SharedMLP._run): with SA_GATHER on the own-kernel inference path
+        the result is a fused_ops.GroupedPoints -- the operands of the gather, not the gathered tensor."""
         with torch.autocast("cuda", enabled=False):
             points_coords = points_coords.float().contiguous()
             centers_coords = centers_coords.float().contiguous()
             neighbor_indices = F.ball_query(centers_coords, points_coords, self.radius, self.num_neighbors)
             if own_kernels(points_coords) and self.include_coordinates and points_coords.shape[1] == 3 \
                     and (points_features is None or points_features.dtype == torch.float32):
-                # inference: relative coordinates and features written straight into one [B, 3 + C, M, U] tensor
+                if grouped_view and SA_GATHER:
+                    return fused_ops.GroupedPoints(points_coords, centers_coords, points_features, neighbor_indices)
+                # relative coordinates and features written straight into one [B, 3 + C, M, U] tensor
                 return fused_ops.group_points(points_coords, centers_coords, points_features, neighbor_indices)
             neighbor_coordinates = F.grouping(points_coords, neighbor_indices)
             neighbor_coordinates = neighbor_coordinates - centers_coords.unsqueeze(-1)
@@ -309,7 +316,9 @@ class SharedMLP(nn.Module):
         """reduce_max: additionally take the max over the last dimension (the SA modules' pooling,
         reference :375-377), fused into the last layer's activation pass on the inference path; add: a tensor summed
         onto the output (PVConv's voxel features), in that same pass on the inference path."""
-        if self._fusable(x):
+        if isinstance(x, fused_ops.GroupedPoints) and not self._fusable(x.coords):
+            x = x.materialize()
+        if self._fusable(x if torch.is_tensor(x) else x.coords):
             n = len(self.layers) // 3
             convs, gns = [self.layers[3 * i] for i in range(n)], [self.layers[3 * i + 1] for i in range(n)]
             return fused_ops.shared_mlp(x, convs, gns, style, reduce_max, add=add)
@@ -557,7 +566,7 @@ class PointNetSAModule(nn.Module):
         S = centers_coords.shape[-1]
         if time_emb is not None and type(time_emb) is not dict:
             time_emb = time_emb[:, :, :S]
-        pooled = [mlp.forward_max(grouper(coords, centers_coords, features), style)
+        pooled = [mlp.forward_max(grouper(coords, centers_coords, features, grouped_view=True), style)
                   for grouper, mlp in zip(self.groupers, self.mlps)]
         out = torch.cat(pooled, dim=1) if len(pooled) > 1 else pooled[0]
         return out, centers_coords, time_emb, style
