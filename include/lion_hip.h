@@ -222,6 +222,25 @@ int lion_chain_begin_step_temb(const float *table, int n_steps, int32_t *counter
                                const float *temb_table, int temb_width, float *temb_out, lionStream_t stream);
 int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
                                const uint32_t *seed, uint32_t stream_id, float *out, float *z_out, lionStream_t stream);
+/* DPM-Solver++(2M) (Lu, Zhou, Bao, Chen, Li, Zhu 2022, Algorithm 2), the second-order multistep solver of the probability-flow
+ * ODE in data-prediction form: one step t -> n over numel floats, every written operation rounded once (no fma):
+ *   x0  = a0*(x - a1*eps)                          a0 = 1/alpha_t, a1 = sigma_t: the model's data prediction
+ *   D   = a5 == 0 ? a4*x0 : a4*x0 + a5*hist        a4 = 1 + 1/(2r), a5 = -1/(2r), hist = the previous step's x0
+ *   out = a2*x + a3*D                              a2 = sigma_n/sigma_t, a3 = -alpha_n*expm1(-h)
+ *   hist_out = x0
+ * hist is NOT read when a5 == 0 (first step, order 1, last step).  out may alias x and hist_out may alias hist.  No noise.
+ * lion_dpmpp_update takes the coefficients by value (hist may be NULL when a5 == 0); lion_chain_update_multistep reads
+ * them from cur[1..6] in device memory, as lion_chain_begin_step leaves them -- the last launch of a captured step;
+ * lion_chain_update_multistep_cm is that update on x / hist / out / hist_out f32[B][N][4] and the denoiser's channel-major
+ * eps_cm f32[B][4][N], as lion_chain_update_noise_cm reads them.
+ * LION_EINVAL before any launch: a NULL pointer (but hist, as said), numel == 0 / B <= 0 / N <= 0, or x, eps, hist, out or
+ * hist_out not 16-byte aligned (eps_cm is read element by element and may have any alignment). */
+int lion_dpmpp_update(const float *x, const float *eps, const float *hist, size_t numel, float a0, float a1, float a2,
+                      float a3, float a4, float a5, float *out, float *hist_out, lionStream_t stream);
+int lion_chain_update_multistep(const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
+                                float *out, float *hist_out, lionStream_t stream);
+int lion_chain_update_multistep_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
+                                   float *out, float *hist_out, lionStream_t stream);
 /* The forward-process draw that starts a chain at an intermediate step (diffuse-denoise; sample_q of
  * utils/diffusion_pvd.py:105-113 with the scalars of iw_quantities_t :44-103):
  *   out = (m*x0) + (s*z)        two products and one sum, each rounded once (no fma)

@@ -139,6 +139,9 @@ SIGNATURES = {
     "lion_chain_begin_step_temb": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "lion_chain_update_noise_cm": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "lion_chain_diffuse": (_i, [_vp, _vp, _sz, _f, _f, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "lion_dpmpp_update": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "lion_chain_update_multistep": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "lion_chain_update_multistep_cm": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_latent_unpack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_concat_broadcast": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lion_three_nn_interpolate_cat_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

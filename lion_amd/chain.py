@@ -4,7 +4,7 @@
 One denoiser evaluation of the local prior is ~500 kernel launches; the reference's samplers
 (utils/diffusion_pvd.py:224-303, :390-473) additionally issue ~10 elementwise launches, a ``torch.full`` and a
 host-side ``randn`` + H2D copy per step.  Here a captured step holds
-    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise
+    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise   (DPMPP: lion_chain_update_multistep)
 and a chain of S steps is S replays of it.  Two things live here, apart:
   * ``CapturedStep``: warm-up, capture and replay of ANY step given as a callable -- the one capture path of the package
     (this chain, ode.OdeGraph, graph.GraphedDenoiser).  One hipGraph for models without set abstraction (the global prior);
@@ -26,6 +26,9 @@ import torch
 from . import _lib, _wcache
 
 DDIM, DDPM = 0, 1
+# the deterministic multistep solver DPM-Solver++(2M) (DiffusionDiscretized.run_dpm_solver): the captured step ends with
+# lion_chain_update_multistep instead of lion_chain_update_noise, and the chain also owns `hist`, the previous step's data prediction
+DPMPP = 2
 # tests: a list here makes every chain run append (start latent, [the noise each step drew]) -- what an eager loop needs
 # to repeat a graphed chain draw for draw (run_ddim(given_noise=...)); chains are then captured with the noise output on
 RECORD = None
@@ -216,8 +219,10 @@ class GraphedChain:
         self.seed = torch.zeros(2, dtype=torch.int32, device=dev)   # two 32-bit words of the Philox key
         self.cur = torch.zeros(8, device=dev)
         self.z = torch.zeros(size, device=dev) if record_noise else None   # tests: the noise each step used
+        self.hist = torch.zeros(size, device=dev) if mode == DPMPP else None   # the previous step's data prediction
         # identity rows until run() uploads a schedule: the warm-up / capture passes must run on finite values (an
-        # all-zero DDPM row is 0/0 -> the second warm-up forward would voxelize NaN latents)
+        # all-zero DDPM row is 0/0 -> the second warm-up forward would voxelize NaN latents).  For the multistep update the
+        # same row is x0 = x, D = 0, out = x.
         self.table[:, 0] = 1.0   # t_model
         self.table[:, 1] = 1.0   # a0: x passes through
         self.table[:, 3] = 1.0   # a2: DDPM divisor (DDIM: z has weight 1 -- finite)
@@ -247,10 +252,17 @@ class GraphedChain:
                 eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, channel_major_out=True,
                             **extra).float().contiguous()
                 assert tuple(eps.shape) == (num_samples, n_cls, n_pts)
+                if mode == DPMPP:
+                    _lib.call("lion_chain_update_multistep_cm", self.x, eps, self.hist, num_samples, n_pts, self.cur, self.x,
+                              self.hist)
+                    return
                 _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
                           self.z)
                 return
             eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **extra).float().contiguous()
+            if mode == DPMPP:
+                _lib.call("lion_chain_update_multistep", self.x, eps, self.hist, self.x.numel(), self.cur, self.x, self.hist)
+                return
             _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
 
@@ -300,6 +312,8 @@ class GraphedChain:
             self.temb_table[:S].copy_(self.model.time_embedding(self.table[:S, 0].contiguous()))
             self.model.train(was_training)
         self.counter.zero_()
+        if self.hist is not None:
+            self.hist.zero_()
         words = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
         self.seed.copy_(torch.from_numpy(words))
         return S

@@ -150,6 +150,66 @@ static int update_noise_launch(int mode, unsigned blocks, hipStream_t st, const 
                                                          cm_points);
 }
 
+// DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2) in data-prediction form, one rounding per written operation:
+//   x0 = a0*(x - a1*eps);   D = a5 == 0 ? a4*x0 : a4*x0 + a5*hist;   out = a2*x + a3*D;   hist_out = x0
+// (a = {1/alpha_t, sigma_t, sigma_n/sigma_t, -alpha_n*expm1(-h), 1 + 1/(2r), -1/(2r)}).  The coefficients come from cur[1..6]
+// in device memory where `cur` is given (the captured step), else from the by-value copies (the eager loop).  hist is NOT read
+// when a5 == 0 (first step, order 1, last step): it may then be NULL or hold anything.  No noise.  cm_points as in
+// update_noise_kernel.  The tensors are not __restrict__: out may alias x and hist_out may alias hist (a lane reads its quad of
+// both before it writes either, no lane reads another's).
+__global__ void multistep_kernel(const float *x, const float *eps, const float *hist, size_t numel,
+                                 const float *__restrict__ cur, float a0, float a1, float a2, float a3, float a4, float a5,
+                                 float *out, float *hist_out, int cm_points) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = q * 4;
+  if (i >= numel) return;
+  if (cur) { a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; a3 = cur[4]; a4 = cur[5]; a5 = cur[6]; }
+  const bool second = a5 != 0.f;
+  float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, o[4], p[4];
+  const bool full = i + 3 < numel;
+  if (full) {
+    const float4 t = *reinterpret_cast<const float4 *>(x + i);
+    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+    if (second) {
+      const float4 h = *reinterpret_cast<const float4 *>(hist + i);
+      hv[0] = h.x; hv[1] = h.y; hv[2] = h.z; hv[3] = h.w;
+    }
+  } else {
+    for (int j = 0; j < 4; ++j) { xv[j] = i + j < numel ? x[i + j] : 0.f; hv[j] = second && i + j < numel ? hist[i + j] : 0.f; }
+  }
+  if (cm_points) {   // numel = B*N*4: every quad is full; eps is the denoiser's channel-major [B][4][N]
+    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
+  } else if (full) {
+    const float4 u = *reinterpret_cast<const float4 *>(eps + i);
+    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
+  } else {
+    for (int j = 0; j < 4; ++j) ev[j] = i + j < numel ? eps[i + j] : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    p[j] = mul_rn(a0, sub_rn(xv[j], mul_rn(a1, ev[j])));
+    float d = mul_rn(a4, p[j]);
+    if (second) d = add_rn(d, mul_rn(a5, hv[j]));
+    o[j] = add_rn(mul_rn(a2, xv[j]), mul_rn(a3, d));
+  }
+  if (full) {
+    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4 *>(hist_out + i) = make_float4(p[0], p[1], p[2], p[3]);
+  } else {
+    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; hist_out[i + j] = p[j]; }
+  }
+}
+
+static int multistep_launch(hipStream_t st, const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
+                            const float a[6], float *out, float *hist_out, int cm_points) {
+  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
+  if (blocks > 0x7fffffffu) return LION_EINVAL;
+  return lion_launch<multistep_kernel>((unsigned)blocks, 256, 0, st, x, eps, hist, numel, cur, a[0], a[1], a[2], a[3], a[4],
+                                       a[5], out, hist_out, cm_points);
+}
+
 // Forward-process draw out = m*x0 + s*z (sample_q, utils/diffusion_pvd.py:105-113) with the chain's generator: quad q of the
 // flat tensor takes Philox counter (q, LION_DIFFUSE_STEP_WORD, stream_id), whatever the pointers' alignment.  VEC: every pointer
 // is 16-byte aligned -> one 16-byte access per operand and full quad; else (and in the tail quad) element by element.
@@ -247,6 +307,33 @@ int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, in
   const unsigned blocks = (unsigned)((quads + 255) / 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return update_noise_launch(mode, blocks, st, x, eps_cm, numel, cur, seed, stream_id, out, z_out, N);
+}
+
+int lion_dpmpp_update(const float *x, const float *eps, const float *hist, size_t numel, float a0, float a1, float a2,
+                      float a3, float a4, float a5, float *out, float *hist_out, lionStream_t stream) {
+  if (!x || !eps || !out || !hist_out || numel == 0) return LION_EINVAL;
+  if (!hist && a5 != 0.f) return LION_EINVAL;
+  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0)
+    return LION_EINVAL;
+  const float a[6] = {a0, a1, a2, a3, a4, a5};
+  return multistep_launch(static_cast<hipStream_t>(stream), x, eps, hist, numel, nullptr, a, out, hist_out, 0);
+}
+
+int lion_chain_update_multistep(const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
+                                float *out, float *hist_out, lionStream_t stream) {
+  if (!x || !eps || !hist || !cur || !out || !hist_out || numel == 0) return LION_EINVAL;
+  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0)
+    return LION_EINVAL;
+  const float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return multistep_launch(static_cast<hipStream_t>(stream), x, eps, hist, numel, cur, a, out, hist_out, 0);
+}
+
+int lion_chain_update_multistep_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
+                                   float *out, float *hist_out, lionStream_t stream) {
+  if (!x || !eps_cm || !hist || !cur || !out || !hist_out || B <= 0 || N <= 0) return LION_EINVAL;
+  if (((((uintptr_t)x) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0) return LION_EINVAL;
+  const float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return multistep_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, (size_t)B * N * 4, cur, a, out, hist_out, N);
 }
 
 int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s, const uint32_t *seed,

@@ -198,6 +198,77 @@ class DiffusionDiscretized(object):
             table[i] = (t + 1, k_outer, k_a, k_b, scale, temp, 1.0 if is0 else 0.0, 0.0)
         return table
 
+    # ---- DPM-Solver++(2M): schedule and coefficients (float64 on the widened float32 schedule, cast once) ----------------
+    def _half_logsnr(self):
+        """lambda[i] = log(alpha_i / sigma_i) = 0.5*(log(ab_i) - log1p(-ab_i)) in float64, with ab widened from float32"""
+        ab = self._h_alpha_bars.numpy().astype(np.float64)
+        return ab, 0.5 * (np.log(ab) - np.log1p(-ab))
+
+    def solver_schedule(self, S, skip_type='logsnr'):
+        """Descending list of DISTINCT schedule indices for run_dpm_solver: starts at T-1 (S >= 2), ends at 0; S == 1 gives
+        [0], as ddim_schedule does.  The list may be SHORTER than S: duplicates are removed, since a step of zero length has
+        h = 0 and no second-order ratio.
+        'logsnr' (default): S points uniform in the half log-SNR lambda from lambda[T-1] to lambda[0], each mapped to the
+        nearest index.  This is the spacing the multistep solver is built for: its error terms are powers of the lambda step
+        h, and with 'uniform' index spacing the last jump (to t = 0) is so large in lambda that the second-order step is no
+        better than DDIM there (measured ratios 0.6 ... 2.8 against 5.5 ... 21 with 'logsnr').
+        'uniform' / 'quad': ddim_schedule(T, S, skip_type) with duplicates removed; where its largest entry falls short of
+        T-1 ('quad' stops at 0.8*T; 'uniform' where the floor rounds down) that entry is moved up to T-1, the index whose
+        marginal the N(0, I) start is drawn for.  Any other string: ValueError."""
+        T, S = self._diffusion_steps, int(S)
+        if skip_type not in ('logsnr', 'uniform', 'quad'):
+            raise ValueError(f"solver_schedule: unknown skip_type {skip_type!r}")
+        if S < 1:
+            raise ValueError(f"solver_schedule: S = {S}")
+        if S == 1:
+            return [0]
+        if skip_type == 'logsnr':
+            _, lam = self._half_logsnr()
+            tau = [int(np.argmin(np.abs(lam - p))) for p in np.linspace(lam[T - 1], lam[0], S)]
+        else:
+            tau = self.ddim_schedule(T, S, skip_type)
+        tau = sorted(set(tau), reverse=True)
+        if tau[0] != T - 1:
+            tau[0] = T - 1
+        if tau[-1] != 0:
+            tau.append(0)
+        return tau
+
+    def dpm_solver_table(self, steps, order=2, dtype=np.float32):
+        """[len(steps), 8] rows {t_model, a0..a5, 0} of DPM-Solver++ (Lu et al. 2022, Algorithm 2; order 1 is DDIM with
+        kappa = 0) over the descending distinct indices `steps`, the last of which is 0 -- what lion_dpmpp_update and the
+        captured chain (chain.DPMPP) read:  x0 = a0*(x - a1*eps);  D = a4*x0 + a5*x0_prev;  x <- a2*x + a3*D.
+        With alpha = sqrt(ab), sigma = sqrt(1 - ab), lambda = log(alpha/sigma), and for the step t = steps[i] -> n = steps[i+1]
+        h_i = lambda[n] - lambda[t]:  a0 = 1/alpha_t, a1 = sigma_t, a2 = sigma_n/sigma_t, a3 = -alpha_n*expm1(-h_i);
+        (a4, a5) = (1, 0) for i == 0 or order 1, else (1 + 1/(2r), -1/(2r)) with r = h_{i-1}/h_i.
+        The last row (t = 0) returns the data prediction, like DDIM's alpha_next = 1: a2 = 0, a3 = 1, a4 = 1, a5 = 0.
+        All arithmetic in float64 on the float32 schedule widened; the result is cast to `dtype` once (float64: the values
+        before the cast)."""
+        if order not in (1, 2):
+            raise ValueError(f"dpm_solver_table: order = {order!r}, must be 1 or 2")
+        steps = [int(t) for t in steps]
+        assert len(steps) >= 1 and steps[-1] == 0, "the last step is t = 0"
+        assert all(a > b for a, b in zip(steps, steps[1:])), "descending distinct indices"
+        ab, lam = self._half_logsnr()
+        alpha, sigma = np.sqrt(ab), np.sqrt(1.0 - ab)
+        table = np.zeros((len(steps), 8), np.float64)
+        h_prev = None
+        for i, t in enumerate(steps):
+            table[i, :3] = (t + 1, 1.0 / alpha[t], sigma[t])
+            if i == len(steps) - 1:
+                table[i, 3:7] = (0.0, 1.0, 1.0, 0.0)
+                break
+            n = steps[i + 1]
+            h = lam[n] - lam[t]
+            table[i, 3:5] = (sigma[n] / sigma[t], -alpha[n] * np.expm1(-h))
+            if i == 0 or order == 1:
+                table[i, 5:7] = (1.0, 0.0)
+            else:
+                r = h_prev / h
+                table[i, 5:7] = (1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r))
+            h_prev = h
+        return table.astype(dtype)
+
     def _noise(self, size, source, device):
         if source == 'cpu':  # the reference's stream: torch.randn(size).to(device), :465-466
             return torch.randn(size).to(device)
@@ -402,3 +473,57 @@ class DiffusionDiscretized(object):
                 output_list.append(x_noisy)
         model.train()
         return x_noisy, output_list
+
+    @torch.no_grad()
+    def run_dpm_solver(self, model, num_samples, shape, steps=20, order=2, skip_type='logsnr', x_noisy=None,
+                       condition_input=None, clip_feat=None, enable_autocast=False, keep_trajectory=True, graph=True,
+                       state_hook=None, conv_precision="fp32"):
+        """Deterministic few-step sampling with DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2): the second-order multistep
+        solver of the probability-flow ODE that run_ddim(kappa=0) integrates to first order.  At most ``steps`` model
+        evaluations (solver_schedule removes duplicate indices), one per visited index of
+        ``solver_schedule(steps, skip_type)``; coefficients from ``dpm_solver_table``; ``order=1`` is DDIM with kappa = 0.
+        skip_type='logsnr' (default) spaces the indices uniformly in log-SNR: with 'uniform' index spacing the last
+        jump in lambda is so large that the second-order step is no better than DDIM.
+        No noise enters after the start (x_noisy, or N(0, I) drawn on the device), so one start gives one result.
+        Returns (x, output_list): output_list the state after every step (empty with keep_trajectory=False).
+        graph=True: S replays of one captured step [prologue -> denoiser -> lion_chain_update_multistep], the latent and
+        the previous data prediction in device memory (chain.DPMPP; a cache entry of its own beside the DDIM / DDPM
+        captures of the same model).  Otherwise -- graph=False, mixed_prediction models, autocast -- the eager per-step loop
+        on lion_dpmpp_update; from the same start the two give the same bits.
+        state_hook(i, x) and conv_precision: as in run_ddim."""
+        with conv_ops.requested_precision(conv_precision):
+            return self._run_dpm_solver(model, num_samples, shape, steps, order, skip_type, x_noisy, condition_input, clip_feat,
+                                        enable_autocast, keep_trajectory, graph, state_hook)
+
+    def _run_dpm_solver(self, model, num_samples, shape, steps, order, skip_type, x_noisy, condition_input, clip_feat,
+                        enable_autocast, keep_trajectory, graph, state_hook):
+        taus = self.solver_schedule(steps, skip_type)
+        table = self.dpm_solver_table(taus, order)
+        model.eval()
+        dev = self.device
+        size = [num_samples] + list(shape)
+        if x_noisy is None:
+            x_noisy = torch.randn(size=size, device=dev)
+        x_noisy = x_noisy.to(dev).contiguous()
+        output_list = []
+        if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
+            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DPMPP,
+                                  self._diffusion_steps)
+            x = ch.run(x_noisy, table, 0, condition_input, clip_feat, trajectory=output_list if keep_trajectory else None,
+                       state_hook=state_hook)   # seed 0: this step draws nothing
+            model.train()
+            return x, output_list
+        x, hist = x_noisy.clone(), None     # the hook may overwrite the latent in place: never the caller's tensor
+        for i, t in enumerate(taus):
+            if state_hook is not None:
+                state_hook(i, x)
+            timestep = torch.full((num_samples,), t + 1, dtype=torch.int64, device=dev)
+            mixing = self.get_mixing_component(x, timestep, enabled=getattr(model, 'mixed_prediction', False))
+            with torch.autocast("cuda", enabled=enable_autocast):
+                pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat)
+                eps_hat = _mixed(model, pred, mixing).float().contiguous()
+            x, hist = diffusion_ops.dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:7]])
+            if keep_trajectory:
+                output_list.append(x)
+        model.train()
+        return x, output_list

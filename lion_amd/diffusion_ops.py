@@ -1,11 +1,11 @@
-"""Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, and the forward-process
-draw lion_chain_diffuse."""
+"""Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, the multistep solver
+step lion_dpmpp_update, and the forward-process draw lion_chain_diffuse."""
 import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["ddim_update", "ddpm_update", "diffuse"]
+__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "diffuse"]
 
 
 def ddim_update(x, eps, z, s, c, sigma, out=None):
@@ -36,6 +36,20 @@ def diffuse(x0, m, s, noise=None, seed=None, stream_id=1, out=None, return_noise
     _lib.call("lion_chain_diffuse", x0, noise, x0.numel(), float(m), float(s),
               None if noise is not None else seed_words(int(seed), x0.device), int(stream_id), out, z_out)
     return (out, z_out) if return_noise else out
+
+
+def dpmpp_update(x, eps, hist, a0, a1, a2, a3, a4, a5, out=None, hist_out=None):
+    """One DPM-Solver++(2M) step (lion_dpmpp_update; coefficients: DiffusionDiscretized.dpm_solver_table):
+    x0 = a0*(x - a1*eps);  D = a4*x0 (+ a5*hist where a5 != 0);  out = a2*x + a3*D;  hist_out = x0.  hist, the previous step's
+    x0, is not read when a5 == 0 and may then be None.  out may be x and hist_out may be hist.  Returns (out, hist_out)."""
+    _lib.require_cuda(x, eps, hist, out, hist_out)
+    if hist is None and float(a5) != 0.0:
+        raise ValueError("dpmpp_update: a second-order row (a5 != 0) needs hist")
+    out = torch.empty_like(x) if out is None else out
+    hist_out = torch.empty_like(x) if hist_out is None else hist_out
+    _lib.call("lion_dpmpp_update", x, eps, hist, x.numel(), float(a0), float(a1), float(a2), float(a3), float(a4), float(a5),
+              out, hist_out)
+    return out, hist_out
 
 
 def ddpm_update(x, eps, z, t_is_zero, k_outer, k_a, k_b, scale, temp, out=None):

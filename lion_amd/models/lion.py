@@ -74,10 +74,12 @@ class LION(object):
         print(f'INFO finish loading from {model_path}')
 
     @torch.no_grad()
-    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32"):
+    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32", dpm_step=0):
         """1000 ancestral steps of the global prior, 1000 of the local prior, one decode
         (reference :38-80).  conv_precision="half": the priors' voxel convolutions run at reduced precision
-        (conv_ops.PRECISION); the decode stays fp32-accurate."""
+        (conv_ops.PRECISION); the decode stays fp32-accurate.
+        dpm_step > 0: both priors run DPM-Solver++(2M) with at most dpm_step evaluations instead of the ancestral steps
+        (DiffusionDiscretized.run_dpm_solver); the default is the reference's chain."""
         self.priors.eval()
         self.vae.eval()
         self.scheduler.set_timesteps(self.diffusion._diffusion_steps, device=self.device)
@@ -90,9 +92,13 @@ class LION(object):
                                 (local_prior, latent_shape[1], 'z_local')):
             # the reference's loop (:55-70: prior forward + scheduler.step per timestep) as one graphed chain:
             # the scheduler's mean / variance rule feeds the chain's coefficient table (lion_amd/chain.py)
-            x, _ = self.diffusion.run_denoising_diffusion(
-                prior, num_samples, shp, condition_input=condition_input, clip_feat=clip_feat,
-                keep_trajectory=False, noise_scale=self.scheduler._noise_scale, conv_precision=conv_precision)
+            if dpm_step > 0:
+                x, _ = self.diffusion.run_dpm_solver(prior, num_samples, shp, steps=dpm_step, condition_input=condition_input,
+                                                     clip_feat=clip_feat, keep_trajectory=False, conv_precision=conv_precision)
+            else:
+                x, _ = self.diffusion.run_denoising_diffusion(
+                    prior, num_samples, shp, condition_input=condition_input, clip_feat=clip_feat,
+                    keep_trajectory=False, noise_scale=self.scheduler._noise_scale, conv_precision=conv_precision)
             prior.eval()
             sampled.append(x)
             output_dict[key] = x
