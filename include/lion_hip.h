@@ -471,6 +471,15 @@ int lion_pwconv_grouped_forward(const float *coords, const float *centers, const
 int lion_pwconv_split_grouped_forward(const float *coords, const float *centers, const float *feat, const int32_t *idx,
                                       const uint16_t *wp, const float *bias, int B, int C, int N, int M, int U, int Cout,
                                       float *y, float *stats, lionStream_t stream);
+/* For tests only: the fp32 kernel of lion_pwconv_forward / lion_pwconv_forward_max / lion_pwconv_grouped_forward at ANY L
+ * (never the short-activation kernel), with at most max_wg workgroups per (sample, channel tile) walking the column tiles
+ * (<= 0: the library's own cap) and the weights through LDS (lds_weights 1), from L2 (0) or by the library's rule (< 0).
+ * idx != NULL: the gathered operand (x unused, Cin = 3 + C, feat NULL when Cin = 3, L = M * U); out_a != NULL: the second
+ * pass of the max form (y = ymax f32[B,Cout,L/32]); y == NULL: its first pass (sums only); otherwise y is stored. */
+int lion_internal_pwconv_walk(const float *x, const float *wp, const float *bias, int B, int Cin, int Cout, int L,
+                              const float *pro_a, const float *pro_b, const float *out_a, const float *out_b,
+                              const float *coords, const float *centers, const float *feat, const int32_t *idx, int N, int U,
+                              float *y, float *stats, int max_wg, int lds_weights, lionStream_t stream);
 /* ---- P5: LinearAttention (models/pvcnn2_ada.py:43-71) between its two 1x1 convolutions ---------------------
  * qkv f32[B, 3*H*D, N] (to_qkv's output, channel order (qkv, head, d)) -> out f32[B, H*D, N] (to_out's input):
  * softmax over the N points of every k row, ctx = softmax(k) v^T (D x D), out = ctx^T q.  D = 32 (every

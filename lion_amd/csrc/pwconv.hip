@@ -13,9 +13,11 @@
 // 128-byte coalesced stores of the [B, Cout, L] layout.  The previous layer's AdaGN + Swish is
 // applied to the operand in flight (PRO), this layer's GroupNorm sums leave with the epilogue
 // (STATS: per (batch, channel, column tile) sum and sum of squares, folded by lion_groupnorm_fold).
-// A wave owns VB x 32 columns x all Cout channels (CB = Cout / 32 row blocks); the weights (k-major
-// packed copy [ceil2(Cin)][Cout]) are staged once per workgroup in LDS.
+// A wave owns VB x 32 columns x all Cout channels (CB = Cout / 32 row blocks) of a column tile; the weights (k-major
+// packed copy [ceil2(Cin)][Cout]) are staged once per workgroup in LDS, and the workgroup walks several column tiles
+// with the operand loads one group of k-steps ahead of the MFMAs (round 7, see "the schedule" in the kernel).
 #include "common.h"
+#include <algorithm>
 
 namespace {
 
@@ -87,15 +89,31 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
     }
   }
   __syncthreads();
-  const int col0 = (blockIdx.x * 4 + wave) * VB * 32;
-  int col[VB];
-  bool cok[VB];
-#pragma unroll
-  for (int vb = 0; vb < VB; ++vb) {
-    col[vb] = col0 + vb * 32 + cl;
-    cok[vb] = col[vb] < L;
-    col[vb] = cok[vb] ? col[vb] : L - 1; // clamped load, select afterwards
-  }
+  // ---- the schedule (round 7): a walk over column tiles with the operand one group ahead -------------------------------
+  // Until round 6 a wave owned ONE column tile: it requested the activation of 64 / VB k-steps (64 loads), waited once, ran
+  // the prologue batch and 128 MFMAs, stored, and ended; the 8 waves of a CU started together and walked those phases in
+  // step, so loads, MFMAs and stores added up instead of overlapping, and every tile paid a workgroup's start (weights into
+  // LDS, the scalars, a barrier, the first load from a standing start).  Now
+  //  * the workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its (sample, channel tile): the staging is
+  //    paid once, and the assignment is static -- no queue, no atomics, nothing read that another workgroup wrote;
+  //  * the items (tile, group of GN = 32 / VB k-steps) form one stream and the operand loads of item i + 1, gathers
+  //    included, are issued BEFORE the MFMA sweep of item i: `raw` (32 registers) is in flight while `bv` (32, the
+  //    prologue's results) feeds the matrix pipe.  At the end of a tile item i + 1 is the first group of the NEXT tile, so
+  //    the epilogue's stores and reductions run under loads in flight.  Weights that come from L2 are issued behind their
+  //    own item's operand and ahead of that request where a group of them fits 16 registers (WPRE: CB <= 2); for CB = 4 / 8
+  //    they are read inside the sweep as before, behind the request.
+  // What the compiler's wait placement leaves: the paths with and without an epilogue meet at the loop head, so the wait
+  // for `raw` there is vmcnt(0) and a wave drains its stores before the next tile's first MFMA (peeling the first tile would
+  // lift that; not done).
+  // Loads stay countable: the request of the next item is issued on every path, for the item after the last as well (tile
+  // and k clamped to the last valid ones; nothing uses the result).  The arithmetic per column is what it was: ascending
+  // k, the same prologue expression, bias add and reduction trees; the sums go to the TILE's slot of [B, CoutY, tiles, 2].
+  constexpr int TILE = 4 * VB * 32; // columns of a workgroup's tile
+  constexpr int GN = 32 / VB;       // k-steps of a group
+  constexpr bool WPRE = !WLDS && CB * GN <= 16; // weights from L2 in registers: a group of them is issued ahead of the
+                                                // next item's request (loads return in order: behind it they would wait for it)
+  const int tiles = (L + TILE - 1) / TILE;
+  const int lc0 = wave * VB * 32 + cl; // this lane's first column inside a tile
   f32x16 acc[CB][VB];
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb)
@@ -104,54 +122,120 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[cb][vb][i] = 0.f;
 
+  // Addresses: a uniform row pointer (scalar registers) + a 32-bit byte offset per lane (the launchers keep L and N below
+  // PW_MAX_L, so (4 kh L + column) * 4 fits) -- one offset register per column block instead of a 64-bit pointer per load.
   const float *xb = x + (size_t)b * Cin * L;
-  // GRP: index and centre of every column of this lane (the centre rows a lane meets are row kh in k-step 0 and, for
-  // kh = 0, row 2 in k-step 1); the clamped column keeps all three reads inside their tensors
-  int gi[GRP ? VB : 1];
-  float gc0[GRP ? VB : 1], gc1[GRP ? VB : 1];
+  const unsigned khL4 = kh ? (unsigned)L * 4u : 0u; // byte offset of the k-half's row
+  // GRP: index as a byte offset (gi4: of the tile being loaded, gin: of the tile after it, fetched a tile ahead) and centre
+  // (rc0 / rc1: requested with the tile's first group; the centre rows a lane meets are row kh in k-step 0 and, for
+  // kh = 0, row 2 in k-step 1) of every column of this lane; the clamped column keeps all three reads inside their tensors
+  unsigned gi4[GRP ? VB : 1];
+  int gin[GRP ? VB : 1];
+  float rc0[GRP ? VB : 1], rc1[GRP ? VB : 1];
   const float *gcb = nullptr, *gfb = nullptr;
   int gfr = 0;
+  unsigned khN4 = 0;
+  float raw[GN][VB]; // the operand of the next item, in flight
+  // clamped columns of tile t (a tile past the last reads the last one's)
+  auto columns = [&](int t, int(&c)[VB]) {
+    const int base = min(t, tiles - 1) * TILE + lc0;
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) c[vb] = min(base + vb * 32, L - 1); // clamped load, select afterwards
+  };
+  [[maybe_unused]] auto request_idx = [&](int t) {
+    int c[VB];
+    columns(t, c);
+    const int32_t *ib = g.idx + (size_t)b * L;
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) gin[vb] = *(const int32_t *)((const char *)ib + (unsigned)c[vb] * 4u);
+  };
+  [[maybe_unused]] auto take_idx = [&]() {
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) gi4[vb] = (unsigned)min(max(gin[vb], 0), g.N - 1) * 4u;
+  };
+  // issue the loads of item (t, s0): GN k-steps from s0 of tile t.  Lane (kh, column) wants row min(2 (s0 + u) + kh, Cin - 1):
+  // the row of kh = 0, clamped, is the uniform base, and kh = 1 adds one row where that row exists.
+  auto request = [&](int t, int s0) {
+    int c[VB];
+    columns(t, c);
+    if constexpr (GRP) {
+      if (s0 == 0) { // uniform
+        const int M = L / g.U;
+#pragma unroll
+        for (int vb = 0; vb < VB; ++vb) {
+          const int m = c[vb] / g.U;
+          rc0[vb] = g.centers[((size_t)b * 3 + kh) * M + m];
+          rc1[vb] = g.centers[((size_t)b * 3 + 2) * M + m];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < GN; ++u) {
+      if constexpr (GRP) {
+        if (u < 2) { // may meet rows 0..2, the coordinates: a pointer per lane
+          const int kc = min(2 * (s0 + u) + kh, Cin - 1);
+          const float *row = gfb + (size_t)min(max(kc - 3, 0), gfr) * g.N;
+          row = kc < 3 ? gcb + (size_t)kc * g.N : row;
+#pragma unroll
+          for (int vb = 0; vb < VB; ++vb) raw[u][vb] = *(const float *)((const char *)row + gi4[vb]);
+        } else { // k >= 4: feature rows only
+          const int r0 = min(2 * (s0 + u) - 3, gfr);
+          const char *ub = (const char *)(gfb + (size_t)r0 * g.N);
+          const unsigned ho = r0 < gfr ? khN4 : 0u;
+#pragma unroll
+          for (int vb = 0; vb < VB; ++vb) raw[u][vb] = *(const float *)(ub + (gi4[vb] + ho));
+        }
+      } else {
+        const int r0 = min(2 * (s0 + u), Cin - 1);
+        const char *ub = (const char *)(xb + (size_t)r0 * L);
+        const unsigned ho = r0 + 1 < Cin ? khL4 : 0u;
+#pragma unroll
+        for (int vb = 0; vb < VB; ++vb) raw[u][vb] = *(const float *)(ub + ((unsigned)c[vb] * 4u + ho));
+      }
+    }
+  };
+
+  int t = blockIdx.x, s0 = 0;
   if constexpr (GRP) {
-    const int M = L / g.U;
     gcb = g.coords + (size_t)b * 3 * g.N;
     gfb = g.feat ? g.feat + (size_t)b * g.C * g.N : gcb; // no features: the (masked) rows past Cin read coordinates
     gfr = g.feat ? g.C - 1 : 0;
+    khN4 = kh ? (unsigned)g.N * 4u : 0u;
+    request_idx(t);
+    take_idx();
+  }
+  request(t, 0);
+  if constexpr (GRP) request_idx(t + gridDim.x);
+  while (t < tiles) { // uniform
+    const int col0 = t * TILE + wave * VB * 32;
+    int col[VB];
+    bool cok[VB];
 #pragma unroll
     for (int vb = 0; vb < VB; ++vb) {
-      const int m = col[vb] / g.U;
-      gc0[vb] = g.centers[((size_t)b * 3 + kh) * M + m];
-      gc1[vb] = g.centers[((size_t)b * 3 + 2) * M + m];
-      gi[vb] = min(max(g.idx[(size_t)b * L + col[vb]], 0), g.N - 1);
-    }
-  }
-  // The activation operand of a whole group of UN k-steps (all of K when Cin <= 2 UN) is requested
-  // before the first MFMA: these layers are bound by the activation bytes, so what matters is bytes in
-  // flight per CU (UN x VB x 256 B per wave), not MFMA issue.  Weights come from LDS just in time.
-  constexpr int UN = 64 / VB;
-  for (int s0 = 0; s0 < ksteps; s0 += UN) {
-    float bv[UN][VB];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int kc = min(2 * (s0 + u) + kh, Cin - 1);
-      if constexpr (GRP) { // rows 0..2 (k-steps 0 and 1 only) are coordinates, the rest features
-        const float *row = gfb + (size_t)min(max(kc - 3, 0), gfr) * g.N;
-        if (u < 2) row = kc < 3 ? gcb + (size_t)kc * g.N : row;
-#pragma unroll
-        for (int vb = 0; vb < VB; ++vb) bv[u][vb] = row[gi[vb]];
-      } else {
-#pragma unroll
-        for (int vb = 0; vb < VB; ++vb) bv[u][vb] = xb[(size_t)kc * L + col[vb]];
-      }
+      col[vb] = col0 + vb * 32 + cl;
+      cok[vb] = col[vb] < L;
     }
     // Round 4: the prologue of the WHOLE group first, the MFMAs afterwards.  Interleaved per operand (rounds 1-3) every
     // pair of MFMAs sat behind its own dependent chain -- LDS read of the scalars, fma, v_exp, v_rcp, mul, select (the
     // ISA: `ds_read x2, wait, v, wait, v v exp v rcp v v, MFMA MFMA` per (k-step, column block)) -- and the matrix pipe
     // ran at ~40 % of its rate inside a wave: SA-0 layer 2 took 108 us without storing a byte, 4x its MFMA time.  As one
-    // batch the 64 chains are independent and pipeline; the MFMA sweep that follows is back to back.
+    // batch the chains are independent and pipeline; the MFMA sweep that follows is back to back.
+    float bv[GN][VB];
+    [[maybe_unused]] float wv[WPRE ? GN : 1][WPRE ? CB : 1];
+    if constexpr (WPRE) { // this item's weights: behind its operand, ahead of the next item's
 #pragma unroll
-    for (int u = 0; u < UN; ++u) {
+      for (int u = 0; u < GN; ++u) {
+        const char *wb = (const char *)(wp + (size_t)min(2 * (s0 + u), 2 * ksteps - 2) * Cout + co0); // rows exist to ceil2(Cin)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) wv[u][cb] = *(const float *)(wb + ((kh ? (unsigned)Cout : 0u) + cb * 32 + cl) * 4u);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < GN; ++u) {
       const int k = 2 * (s0 + u) + kh;
       const bool kok = k < Cin; // odd Cin: zero operand (the packed weights are zero there too)
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb) bv[u][vb] = raw[u][vb];
       if (PRO) {
         const int kc = min(k, Cin - 1);
         const float pa_ = spa[kc], pb_ = spb[kc];
@@ -159,9 +243,9 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
         for (int vb = 0; vb < VB; ++vb) bv[u][vb] = swish_fast(bv[u][vb] * pa_ + pb_);
       }
       if constexpr (GRP) {
-        if (u < 2) {
+        if (u < 2) { // k < 3 only in the first group of a tile
 #pragma unroll
-          for (int vb = 0; vb < VB; ++vb) bv[u][vb] = k < 3 ? sub_rn(bv[u][vb], u == 0 ? gc0[vb] : gc1[vb]) : bv[u][vb];
+          for (int vb = 0; vb < VB; ++vb) bv[u][vb] = k < 3 ? sub_rn(bv[u][vb], u == 0 ? rc0[vb] : rc1[vb]) : bv[u][vb];
         }
       }
 #pragma unroll
@@ -170,15 +254,27 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
         asm volatile("" : "+v"(bv[u][vb])); // materialised HERE: left alone the compiler sinks each chain back in front of its MFMAs
       }
     }
+    // the next item: this tile's next group, or the first group of the workgroup's next tile
+    const bool last = s0 + GN >= ksteps;
+    const int tn = last ? t + (int)gridDim.x : t, sn = last ? 0 : s0 + GN;
+    if constexpr (GRP) {
+      if (last) take_idx();
+    }
+    request(tn, sn);
+    if constexpr (GRP) {
+      if (last) request_idx(tn + (int)gridDim.x);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int u = 0; u < UN; ++u) {
+    for (int u = 0; u < GN; ++u) {
       if (s0 + u < ksteps) { // uniform
         const int k = 2 * (s0 + u) + kh;
         float av[CB];
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-          av[cb] = WLDS ? sw[k * COUT + cb * 32 + cl] : wp[(size_t)k * Cout + co0 + cb * 32 + cl]; // rows exist to ceil2(Cin)
+        for (int cb = 0; cb < CB; ++cb) {
+          if constexpr (WPRE) av[cb] = wv[u][cb];
+          else av[cb] = WLDS ? sw[k * COUT + cb * 32 + cl] : wp[(size_t)k * Cout + co0 + cb * 32 + cl]; // rows exist to ceil2(Cin)
+        }
 #pragma unroll
         for (int vb = 0; vb < VB; ++vb) {
 #pragma unroll
@@ -187,71 +283,101 @@ __global__ __launch_bounds__(256, 2) void pwconv_kernel(const float *__restrict_
         }
       }
     }
-  }
-
-  // epilogue: + bias, [B, Cout, L] store.  acc register i of lane l: channel row (i&3) + 8*(i>>2) + 4*(l>>5),
-  // column l&31 -> 32 consecutive columns per (register, half-wave).
-  float *yb = y + ((size_t)b * CoutY + co0) * L;
-  if (OUT == 2) {
-    const int M = L >> 5; // centres: blocks of 32 columns (the launcher guarantees L % 32 == 0)
-    float *ym = y + ((size_t)b * CoutY + co0) * M;
+    if (last) { // uniform: the tile is complete
+      // epilogue: + bias, [B, Cout, L] store.  acc register i of lane l: channel row (i&3) + 8*(i>>2) + 4*(l>>5),
+      // column l&31 -> 32 consecutive columns per (register, half-wave).
+      if (OUT == 2) {
+        const int M = L >> 5; // centres: blocks of 32 columns (the launcher guarantees L % 32 == 0)
+        float *ym = y + ((size_t)b * CoutY + co0) * M;
+        unsigned mo[VB]; // byte offset of (row 4 kh, this column block's centre) from a row's uniform pointer
 #pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
+        for (int vb = 0; vb < VB; ++vb) mo[vb] = (unsigned)(4 * kh * M + ((col0 + vb * 32) >> 5)) * 4u;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int co = cb * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
-        const bool rok = co0 + co < CoutY;
-        const float bz = sbias[co], a2 = soa[co], b2 = sob[co];
+        for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-        for (int vb = 0; vb < VB; ++vb) {
-          float v = swish_fast((acc[cb][vb][i] + bz) * a2 + b2); // == affine_swish_max on the stored y, bit for bit
-          v = row16_max(v);                                       // max over the 32 columns of this half-wave:
-          v = fmaxf(v, LION_DPP_F32_ROWS(v, 0x142, 0xa));         // rows 1 / 3 take lane 15 of rows 0 / 2
-          const int m = (col0 + vb * 32) >> 5;
-          if (cl == 16 && rok && m < M) ym[(size_t)co * M + m] = v;
+          for (int i = 0; i < 16; ++i) {
+            const int cu = cb * 32 + (i & 3) + 8 * (i >> 2), co = cu + 4 * kh;
+            const bool rok = co0 + co < CoutY;
+            const float bz = sbias[co], a2 = soa[co], b2 = sob[co];
+            char *yr = (char *)(ym + (size_t)cu * M);
+#pragma unroll
+            for (int vb = 0; vb < VB; ++vb) {
+              float v = swish_fast((acc[cb][vb][i] + bz) * a2 + b2); // == affine_swish_max on the stored y, bit for bit
+              v = row16_max(v);                                       // max over the 32 columns of this half-wave:
+              v = fmaxf(v, LION_DPP_F32_ROWS(v, 0x142, 0xa));         // rows 1 / 3 take lane 15 of rows 0 / 2
+              const int m = (col0 + vb * 32) >> 5;
+              if (cl == 16 && rok && m < M) *(float *)(yr + mo[vb]) = v;
+            }
+          }
+      } else {
+        float *yb = y + ((size_t)b * CoutY + co0) * L;
+        unsigned so[VB]; // byte offset of (row 4 kh, this lane's column) from a row's uniform pointer
+#pragma unroll
+        for (int vb = 0; vb < VB; ++vb) so[vb] = khL4 * 4u + (unsigned)col[vb] * 4u;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const float bz = sbias[cb * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh];
+#pragma unroll
+            for (int vb = 0; vb < VB; ++vb) acc[cb][vb][i] = cok[vb] ? acc[cb][vb][i] + bz : 0.f;
+          }
+        if (OUT == 0) {
+          // a tile wholly inside [0, L) x [0, CoutY) -- all but the last of a ragged L, all but a padded Cout's last channel
+          // tile -- stores without a predicate: the general form costs a branch around every one of the 128 stores
+          auto store = [&](auto WHOLE) {
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+              for (int i = 0; i < 16; ++i) {
+                const int cu = cb * 32 + (i & 3) + 8 * (i >> 2);
+                const bool rok = co0 + cu + 4 * kh < CoutY; // padded channel rows (CoutY % 32 != 0) are computed on zeros and dropped
+                char *yr = (char *)(yb + (size_t)cu * L);
+#pragma unroll
+                for (int vb = 0; vb < VB; ++vb)
+                  if (decltype(WHOLE)::value || (cok[vb] && rok)) *(float *)(yr + so[vb]) = acc[cb][vb][i];
+              }
+          };
+          if ((t + 1) * TILE <= L && co0 + COUT <= CoutY) store(BoolC<true>{}); // uniform
+          else store(BoolC<false>{});
+        }
+        if (STATS) {
+#pragma unroll
+          for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+              for (int vb = 0; vb < VB; ++vb) { s1 += acc[cb][vb][i]; s2 += acc[cb][vb][i] * acc[cb][vb][i]; }
+              s1 = row16_sum_rn(s1); s2 = row16_sum_rn(s2);
+              s1 = row_pair_sum_odd_rows(s1); s2 = row_pair_sum_odd_rows(s2);
+              if (cl == 16) { // the row pair's sum lives in the odd rows
+                const int co = cb * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
+                sred[(wave * COUT + co) * 2] = s1;
+                sred[(wave * COUT + co) * 2 + 1] = s2;
+              }
+            }
+          __syncthreads();
+          for (int c = tid; c < COUT && co0 + c < CoutY; c += 256) {
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) { s1 += sred[(w * COUT + c) * 2]; s2 += sred[(w * COUT + c) * 2 + 1]; }
+            float *o = stats + (((size_t)b * CoutY + co0 + c) * tiles + t) * 2; // the TILE's slot, not the workgroup's
+            o[0] = s1;
+            o[1] = s2;
+          }
+          if (tn < tiles) __syncthreads(); // sred is written again by the next tile
         }
       }
-    return;
-  }
 #pragma unroll
-  for (int cb = 0; cb < CB; ++cb)
+      for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int co = cb * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
-      const bool rok = co0 + co < CoutY; // padded channel rows (CoutY % 32 != 0) are computed on zeros and dropped
-      const float bz = sbias[co];
+        for (int vb = 0; vb < VB; ++vb)
 #pragma unroll
-      for (int vb = 0; vb < VB; ++vb) {
-        const float o = acc[cb][vb][i] + bz;
-        acc[cb][vb][i] = cok[vb] ? o : 0.f;
-        if (OUT == 0 && cok[vb] && rok) yb[(size_t)co * L + col[vb]] = o;
-      }
+          for (int i = 0; i < 16; ++i) acc[cb][vb][i] = 0.f;
     }
-  if (STATS) {
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int vb = 0; vb < VB; ++vb) { s1 += acc[cb][vb][i]; s2 += acc[cb][vb][i] * acc[cb][vb][i]; }
-        s1 = row16_sum_rn(s1); s2 = row16_sum_rn(s2);
-        s1 = row_pair_sum_odd_rows(s1); s2 = row_pair_sum_odd_rows(s2);
-        if (cl == 16) { // the row pair's sum lives in the odd rows
-          const int co = cb * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh;
-          sred[(wave * COUT + co) * 2] = s1;
-          sred[(wave * COUT + co) * 2 + 1] = s2;
-        }
-      }
-    __syncthreads();
-    for (int c = tid; c < COUT && co0 + c < CoutY; c += 256) {
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) { s1 += sred[(w * COUT + c) * 2]; s2 += sred[(w * COUT + c) * 2 + 1]; }
-      float *o = stats + (((size_t)b * CoutY + co0 + c) * gridDim.x + blockIdx.x) * 2;
-      o[0] = s1;
-      o[1] = s2;
-    }
+    t = tn;
+    s0 = sn;
   }
 }
 
@@ -441,13 +567,31 @@ static PwPlan pw_plan(int Cout, int Cin) {
   return {0, 0};
 }
 
+// The grid of pwconv_kernel: `tiles` column tiles of a (sample, channel tile) are walked by gx <= tiles workgroups (tile
+// blockIdx.x + i gx each).  gx is capped so that the whole grid is about PW_WALK_WGS workgroups -- a few rounds of the two a CU
+// holds, so that the staging of a workgroup is paid once for several tiles and the next tile's loads fly under the
+// epilogue -- and then lowered to the smallest that keeps the longest walk as short: every workgroup gets cdiv(tiles, gx)
+// tiles or one fewer.  Results do not depend on gx: the sums are stored per tile.
+// PwSched: the test entry point's overrides (max_wg > 0: the cap itself; wlds 0 / 1: weights from L2 / through LDS
+// whatever the grid).
+constexpr int PW_WALK_WGS = 1024;
+// pwconv_kernel addresses a lane's element as a uniform row pointer + a 32-bit byte offset of up to 5 rows: L (and the N of
+// a gathered operand) stay below 2^27 columns -- 512 MiB per channel row.  Beyond: LION_EUNSUPPORTED, 0 statistics tiles.
+constexpr int PW_MAX_L = 1 << 27;
+struct PwSched { int max_wg = 0, wlds = -1; };
+static int pw_grid_x(int tiles, int gy, int B, const PwSched &o) {
+  const long cap = o.max_wg > 0 ? o.max_wg : std::max(1L, PW_WALK_WGS / ((long)gy * B));
+  const int walk = lion_cdiv(tiles, (int)std::min<long>(tiles, cap));
+  return lion_cdiv(tiles, walk);
+}
+
 template <int CB, int VB>
 static int launch_pw(const float *x, const float *wp, const float *bias, float *y, int B, int Cin, int Cout, int L,
-                     const float *pa, const float *pb, float *stats, hipStream_t st) {
-  const int Cpad = pw_pad(Cout);
-  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
+                     const float *pa, const float *pb, float *stats, hipStream_t st, const PwSched &o = {}) {
+  const int Cpad = pw_pad(Cout), tiles = lion_cdiv(L, 4 * VB * 32);
+  const dim3 grid(pw_grid_x(tiles, Cpad / (CB * 32), B, o), Cpad / (CB * 32), B);
   // weights through LDS only when a workgroup's column tile is one of many (the staging is then amortised by the L2)
-  const bool wlds = (long)grid.x * B >= 2048;
+  const bool wlds = o.wlds < 0 ? (long)tiles * B >= 2048 : o.wlds != 0;
   const size_t lds = pw_lds(CB, Cin, pa != nullptr, wlds);
   return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
     return lion_with_flags(wlds, [&](auto WLDS) {
@@ -460,10 +604,10 @@ static int launch_pw(const float *x, const float *wp, const float *bias, float *
 // the gathered-operand form: launch_pw's grid, LDS and weights-through-LDS choice, no prologue
 template <int CB, int VB>
 static int launch_pw_grouped(const PwGather &g, const float *wp, const float *bias, float *y, int B, int Cin, int Cout, int L,
-                             float *stats, hipStream_t st) {
-  const int Cpad = pw_pad(Cout);
-  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
-  const bool wlds = (long)grid.x * B >= 2048;
+                             float *stats, hipStream_t st, const PwSched &o = {}) {
+  const int Cpad = pw_pad(Cout), tiles = lion_cdiv(L, 4 * VB * 32);
+  const dim3 grid(pw_grid_x(tiles, Cpad / (CB * 32), B, o), Cpad / (CB * 32), B);
+  const bool wlds = o.wlds < 0 ? (long)tiles * B >= 2048 : o.wlds != 0;
   const size_t lds = pw_lds(CB, Cin, false, wlds);
   return lion_with_flags(stats != nullptr, wlds, [&](auto ST, auto WLDS) {
     return lion_launch<pwconv_kernel<CB, VB, false, decltype(ST)::value, decltype(WLDS)::value, 0, PwGather>>(
@@ -475,16 +619,20 @@ static int launch_pw_grouped(const PwGather &g, const float *wp, const float *bi
 // (weights through LDS), same tiling and the same column tiles of the statistics as launch_pw
 template <int CB, int VB>
 static int launch_pw_max(const float *x, const float *wp, const float *bias, float *ymax, int B, int Cin, int Cout, int L,
-                         const float *pa, const float *pb, float *stats, const float *oa, const float *ob, hipStream_t st) {
-  const int Cpad = pw_pad(Cout);
-  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
-  if ((long)grid.x * B < 2048) return LION_EUNSUPPORTED;
-  const size_t lds = pw_lds(CB, Cin, pa != nullptr, true);
+                         const float *pa, const float *pb, float *stats, const float *oa, const float *ob, hipStream_t st,
+                         const PwSched &o = {}) {
+  const int Cpad = pw_pad(Cout), tiles = lion_cdiv(L, 4 * VB * 32);
+  const dim3 grid(pw_grid_x(tiles, Cpad / (CB * 32), B, o), Cpad / (CB * 32), B);
+  if (o.wlds < 0 && (long)tiles * B < 2048) return LION_EUNSUPPORTED;
+  const bool wlds = o.wlds != 0;
+  const size_t lds = pw_lds(CB, Cin, pa != nullptr, wlds);
   // first pass (no out_a): OUT = 1 with the statistics; second pass: OUT = 2 without them
   return lion_with_flags(pa != nullptr, oa != nullptr, [&](auto PRO, auto SECOND) {
-    constexpr bool second = decltype(SECOND)::value;
-    return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, !second, true, second ? 2 : 1>>(
-        grid, 256, lds, st, x, wp, bias, ymax, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, oa, ob);
+    return lion_with_flags(wlds, [&](auto WLDS) {
+      constexpr bool second = decltype(SECOND)::value;
+      return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, !second, decltype(WLDS)::value, second ? 2 : 1>>(
+          grid, 256, lds, st, x, wp, bias, ymax, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, oa, ob);
+    });
   });
 }
 
@@ -503,7 +651,7 @@ int lion_pwconv_forward_max(const float *x, const float *wp, const float *bias, 
   if (!x || !wp || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0) return LION_EINVAL;
   if ((pro_a == nullptr) != (pro_b == nullptr) || (out_a == nullptr) != (out_b == nullptr)) return LION_EINVAL;
   if (out_a ? !ymax : !stats) return LION_EINVAL;
-  if (L % 32 != 0 || L <= PW_SMALL_L) return LION_EUNSUPPORTED;
+  if (L % 32 != 0 || L <= PW_SMALL_L || L >= PW_MAX_L) return LION_EUNSUPPORTED;
   const PwPlan p = pw_plan(Cout, Cin);
   if (!p.cb) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -528,7 +676,7 @@ int lion_pwconv_pack_weights(const float *w, int Cout, int Cin, float *wp, lionS
 int lion_pwconv_stat_tiles(int Cout, int Cin, int L) {
   if (L > 0 && L <= PW_SMALL_L && Cout > 0 && Cin > 0) return lion_cdiv(L, 32); // pwconv_small_kernel: 32-column tiles
   const PwPlan p = pw_plan(Cout, Cin);
-  return (p.cb && L > 0) ? lion_cdiv(L, 4 * p.vb * 32) : 0;
+  return (p.cb && L > 0 && L < PW_MAX_L) ? lion_cdiv(L, 4 * p.vb * 32) : 0;
 }
 
 // x f32[B,Cin,L], wp from lion_pwconv_pack_weights, bias f32[Cout] or NULL -> y f32[B,Cout,L];
@@ -551,7 +699,7 @@ int lion_pwconv_forward(const float *x, const float *wp, const float *bias, int 
     });
   }
   const PwPlan p = pw_plan(Cout, Cin);
-  if (!p.cb) return LION_EUNSUPPORTED;
+  if (!p.cb || L >= PW_MAX_L) return LION_EUNSUPPORTED;
   switch (p.cb) {
   case 1: return launch_pw<1, 4>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
   case 2: return launch_pw<2, 4>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
@@ -581,12 +729,48 @@ int lion_pwconv_grouped_forward(const float *coords, const float *centers, const
     });
   }
   const PwPlan p = pw_plan(Cout, Cin);
-  if (!p.cb) return LION_EUNSUPPORTED;
+  if (!p.cb || L >= PW_MAX_L || N >= PW_MAX_L) return LION_EUNSUPPORTED;
   switch (p.cb) {
   case 1: return launch_pw_grouped<1, 4>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
   case 2: return launch_pw_grouped<2, 4>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
   case 4: return launch_pw_grouped<4, 2>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
   default: return launch_pw_grouped<8, 1>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
+  }
+}
+
+// For tests only: pwconv_kernel itself at ANY L (the entry points above hand L <= 4096 to pwconv_small_kernel and refuse
+// the max form on small grids), with at most max_wg workgroups per (sample, channel tile) (<= 0: the library's cap) and
+// the weights through LDS (lds_weights 1), from L2 (0) or by the tiles * B >= 2048 rule (< 0): a few hundred columns then
+// walk several tiles.  idx != NULL: the gathered operand of lion_pwconv_grouped_forward (x unused, Cin = 3 + C, feat NULL
+// when Cin = 3, L = M * U); otherwise x as lion_pwconv_forward.  out_a != NULL: the second pass of
+// lion_pwconv_forward_max (y = ymax); y == NULL: its first pass (sums only); otherwise y is stored.
+int lion_internal_pwconv_walk(const float *x, const float *wp, const float *bias, int B, int Cin, int Cout, int L,
+                              const float *pro_a, const float *pro_b, const float *out_a, const float *out_b,
+                              const float *coords, const float *centers, const float *feat, const int32_t *idx, int N, int U,
+                              float *y, float *stats, int max_wg, int lds_weights, lionStream_t stream) {
+  if (!wp || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0) return LION_EINVAL;
+  if ((pro_a == nullptr) != (pro_b == nullptr) || (out_a == nullptr) != (out_b == nullptr)) return LION_EINVAL;
+  const bool grouped = idx != nullptr, maxform = out_a || !y;
+  if (out_a ? !y : (!y && !stats)) return LION_EINVAL;
+  if (grouped ? (!coords || !centers || N <= 0 || U <= 0 || L % U != 0 || Cin < 3 || (Cin > 3 && !feat) || pro_a || maxform) : !x)
+    return LION_EINVAL;
+  if ((maxform && L % 32 != 0) || L >= PW_MAX_L || (grouped && N >= PW_MAX_L)) return LION_EUNSUPPORTED;
+  const PwPlan p = pw_plan(Cout, Cin);
+  if (!p.cb) return LION_EUNSUPPORTED;
+  const PwSched o{max_wg, lds_weights};
+  const PwGather g{coords, centers, Cin > 3 ? feat : nullptr, idx, Cin - 3, N, U};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto run = [&](auto CBc, auto VBc) {
+    constexpr int CB = decltype(CBc)::value, VB = decltype(VBc)::value;
+    if (grouped) return launch_pw_grouped<CB, VB>(g, wp, bias, y, B, Cin, Cout, L, stats, st, o);
+    if (maxform) return launch_pw_max<CB, VB>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, out_a, out_b, st, o);
+    return launch_pw<CB, VB>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st, o);
+  };
+  switch (p.cb) {
+  case 1: return run(IntC<1>{}, IntC<4>{});
+  case 2: return run(IntC<2>{}, IntC<4>{});
+  case 4: return run(IntC<4>{}, IntC<2>{});
+  default: return run(IntC<8>{}, IntC<1>{});
   }
 }
 

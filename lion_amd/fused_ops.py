@@ -274,10 +274,11 @@ def pwconv_fused(x, conv, pro=None, want_stats=True, split=None):
 
 
 # The last layer of a set-abstraction MLP evaluated twice (sums, then activated maximum) instead of stored (round 4) --
-# built, bit-identical (tests/test_fold_se_gpu.py), and NOT faster: SA-0 layer 2 (32 -> 64 over 1 M columns) takes 100 us per
-# pass without storing a byte against 121 us with its 268 MB output + 42 us for the max pass (208 vs 163 us; the sampling
-# step is unchanged within noise).  The layer is not bound by its bytes: one wave = 64 loads, one wait, 128 MFMAs, with two
-# workgroups per CU to overlap those phases.  Off by default; LION_PW_MAX_RECOMPUTE=1 selects it (saves the 268 MB tensor).
+# built, bit-identical (tests/test_fold_se_gpu.py), and NOT faster, also with the pipelined pwconv_kernel (round 7,
+# profiles/pw_fp32_pipeline_ab.txt): SA-0 layer 2 (32 -> 64 over 1 M columns) takes 67 us for the sums-only pass and 117 us for
+# the pass with the activated maximum in its epilogue, against 101 us with its 268 MB output stored + 41 us for the max pass
+# (185 vs 148 us).  The second pass is bound by its epilogue -- per lane and tile 128 swishes and 128 DPP maxima -- not by
+# its loads, so the schedule does not move it.  Off by default; LION_PW_MAX_RECOMPUTE=1 selects it (saves the 268 MB tensor).
 MAX_RECOMPUTE = os.environ.get("LION_PW_MAX_RECOMPUTE", "0") != "0"
 
 
