@@ -241,6 +241,33 @@ int lion_chain_update_multistep(const float *x, const float *eps, const float *h
                                 float *out, float *hist_out, lionStream_t stream);
 int lion_chain_update_multistep_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
                                    float *out, float *hist_out, lionStream_t stream);
+/* SDE-DPM-Solver++(2M) (the same paper, the SDE form of Algorithm 2): the multistep update above with other exponents in a2 and
+ * a3 and one Gaussian term.  Same reads, same first three operations, every written operation rounded once (no fma):
+ *   x0  = a0*(x - a1*eps);   D = a5 == 0 ? a4*x0 : a4*x0 + a5*hist;   hist_out = x0
+ *   out = (a2*x + a3*D) + a6*z        when a6 != 0
+ *   out =  a2*x + a3*D                when a6 == 0: nothing is drawn, neither z_in nor seed is read
+ *   a2 = (sigma_n/sigma_t)*exp(-h), a3 = -alpha_n*expm1(-2h), a6 = sigma_n*sqrt(-expm1(-2h))
+ * z = z_in where z_in != NULL, else z ~ N(0,1) drawn in the kernel by the chain's generator, the device function of
+ * lion_chain_update_noise, at counter = (element/4, step word, stream_id) under the 64-bit seed in device memory: for the same
+ * seed, step index and stream_id it is the z of lion_chain_update_noise, bit for bit.  z_out (may be NULL) receives the z that
+ * was used, zeros when a6 == 0.  hist is NOT read when a5 == 0; out may alias x and hist_out may alias hist.
+ * lion_sde_dpmpp_update takes coefficients and step word by value (the eager loop; hist may be NULL when a5 == 0, z_in and
+ * seed both NULL only when a6 == 0).  lion_chain_update_multistep_noise reads a0..a5 from cur[1..6] and the step index i from
+ * cur[7] as lion_chain_begin_step leaves them (cur has no room for a6), and a6 from table[8*i + 7], the schedule table the
+ * step was begun on: the last launch of a captured step.  lion_chain_update_multistep_noise_cm is that update on
+ * x / hist / out / hist_out / z_out f32[B][N][4] and the denoiser's channel-major eps_cm f32[B][4][N].
+ * LION_EINVAL before any launch: a NULL pointer (but hist, z_in, seed, z_out, as said), numel == 0 / B <= 0 / N <= 0, or x,
+ * eps, hist, z_in, out, hist_out or z_out not 16-byte aligned (eps_cm may have any alignment). */
+int lion_sde_dpmpp_update(const float *x, const float *eps, const float *hist, const float *z_in, size_t numel, float a0,
+                          float a1, float a2, float a3, float a4, float a5, float a6,
+                          const uint32_t *seed /* device u32[2]: lo, hi */, uint32_t step_word, uint32_t stream_id, float *out,
+                          float *hist_out, float *z_out, lionStream_t stream);
+int lion_chain_update_multistep_noise(const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
+                                      const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
+                                      float *hist_out, float *z_out, lionStream_t stream);
+int lion_chain_update_multistep_noise_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
+                                         const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
+                                         float *hist_out, float *z_out, lionStream_t stream);
 /* The forward-process draw that starts a chain at an intermediate step (diffuse-denoise; sample_q of
  * utils/diffusion_pvd.py:105-113 with the scalars of iw_quantities_t :44-103):
  *   out = (m*x0) + (s*z)        two products and one sum, each rounded once (no fma)

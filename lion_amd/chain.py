@@ -4,7 +4,7 @@
 One denoiser evaluation of the local prior is ~500 kernel launches; the reference's samplers
 (utils/diffusion_pvd.py:224-303, :390-473) additionally issue ~10 elementwise launches, a ``torch.full`` and a
 host-side ``randn`` + H2D copy per step.  Here a captured step holds
-    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise   (DPMPP: lion_chain_update_multistep)
+    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise   (DPMPP: lion_chain_update_multistep[_noise])
 and a chain of S steps is S replays of it.  Two things live here, apart:
   * ``CapturedStep``: warm-up, capture and replay of ANY step given as a callable -- the one capture path of the package
     (this chain, ode.OdeGraph, graph.GraphedDenoiser).  One hipGraph for models without set abstraction (the global prior);
@@ -29,6 +29,10 @@ DDIM, DDPM = 0, 1
 # the deterministic multistep solver DPM-Solver++(2M) (DiffusionDiscretized.run_dpm_solver): the captured step ends with
 # lion_chain_update_multistep instead of lion_chain_update_noise, and the chain also owns `hist`, the previous step's data prediction
 DPMPP = 2
+# its stochastic form SDE-DPM-Solver++(2M) (run_dpm_solver(stochastic=True)): the captured step ends with
+# lion_chain_update_multistep_noise, which draws the step's noise like lion_chain_update_noise and reads its scale from column 7
+# of the schedule table; the chain owns `hist` like DPMPP and records its noise like DDIM / DDPM
+SDE_DPMPP = 3
 # tests: a list here makes every chain run append (start latent, [the noise each step drew]) -- what an eager loop needs
 # to repeat a graphed chain draw for draw (run_ddim(given_noise=...)); chains are then captured with the noise output on
 RECORD = None
@@ -219,10 +223,10 @@ class GraphedChain:
         self.seed = torch.zeros(2, dtype=torch.int32, device=dev)   # two 32-bit words of the Philox key
         self.cur = torch.zeros(8, device=dev)
         self.z = torch.zeros(size, device=dev) if record_noise else None   # tests: the noise each step used
-        self.hist = torch.zeros(size, device=dev) if mode == DPMPP else None   # the previous step's data prediction
+        self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
         # identity rows until run() uploads a schedule: the warm-up / capture passes must run on finite values (an
         # all-zero DDPM row is 0/0 -> the second warm-up forward would voxelize NaN latents).  For the multistep update the
-        # same row is x0 = x, D = 0, out = x.
+        # same row is x0 = x, D = 0, out = x, and column 7 is 0: SDE_DPMPP's warm-up draws nothing.
         self.table[:, 0] = 1.0   # t_model
         self.table[:, 1] = 1.0   # a0: x passes through
         self.table[:, 3] = 1.0   # a2: DDPM divisor (DDIM: z has weight 1 -- finite)
@@ -256,12 +260,20 @@ class GraphedChain:
                     _lib.call("lion_chain_update_multistep_cm", self.x, eps, self.hist, num_samples, n_pts, self.cur, self.x,
                               self.hist)
                     return
+                if mode == SDE_DPMPP:
+                    _lib.call("lion_chain_update_multistep_noise_cm", self.x, eps, self.hist, num_samples, n_pts, self.cur,
+                              self.table, self.seed, 0, self.x, self.hist, self.z)
+                    return
                 _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
                           self.z)
                 return
             eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **extra).float().contiguous()
             if mode == DPMPP:
                 _lib.call("lion_chain_update_multistep", self.x, eps, self.hist, self.x.numel(), self.cur, self.x, self.hist)
+                return
+            if mode == SDE_DPMPP:
+                _lib.call("lion_chain_update_multistep_noise", self.x, eps, self.hist, self.x.numel(), self.cur, self.table,
+                          self.seed, 0, self.x, self.hist, self.z)
                 return
             _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
@@ -272,8 +284,8 @@ class GraphedChain:
     @torch.no_grad()
     def run(self, x_init, table: np.ndarray, seed: int, condition_input=None, clip_feat=None, trajectory=None,
             trajectory_before_last=False, noise_trajectory=None, state_hook=None):
-        """x_init: the chain's start; table [S, 8] float32 rows {t_model, a0..a5, 0}.  Returns the final latent
-        (a fresh tensor).  `trajectory`: list that receives a copy of x after every step (before the last
+        """x_init: the chain's start; table [S, 8] float32 rows {t_model, a0..a5, a6} (a6: SDE_DPMPP's noise scale, 0 in
+        every other mode).  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after every step (before the last
         step's update if `trajectory_before_last`, as run_denoising_diffusion reports it).
         `state_hook(i, x)`: called before step i's replay with the chain's latent buffer, which it may overwrite IN PLACE
         with launches on the current stream (no host synchronisation): inpainting / known-region replacement, or a

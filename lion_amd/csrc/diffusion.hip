@@ -210,6 +210,89 @@ static int multistep_launch(hipStream_t st, const float *x, const float *eps, co
                                        a[5], out, hist_out, cm_points);
 }
 
+// SDE-DPM-Solver++(2M) (Lu et al. 2022, the SDE form of Algorithm 2): multistep_kernel's reads and its first three operations,
+// then one Gaussian term, one rounding per written operation:
+//   x0 = a0*(x - a1*eps);   D = a5 == 0 ? a4*x0 : a4*x0 + a5*hist;   hist_out = x0
+//   out = a6 != 0 ? (a2*x + a3*D) + a6*z : a2*x + a3*D
+// (a2 = (sigma_n/sigma_t)*exp(-h), a3 = -alpha_n*expm1(-2h), a6 = sigma_n*sqrt(-expm1(-2h))).  With `cur` (the captured step)
+// a0..a5 are cur[1..6], the step word is cur[7] (the step's index, as begin_step leaves it) and a6 = table[8*step + 7]; else
+// all come by value (the eager loop).  z = z_in where given, else normal4 at counter (quad, step word, stream_id) under the
+// seed in device memory: update_noise_kernel's counters.  Nothing is drawn and neither z_in nor the seed is read when a6 == 0;
+// z_out (may be NULL) then receives zeros, else the z that was used.  hist, cm_points and aliasing as in multistep_kernel.
+__global__ void multistep_noise_kernel(const float *x, const float *eps, const float *hist, const float *z_in, size_t numel,
+                                       const float *__restrict__ cur, const float *__restrict__ table, float a0, float a1,
+                                       float a2, float a3, float a4, float a5, float a6,
+                                       const uint32_t *__restrict__ seed_words, uint32_t step, uint32_t stream_id, float *out,
+                                       float *hist_out, float *z_out, int cm_points) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = q * 4;
+  if (i >= numel) return;
+  if (cur) {
+    a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; a3 = cur[4]; a4 = cur[5]; a5 = cur[6];
+    step = (uint32_t)__float_as_int(cur[7]);
+    a6 = table[(size_t)step * 8 + 7];
+  }
+  const bool second = a5 != 0.f, noisy = a6 != 0.f;
+  float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, o[4], p[4];
+  const bool full = i + 3 < numel;
+  if (full) {
+    const float4 t = *reinterpret_cast<const float4 *>(x + i);
+    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+    if (second) {
+      const float4 h = *reinterpret_cast<const float4 *>(hist + i);
+      hv[0] = h.x; hv[1] = h.y; hv[2] = h.z; hv[3] = h.w;
+    }
+  } else {
+    for (int j = 0; j < 4; ++j) { xv[j] = i + j < numel ? x[i + j] : 0.f; hv[j] = second && i + j < numel ? hist[i + j] : 0.f; }
+  }
+  if (cm_points) {   // numel = B*N*4: every quad is full; eps is the denoiser's channel-major [B][4][N]
+    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
+  } else if (full) {
+    const float4 u = *reinterpret_cast<const float4 *>(eps + i);
+    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
+  } else {
+    for (int j = 0; j < 4; ++j) ev[j] = i + j < numel ? eps[i + j] : 0.f;
+  }
+  if (noisy) {
+    if (!z_in) {
+      const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
+      normal4(q, step, stream_id, seed, z);
+    } else if (full) {
+      const float4 t = *reinterpret_cast<const float4 *>(z_in + i);
+      z[0] = t.x; z[1] = t.y; z[2] = t.z; z[3] = t.w;
+    } else {
+      for (int j = 0; j < 4; ++j) z[j] = i + j < numel ? z_in[i + j] : 0.f;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    p[j] = mul_rn(a0, sub_rn(xv[j], mul_rn(a1, ev[j])));
+    float d = mul_rn(a4, p[j]);
+    if (second) d = add_rn(d, mul_rn(a5, hv[j]));
+    o[j] = add_rn(mul_rn(a2, xv[j]), mul_rn(a3, d));
+    if (noisy) o[j] = add_rn(o[j], mul_rn(a6, z[j]));
+  }
+  if (full) {
+    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4 *>(hist_out + i) = make_float4(p[0], p[1], p[2], p[3]);
+    if (z_out) *reinterpret_cast<float4 *>(z_out + i) = make_float4(z[0], z[1], z[2], z[3]);
+  } else {
+    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; hist_out[i + j] = p[j]; if (z_out) z_out[i + j] = z[j]; }
+  }
+}
+
+static int multistep_noise_launch(hipStream_t st, const float *x, const float *eps, const float *hist, const float *z_in,
+                                  size_t numel, const float *cur, const float *table, const float a[7], const uint32_t *seed,
+                                  uint32_t step, uint32_t stream_id, float *out, float *hist_out, float *z_out, int cm_points) {
+  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
+  if (blocks > 0x7fffffffu) return LION_EINVAL;
+  return lion_launch<multistep_noise_kernel>((unsigned)blocks, 256, 0, st, x, eps, hist, z_in, numel, cur, table, a[0], a[1],
+                                             a[2], a[3], a[4], a[5], a[6], seed, step, stream_id, out, hist_out, z_out,
+                                             cm_points);
+}
+
 // Forward-process draw out = m*x0 + s*z (sample_q, utils/diffusion_pvd.py:105-113) with the chain's generator: quad q of the
 // flat tensor takes Philox counter (q, LION_DIFFUSE_STEP_WORD, stream_id), whatever the pointers' alignment.  VEC: every pointer
 // is 16-byte aligned -> one 16-byte access per operand and full quad; else (and in the tail quad) element by element.
@@ -334,6 +417,43 @@ int lion_chain_update_multistep_cm(const float *x, const float *eps_cm, const fl
   if (((((uintptr_t)x) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0) return LION_EINVAL;
   const float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   return multistep_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, (size_t)B * N * 4, cur, a, out, hist_out, N);
+}
+
+int lion_sde_dpmpp_update(const float *x, const float *eps, const float *hist, const float *z_in, size_t numel, float a0,
+                          float a1, float a2, float a3, float a4, float a5, float a6, const uint32_t *seed, uint32_t step_word,
+                          uint32_t stream_id, float *out, float *hist_out, float *z_out, lionStream_t stream) {
+  if (!x || !eps || !out || !hist_out || numel == 0) return LION_EINVAL;
+  if (!hist && a5 != 0.f) return LION_EINVAL;
+  if (!z_in && !seed && a6 != 0.f) return LION_EINVAL;
+  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)z_in) | ((uintptr_t)out) | ((uintptr_t)hist_out) |
+        ((uintptr_t)z_out)) & 15) != 0)
+    return LION_EINVAL;
+  const float a[7] = {a0, a1, a2, a3, a4, a5, a6};
+  return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps, hist, z_in, numel, nullptr, nullptr, a, seed,
+                                step_word, stream_id, out, hist_out, z_out, 0);
+}
+
+int lion_chain_update_multistep_noise(const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
+                                      const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
+                                      float *hist_out, float *z_out, lionStream_t stream) {
+  if (!x || !eps || !hist || !cur || !table || !seed || !out || !hist_out || numel == 0) return LION_EINVAL;
+  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out) | ((uintptr_t)z_out)) &
+       15) != 0)
+    return LION_EINVAL;
+  const float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps, hist, nullptr, numel, cur, table, a, seed, 0,
+                                stream_id, out, hist_out, z_out, 0);
+}
+
+int lion_chain_update_multistep_noise_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
+                                         const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
+                                         float *hist_out, float *z_out, lionStream_t stream) {
+  if (!x || !eps_cm || !hist || !cur || !table || !seed || !out || !hist_out || B <= 0 || N <= 0) return LION_EINVAL;
+  if (((((uintptr_t)x) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out) | ((uintptr_t)z_out)) & 15) != 0)
+    return LION_EINVAL;
+  const float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, nullptr, (size_t)B * N * 4, cur, table, a,
+                                seed, 0, stream_id, out, hist_out, z_out, N);
 }
 
 int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s, const uint32_t *seed,

@@ -204,7 +204,7 @@ class DiffusionDiscretized(object):
         ab = self._h_alpha_bars.numpy().astype(np.float64)
         return ab, 0.5 * (np.log(ab) - np.log1p(-ab))
 
-    def solver_schedule(self, S, skip_type='logsnr'):
+    def solver_schedule(self, S, skip_type='logsnr', t_start=None):
         """Descending list of DISTINCT schedule indices for run_dpm_solver: starts at T-1 (S >= 2), ends at 0; S == 1 gives
         [0], as ddim_schedule does.  The list may be SHORTER than S: duplicates are removed, since a step of zero length has
         h = 0 and no second-order ratio.
@@ -214,27 +214,40 @@ class DiffusionDiscretized(object):
         better than DDIM there (measured ratios 0.6 ... 2.8 against 5.5 ... 21 with 'logsnr').
         'uniform' / 'quad': ddim_schedule(T, S, skip_type) with duplicates removed; where its largest entry falls short of
         T-1 ('quad' stops at 0.8*T; 'uniform' where the floor rounds down) that entry is moved up to T-1, the index whose
-        marginal the N(0, I) start is drawn for.  Any other string: ValueError."""
+        marginal the N(0, I) start is drawn for.  Any other string: ValueError.
+        t_start (an index, 1 <= t_start <= T-1; anything else: ValueError): the tail of a chain from that index -- the same
+        construction on the indices <= t_start, as if the process had t_start + 1 steps: 'logsnr' takes S points uniform in
+        lambda from lambda[t_start] to lambda[0], 'uniform' / 'quad' are ddim_schedule(t_start + 1, S, skip_type).  The list
+        starts at t_start and ends at 0, so a tail needs S >= 2 (S == 1: ValueError).  t_start = T-1 is the default list."""
         T, S = self._diffusion_steps, int(S)
         if skip_type not in ('logsnr', 'uniform', 'quad'):
             raise ValueError(f"solver_schedule: unknown skip_type {skip_type!r}")
         if S < 1:
             raise ValueError(f"solver_schedule: S = {S}")
+        if t_start is None:
+            top = T - 1
+        else:
+            if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 1 <= t_start <= T - 1:
+                raise ValueError(f"solver_schedule: t_start = {t_start!r} is not an index in [1, {T - 1}]")
+            if S == 1:
+                raise ValueError("solver_schedule: a tail from t_start visits t_start and 0: S >= 2")
+            top = int(t_start)
         if S == 1:
             return [0]
         if skip_type == 'logsnr':
             _, lam = self._half_logsnr()
-            tau = [int(np.argmin(np.abs(lam - p))) for p in np.linspace(lam[T - 1], lam[0], S)]
+            lam = lam[:top + 1]
+            tau = [int(np.argmin(np.abs(lam - p))) for p in np.linspace(lam[top], lam[0], S)]
         else:
-            tau = self.ddim_schedule(T, S, skip_type)
+            tau = self.ddim_schedule(top + 1, S, skip_type)
         tau = sorted(set(tau), reverse=True)
-        if tau[0] != T - 1:
-            tau[0] = T - 1
+        if tau[0] != top:
+            tau[0] = top
         if tau[-1] != 0:
             tau.append(0)
         return tau
 
-    def dpm_solver_table(self, steps, order=2, dtype=np.float32):
+    def dpm_solver_table(self, steps, order=2, dtype=np.float32, stochastic=False):
         """[len(steps), 8] rows {t_model, a0..a5, 0} of DPM-Solver++ (Lu et al. 2022, Algorithm 2; order 1 is DDIM with
         kappa = 0) over the descending distinct indices `steps`, the last of which is 0 -- what lion_dpmpp_update and the
         captured chain (chain.DPMPP) read:  x0 = a0*(x - a1*eps);  D = a4*x0 + a5*x0_prev;  x <- a2*x + a3*D.
@@ -243,7 +256,12 @@ class DiffusionDiscretized(object):
         (a4, a5) = (1, 0) for i == 0 or order 1, else (1 + 1/(2r), -1/(2r)) with r = h_{i-1}/h_i.
         The last row (t = 0) returns the data prediction, like DDIM's alpha_next = 1: a2 = 0, a3 = 1, a4 = 1, a5 = 0.
         All arithmetic in float64 on the float32 schedule widened; the result is cast to `dtype` once (float64: the values
-        before the cast)."""
+        before the cast).
+        stochastic=True: SDE-DPM-Solver++(2M) (the same paper, the SDE form of Algorithm 2), x <- a2*x + a3*D + a6*z with
+        z ~ N(0, I): a2 = (sigma_n/sigma_t)*exp(-h_i), a3 = -alpha_n*expm1(-2*h_i), and the noise scale
+        a6 = sigma_n*sqrt(-expm1(-2*h_i)) in column 7 (0 otherwise); a0, a1, a4, a5 and the last row (a6 = 0: it draws nothing)
+        as above.  Order 1 is DDIM with kappa = 1 (a2 + a3*a0 = s, -a3*a0*a1 = c, a6 = sigma of ddim_coefficients), and
+        (a2*sigma_t)^2 + a6^2 = sigma_n^2: what is left of the old noise plus the fresh noise is the new marginal's."""
         if order not in (1, 2):
             raise ValueError(f"dpm_solver_table: order = {order!r}, must be 1 or 2")
         steps = [int(t) for t in steps]
@@ -260,7 +278,11 @@ class DiffusionDiscretized(object):
                 break
             n = steps[i + 1]
             h = lam[n] - lam[t]
-            table[i, 3:5] = (sigma[n] / sigma[t], -alpha[n] * np.expm1(-h))
+            if stochastic:
+                table[i, 3:5] = (sigma[n] / sigma[t] * np.exp(-h), -alpha[n] * np.expm1(-2.0 * h))
+                table[i, 7] = sigma[n] * np.sqrt(-np.expm1(-2.0 * h))
+            else:
+                table[i, 3:5] = (sigma[n] / sigma[t], -alpha[n] * np.expm1(-h))
             if i == 0 or order == 1:
                 table[i, 5:7] = (1.0, 0.0)
             else:
@@ -477,7 +499,7 @@ class DiffusionDiscretized(object):
     @torch.no_grad()
     def run_dpm_solver(self, model, num_samples, shape, steps=20, order=2, skip_type='logsnr', x_noisy=None,
                        condition_input=None, clip_feat=None, enable_autocast=False, keep_trajectory=True, graph=True,
-                       state_hook=None, conv_precision="fp32"):
+                       state_hook=None, conv_precision="fp32", stochastic=False, t_start=None, seed=None):
         """Deterministic few-step sampling with DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2): the second-order multistep
         solver of the probability-flow ODE that run_ddim(kappa=0) integrates to first order.  At most ``steps`` model
         evaluations (solver_schedule removes duplicate indices), one per visited index of
@@ -490,15 +512,29 @@ class DiffusionDiscretized(object):
         the previous data prediction in device memory (chain.DPMPP; a cache entry of its own beside the DDIM / DDPM
         captures of the same model).  Otherwise -- graph=False, mixed_prediction models, autocast -- the eager per-step loop
         on lion_dpmpp_update; from the same start the two give the same bits.
-        state_hook(i, x) and conv_precision: as in run_ddim."""
+        state_hook(i, x) and conv_precision: as in run_ddim.
+        stochastic=True: SDE-DPM-Solver++(2M), the same multistep update with the SDE's exponents and fresh noise at every
+        step but the last (dpm_solver_table(stochastic=True); order 1 is DDIM with kappa = 1).  At equal steps it is LESS
+        accurate than the deterministic solver: it buys stochasticity, which diffuse-denoise relies on.
+        The noise comes from the chain's Philox generator under ``seed`` (None: chain.draw_seed(), so torch.manual_seed
+        governs it), step i at counter word i, stream 0.  graph=True replays the chain.SDE_DPMPP capture [prologue -> denoiser
+        -> lion_chain_update_multistep_noise], otherwise the eager loop runs lion_sde_dpmpp_update on the same seed, step
+        words and stream: from the same start and seed the two give the same bits.
+        t_start (an index in 1 ... T-1; needs x_noisy, else ValueError): the tail of the chain from x_noisy, taken as a draw
+        of the marginal at index t_start (DiffusionDiscretized.diffuse(x0, t_start)), over
+        solver_schedule(steps, skip_type, t_start).  Either solver runs it."""
         with conv_ops.requested_precision(conv_precision):
             return self._run_dpm_solver(model, num_samples, shape, steps, order, skip_type, x_noisy, condition_input, clip_feat,
-                                        enable_autocast, keep_trajectory, graph, state_hook)
+                                        enable_autocast, keep_trajectory, graph, state_hook, stochastic, t_start, seed)
 
     def _run_dpm_solver(self, model, num_samples, shape, steps, order, skip_type, x_noisy, condition_input, clip_feat,
-                        enable_autocast, keep_trajectory, graph, state_hook):
-        taus = self.solver_schedule(steps, skip_type)
-        table = self.dpm_solver_table(taus, order)
+                        enable_autocast, keep_trajectory, graph, state_hook, stochastic=False, t_start=None, seed=None):
+        if t_start is not None and x_noisy is None:
+            raise ValueError("run_dpm_solver: t_start needs x_noisy, the state at that index")
+        taus = self.solver_schedule(steps, skip_type, t_start)
+        table = self.dpm_solver_table(taus, order, stochastic=bool(stochastic))
+        if stochastic:
+            seed = _chain.draw_seed() if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
         model.eval()
         dev = self.device
         size = [num_samples] + list(shape)
@@ -507,13 +543,15 @@ class DiffusionDiscretized(object):
         x_noisy = x_noisy.to(dev).contiguous()
         output_list = []
         if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
-            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DPMPP,
-                                  self._diffusion_steps)
-            x = ch.run(x_noisy, table, 0, condition_input, clip_feat, trajectory=output_list if keep_trajectory else None,
-                       state_hook=state_hook)   # seed 0: this step draws nothing
+            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev,
+                                  _chain.SDE_DPMPP if stochastic else _chain.DPMPP, self._diffusion_steps)
+            x = ch.run(x_noisy, table, seed if stochastic else 0, condition_input, clip_feat,
+                       trajectory=output_list if keep_trajectory else None,
+                       state_hook=state_hook)   # seed 0: the deterministic step draws nothing
             model.train()
             return x, output_list
         x, hist = x_noisy.clone(), None     # the hook may overwrite the latent in place: never the caller's tensor
+        words = diffusion_ops.seed_words(seed, dev) if stochastic else None
         for i, t in enumerate(taus):
             if state_hook is not None:
                 state_hook(i, x)
@@ -522,7 +560,11 @@ class DiffusionDiscretized(object):
             with torch.autocast("cuda", enabled=enable_autocast):
                 pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat)
                 eps_hat = _mixed(model, pred, mixing).float().contiguous()
-            x, hist = diffusion_ops.dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:7]])
+            if stochastic:   # step i of the captured chain: counter word i, stream 0
+                x, hist = diffusion_ops.sde_dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:8]], seed=words,
+                                                         step=i)
+            else:
+                x, hist = diffusion_ops.dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:7]])
             if keep_trajectory:
                 output_list.append(x)
         model.train()

@@ -1,11 +1,11 @@
 """Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, the multistep solver
-step lion_dpmpp_update, and the forward-process draw lion_chain_diffuse."""
+step lion_dpmpp_update and its stochastic form lion_sde_dpmpp_update, and the forward-process draw lion_chain_diffuse."""
 import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "diffuse"]
+__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "sde_dpmpp_update", "diffuse"]
 
 
 def ddim_update(x, eps, z, s, c, sigma, out=None):
@@ -50,6 +50,33 @@ def dpmpp_update(x, eps, hist, a0, a1, a2, a3, a4, a5, out=None, hist_out=None):
     _lib.call("lion_dpmpp_update", x, eps, hist, x.numel(), float(a0), float(a1), float(a2), float(a3), float(a4), float(a5),
               out, hist_out)
     return out, hist_out
+
+
+def sde_dpmpp_update(x, eps, hist, a0, a1, a2, a3, a4, a5, a6, noise=None, seed=None, step=0, stream_id=0, out=None,
+                     hist_out=None, return_noise=False):
+    """One SDE-DPM-Solver++(2M) step (lion_sde_dpmpp_update; coefficients: dpm_solver_table(stochastic=True), a6 its
+    column 7): dpmpp_update's x0, D and hist_out, then out = (a2*x + a3*D) + a6*z where a6 != 0, else out = a2*x + a3*D.
+    z = `noise` if given, else N(0, 1) drawn in the kernel by the chain's Philox generator at counter (element/4, `step`,
+    stream_id) under `seed`: a 64-bit int, or the device words of seed_words() (a loop uploads them once) -- what step `step`
+    of a captured chain (chain.SDE_DPMPP) under that seed draws.  Neither is needed when a6 == 0: nothing is drawn.
+    return_noise: (out, hist_out, z), z the noise that was used, zeros when a6 == 0."""
+    _lib.require_cuda(x, eps, hist, noise, out, hist_out)
+    if hist is None and float(a5) != 0.0:
+        raise ValueError("sde_dpmpp_update: a second-order row (a5 != 0) needs hist")
+    if noise is None and seed is None and float(a6) != 0.0:
+        raise ValueError("sde_dpmpp_update: a noisy row (a6 != 0) needs noise or seed")
+    if noise is not None and noise.shape != x.shape:
+        raise ValueError(f"sde_dpmpp_update: noise {tuple(noise.shape)} for x {tuple(x.shape)}")
+    out = torch.empty_like(x) if out is None else out
+    hist_out = torch.empty_like(x) if hist_out is None else hist_out
+    z_out = torch.empty_like(x) if return_noise else None
+    if noise is not None or seed is None:
+        words = None
+    else:
+        words = seed if isinstance(seed, torch.Tensor) else seed_words(int(seed), x.device)
+    _lib.call("lion_sde_dpmpp_update", x, eps, hist, noise, x.numel(), float(a0), float(a1), float(a2), float(a3), float(a4),
+              float(a5), float(a6), words, int(step), int(stream_id), out, hist_out, z_out)
+    return (out, hist_out, z_out) if return_noise else (out, hist_out)
 
 
 def ddpm_update(x, eps, z, t_is_zero, k_outer, k_a, k_b, scale, temp, out=None):

@@ -5,7 +5,8 @@ of noisy or voxelised inputs, editing.
 Per latent the device work is one forward draw (``DiffusionDiscretized.diffuse``: lion_chain_diffuse, noise on the chip) and
 ``time_start`` replays of the prior's captured ancestral step (``run_denoising_diffusion_from_t``) -- the chain a sampling
 call of the same batch shape captured is the one replayed here.  One ``time_start`` per latent for the whole batch, as in the
-reference.
+reference.  With ``solver_steps=S`` the tail is instead at most S replays of the few-step solver's captured step
+(``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ def _split_seed(seed: int, n: int):
 
 @torch.no_grad()
 def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=None, keep_first=False, graph=True,
-                    conv_precision="fp32", seed=None):
+                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True):
     """x [B, N, 3] -> (points [B, N, 3], info).  vae: models.vae_adain.Model (in the mode the caller wants: eval() for
     inference); dae: [global prior, local prior]; diffusion: DiffusionDiscretized.
 
@@ -53,13 +54,26 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     package pass it; the reference's recipe passes the latent itself, which is the same tensor whenever style_mlp is '' (every
     released configuration).
     info: 'global_original', 'global_edited', 'local_original', 'local_edited' (the four latents, [B] + latent_shape()),
-    'condition_input' (what the local prior was conditioned on), 'time_start' (the pair) and 'seeds' (the call's seed and the
-    key of every draw derived from it)."""
+    'condition_input' (what the local prior was conditioned on), 'time_start' (the pair), 'seeds' (the call's seed and the
+    key of every draw derived from it) and 'tail_steps' (per latent the list of schedule indices its tail evaluated the prior
+    at, in order; [] where time_start is 0).
+    solver_steps: None (default) is the ancestral tail above.  An int S >= 2 runs each latent's tail with the few-step solver,
+    run_dpm_solver(steps=S, t_start=time_start[i], stochastic=stochastic, seed=seeds['chain_*']): at most S evaluations of the
+    prior, at the indices solver_schedule(S, 'logsnr', time_start[i]), instead of time_start[i].  The solver tail STARTS AT
+    index time_start, the marginal the latent was actually drawn from: it does not reproduce the reference's off-by-one,
+    which stays with the ancestral tail.  stochastic=True (default) is SDE-DPM-Solver++(2M), whose steps draw fresh noise
+    as the ancestral steps do; False is the deterministic solver, which only transports the perturbation of the forward draw.
+    keep_first, conv_precision, graph and time_start = 0 behave as in the ancestral tail; temp scales the ancestral steps'
+    noise only, the solver has no such knob."""
     T = diffusion._diffusion_steps
     pair = tuple(time_start) if isinstance(time_start, (tuple, list)) else (time_start, time_start)
     if len(pair) != 2 or any(isinstance(t, bool) or not isinstance(t, numbers.Integral) or not 0 <= t <= T - 1 for t in pair):
         raise ValueError(f"diffuse_denoise: time_start = {time_start!r}: an int or a (global, local) pair in [0, {T - 1}]")
     pair = (int(pair[0]), int(pair[1]))
+    if solver_steps is not None and (isinstance(solver_steps, bool) or not isinstance(solver_steps, numbers.Integral)
+                                     or solver_steps < 2):
+        raise ValueError(f"diffuse_denoise: solver_steps = {solver_steps!r}: None or an int >= 2")
+    visited = [[], []]
     if not x.is_cuda:
         raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
     base = _chain.draw_seed() if seed is None else int(seed) & _MASK64
@@ -76,9 +90,17 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
             return eps_ori
         which = ("global", "local")[i]
         eps_t = diffusion.diffuse(eps_ori, pair[i], seed=seeds["diffuse_" + which])
-        with conv_ops.requested_precision(conv_precision):
-            eps, _ = diffusion._denoise_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp, False, condition_input, None,
-                                               clip_feat, graph, False, seeds["chain_" + which])
+        if solver_steps is not None:
+            visited[i] = diffusion.solver_schedule(int(solver_steps), 'logsnr', pair[i])
+            eps, _ = diffusion.run_dpm_solver(dae[i], B, shapes[i], steps=int(solver_steps), x_noisy=eps_t,
+                                              condition_input=condition_input, clip_feat=clip_feat, keep_trajectory=False,
+                                              graph=graph, conv_precision=conv_precision, stochastic=stochastic,
+                                              t_start=pair[i], seed=seeds["chain_" + which])
+        else:
+            visited[i] = list(range(pair[i] - 1, -1, -1))
+            with conv_ops.requested_precision(conv_precision):
+                eps, _ = diffusion._denoise_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp, False, condition_input, None,
+                                                   clip_feat, graph, False, seeds["chain_" + which])
         if keep_first:
             eps[0:1] = eps_ori[0:1]
         return eps.contiguous()
@@ -96,5 +118,6 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     local_new = edit(1, local_ori, condition_input)
     points = vae.decoder(None, beta=None, context=local_new.view(flat_shape), style=style)
     info = {"global_original": global_ori, "global_edited": global_new, "local_original": local_ori,
-            "local_edited": local_new, "condition_input": condition_input, "time_start": pair, "seeds": seeds}
+            "local_edited": local_new, "condition_input": condition_input, "time_start": pair, "seeds": seeds,
+            "tail_steps": (visited[0], visited[1])}
     return points, info

@@ -74,12 +74,13 @@ class LION(object):
         print(f'INFO finish loading from {model_path}')
 
     @torch.no_grad()
-    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32", dpm_step=0):
+    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32", dpm_step=0, dpm_stochastic=False):
         """1000 ancestral steps of the global prior, 1000 of the local prior, one decode
         (reference :38-80).  conv_precision="half": the priors' voxel convolutions run at reduced precision
         (conv_ops.PRECISION); the decode stays fp32-accurate.
         dpm_step > 0: both priors run DPM-Solver++(2M) with at most dpm_step evaluations instead of the ancestral steps
-        (DiffusionDiscretized.run_dpm_solver); the default is the reference's chain."""
+        (DiffusionDiscretized.run_dpm_solver), dpm_stochastic=True its stochastic form; the default is the reference's
+        chain."""
         self.priors.eval()
         self.vae.eval()
         self.scheduler.set_timesteps(self.diffusion._diffusion_steps, device=self.device)
@@ -94,7 +95,8 @@ class LION(object):
             # the scheduler's mean / variance rule feeds the chain's coefficient table (lion_amd/chain.py)
             if dpm_step > 0:
                 x, _ = self.diffusion.run_dpm_solver(prior, num_samples, shp, steps=dpm_step, condition_input=condition_input,
-                                                     clip_feat=clip_feat, keep_trajectory=False, conv_precision=conv_precision)
+                                                     clip_feat=clip_feat, keep_trajectory=False, conv_precision=conv_precision,
+                                                     stochastic=dpm_stochastic)
             else:
                 x, _ = self.diffusion.run_denoising_diffusion(
                     prior, num_samples, shp, condition_input=condition_input, clip_feat=clip_feat,

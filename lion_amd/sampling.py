@@ -13,7 +13,8 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
                                  temp=1.0, ddim_step=0, clip_feat=None, ddim_skip_type='uniform',
                                  ddim_kappa=1.0, noise='device', step_callback=None, graph=True, given_noise=None,
                                  state_hook=None, ode_sample=0, ode_eps=1e-5, ode_solver_tol=1e-5, start_noise=None,
-                                 conv_precision="fp32", dpm_step=0, dpm_order=2, dpm_skip_type='logsnr'):
+                                 conv_precision="fp32", dpm_step=0, dpm_order=2, dpm_skip_type='logsnr',
+                                 dpm_stochastic=False):
     """shape: vae.latent_shape(); dae: [global prior, local prior].  Returns (points [B,N,3], info).
     graph=True (default): every chain is replayed from one captured hipGraph per prior (lion_amd/chain.py);
     graph=False: the eager per-step loop; noise='cpu' draws the start and every step's noise from torch's CPU generator
@@ -26,7 +27,9 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
     start_noise[i] if given (else fresh N(0, I) draws); info['nfe'] lists the evaluations per prior.
     dpm_step > 0: each prior runs DPM-Solver++(2M) with at most dpm_step evaluations (DiffusionDiscretized.run_dpm_solver,
     order dpm_order, spacing dpm_skip_type): deterministic after the start draw; state_hook applies, noise / given_noise do
-    not.  Precedence: ode_sample == 1, then dpm_step > 0, then ddim_step > 0, then the ancestral chain.
+    not.  dpm_stochastic=True: the stochastic form of that solver (SDE-DPM-Solver++(2M), run_dpm_solver(stochastic=True)):
+    fresh noise enters at every step but the last, from the chain's generator under a key drawn with chain.draw_seed().
+    Precedence: ode_sample == 1, then dpm_step > 0, then ddim_step > 0, then the ancestral chain.
     conv_precision="half": the supported reduced-precision mode -- the denoiser evaluations of every chain run their voxel
     convolutions at r = 16 / 32 with one fp16 product per operand pair, inside the captured chain (conv_ops.PRECISION,
     DESIGN.md 4.3); the VAE decode stays fp32-accurate.  enable_autocast is unrelated and keeps its behaviour (it leaves
@@ -49,7 +52,8 @@ def generate_samples_vada_2prior(shape, dae, diffusion, vae, num_samples, enable
                                               skip_type=dpm_skip_type, condition_input=condition_input, clip_feat=clip_feat,
                                               enable_autocast=enable_autocast, keep_trajectory=False, graph=graph,
                                               state_hook=None if state_hook is None else
-                                              (lambda k, x, _i=i: state_hook(_i, k, x)), conv_precision=conv_precision)
+                                              (lambda k, x, _i=i: state_hook(_i, k, x)), conv_precision=conv_precision,
+                                              stochastic=dpm_stochastic)
         elif ddim_step > 0:
             eps, _ = diffusion.run_ddim(dae[i], num_samples, shape[i], temp, enable_autocast,
                                         is_image=False, ddim_step=ddim_step,
