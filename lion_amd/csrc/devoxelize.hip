@@ -116,7 +116,8 @@ __global__ __launch_bounds__(256) void devox_fwd_kernel(const float *__restrict_
 // whose (base index, fractions) stay in registers.  Same expressions as corners_of()/the gather
 // kernel: bit-exact vs the oracle.
 // ---------------------------------------------------------------------------------------------
-template <int LD, bool AFF>
+// SPLIT: r = 4k + 2 (the launcher asks for r^2 % 4 == 0 only), a z-row is not a whole number of 16-byte pieces.
+template <int LD, bool AFF, bool SPLIT>
 __global__ __launch_bounds__(256) void devox_slab_kernel(
     const float *__restrict__ coords, const float *__restrict__ feat, int C, int N, int r, int PX,
     int XS, int CT, int CI, int slab_floats, int training, float *__restrict__ out,
@@ -163,7 +164,16 @@ __global__ __launch_bounds__(256) void devox_slab_kernel(
       int row = (4 * f) / r;
       if (XS == 1) row %= r2;
       else row += row0;
-      const bool want = f < n4 && ((need[row >> 5] >> (row & 31)) & 1u);
+      bool want = f < n4 && ((need[row >> 5] >> (row & 31)) & 1u);
+      // SPLIT: every odd row starts in the middle of a piece whose first float belongs to the row before it, so the piece
+      // is needed when the row of either END is.  f < n4 keeps the last float inside the slab (XS == 1: CI whole grids,
+      // else <= PX + 1 planes: row < r^2).
+      if (SPLIT && !want && f < n4) {
+        int rowh = (4 * f + 3) / r;
+        if (XS == 1) rowh %= r2;
+        else rowh += row0;
+        want = (need[rowh >> 5] >> (rowh & 31)) & 1u;
+      }
       if (want) {
         unsigned keep;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -760,8 +770,8 @@ static int devox_launch(const float *coords, const float *feat, int B, int C, in
     while (CT > CI && (long)B * lion_cdiv(C, CT) < 512) CT >>= 1;
     dim3 grid(lion_cdiv(C, CT), B);
     auto slab = [&](auto LD) {
-      return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
-        return lion_launch<devox_slab_kernel<decltype(LD)::value, decltype(AFFINE)::value>>(
+      return lion_with_flags(scale != nullptr, (r & 3) != 0, [&](auto AFFINE, auto SPLIT) {
+        return lion_launch<devox_slab_kernel<decltype(LD)::value, decltype(AFFINE)::value, decltype(SPLIT)::value>>(
             grid, 256, lds, st, coords, feat, C, N, r, PX, XS, CT, CI, slab_floats, training, out, inds, wgts, scale, shift);
       });
     };
