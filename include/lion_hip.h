@@ -268,6 +268,25 @@ int lion_chain_update_multistep_noise(const float *x, const float *eps, const fl
 int lion_chain_update_multistep_noise_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
                                          const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
                                          float *hist_out, float *z_out, lionStream_t stream);
+/* Deterministic encoder: refined DDIM inversion, the inverse of the first-order solver step (DPM-Solver++ order 1 = DDIM with
+ * kappa = 0).  The decoder step t -> n is x_n = s'*x_t + c'*eps(x_t, t); its exact inverse is the implicit equation
+ * x_t = s*x_n + c*eps(x_t, t) with s = alpha_t/alpha_n, c = sigma_t - sigma_n*s, solved by fixed-point iteration from the
+ * predictor eps(x_n, n).  One row of that iteration over numel floats, every written operation rounded once (no fma):
+ *   out = a0*base + a1*eps                         a0 = s, a1 = c; base = x_n, eps = the model's output at the current iterate
+ *   if (a2 != 0) base_out = out                    a2 = commit: the leg's last row hands its iterate on as the next base
+ * base_out is neither read nor written when a2 == 0.  out may alias base or the buffer the model read, base_out may alias base.
+ * lion_ddim_encode_update takes the coefficients by value (the eager loop; base_out may be NULL when a2 == 0);
+ * lion_chain_update_encode reads them from cur[1..3] in device memory, as lion_chain_begin_step leaves them -- the last launch
+ * of a captured step, base_out required; lion_chain_update_encode_cm is that update on base / out / base_out f32[B][N][4] and
+ * the denoiser's channel-major eps_cm f32[B][4][N], as lion_chain_update_multistep_cm reads it.
+ * LION_EINVAL before any launch: a NULL pointer (but base_out, as said), numel == 0 / B <= 0 / N <= 0, or base, eps, out or
+ * base_out not 16-byte aligned (eps_cm is read element by element and may have any alignment). */
+int lion_ddim_encode_update(const float *base, const float *eps, size_t numel, float a0, float a1, float a2, float *out,
+                            float *base_out, lionStream_t stream);
+int lion_chain_update_encode(const float *base, const float *eps, size_t numel, const float *cur, float *out, float *base_out,
+                             lionStream_t stream);
+int lion_chain_update_encode_cm(const float *base, const float *eps_cm, int B, int N, const float *cur, float *out,
+                                float *base_out, lionStream_t stream);
 /* The forward-process draw that starts a chain at an intermediate step (diffuse-denoise; sample_q of
  * utils/diffusion_pvd.py:105-113 with the scalars of iw_quantities_t :44-103):
  *   out = (m*x0) + (s*z)        two products and one sum, each rounded once (no fma)

@@ -147,6 +147,9 @@ SIGNATURES = {
                                    _vp, _vp]),
     "lion_chain_update_multistep_noise": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "lion_chain_update_multistep_noise_cm": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "lion_ddim_encode_update": (_i, [_vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp]),
+    "lion_chain_update_encode": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "lion_chain_update_encode_cm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_latent_unpack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_concat_broadcast": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lion_three_nn_interpolate_cat_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -4,7 +4,8 @@
 One denoiser evaluation of the local prior is ~500 kernel launches; the reference's samplers
 (utils/diffusion_pvd.py:224-303, :390-473) additionally issue ~10 elementwise launches, a ``torch.full`` and a
 host-side ``randn`` + H2D copy per step.  Here a captured step holds
-    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise   (DPMPP: lion_chain_update_multistep[_noise])
+    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise   (DPMPP: lion_chain_update_multistep[_noise];
+                                                                                 ENCODE: lion_chain_update_encode)
 and a chain of S steps is S replays of it.  Two things live here, apart:
   * ``CapturedStep``: warm-up, capture and replay of ANY step given as a callable -- the one capture path of the package
     (this chain, ode.OdeGraph, graph.GraphedDenoiser).  One hipGraph for models without set abstraction (the global prior);
@@ -33,6 +34,10 @@ DPMPP = 2
 # lion_chain_update_multistep_noise, which draws the step's noise like lion_chain_update_noise and reads its scale from column 7
 # of the schedule table; the chain owns `hist` like DPMPP and records its noise like DDIM / DDPM
 SDE_DPMPP = 3
+# the deterministic encoder (DiffusionDiscretized.run_ddim_forward: refined DDIM inversion, low noise -> high noise): the captured
+# step ends with lion_chain_update_encode, x <- a0*base + a1*eps and, on a leg's last row, base <- x; the chain owns `base`, the
+# state at the current leg's low end, beside `x`, the iterate the model reads.  No noise: neither the seed nor `z` is read.
+ENCODE = 4
 # tests: a list here makes every chain run append (start latent, [the noise each step drew]) -- what an eager loop needs
 # to repeat a graphed chain draw for draw (run_ddim(given_noise=...)); chains are then captured with the noise output on
 RECORD = None
@@ -224,9 +229,11 @@ class GraphedChain:
         self.cur = torch.zeros(8, device=dev)
         self.z = torch.zeros(size, device=dev) if record_noise else None   # tests: the noise each step used
         self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
+        self.base = torch.zeros(size, device=dev) if mode == ENCODE else None   # ENCODE: the state at the leg's low end
         # identity rows until run() uploads a schedule: the warm-up / capture passes must run on finite values (an
         # all-zero DDPM row is 0/0 -> the second warm-up forward would voxelize NaN latents).  For the multistep update the
-        # same row is x0 = x, D = 0, out = x, and column 7 is 0: SDE_DPMPP's warm-up draws nothing.
+        # same row is x0 = x, D = 0, out = x, and column 7 is 0: SDE_DPMPP's warm-up draws nothing.  For ENCODE it is a0 = 1,
+        # a1 = 0, commit = 1: x = base (zeros until prepare) and base = x.
         self.table[:, 0] = 1.0   # t_model
         self.table[:, 1] = 1.0   # a0: x passes through
         self.table[:, 3] = 1.0   # a2: DDPM divisor (DDIM: z has weight 1 -- finite)
@@ -264,6 +271,9 @@ class GraphedChain:
                     _lib.call("lion_chain_update_multistep_noise_cm", self.x, eps, self.hist, num_samples, n_pts, self.cur,
                               self.table, self.seed, 0, self.x, self.hist, self.z)
                     return
+                if mode == ENCODE:
+                    _lib.call("lion_chain_update_encode_cm", self.base, eps, num_samples, n_pts, self.cur, self.x, self.base)
+                    return
                 _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
                           self.z)
                 return
@@ -274,6 +284,9 @@ class GraphedChain:
             if mode == SDE_DPMPP:
                 _lib.call("lion_chain_update_multistep_noise", self.x, eps, self.hist, self.x.numel(), self.cur, self.table,
                           self.seed, 0, self.x, self.hist, self.z)
+                return
+            if mode == ENCODE:
+                _lib.call("lion_chain_update_encode", self.base, eps, self.x.numel(), self.cur, self.x, self.base)
                 return
             _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
@@ -326,6 +339,8 @@ class GraphedChain:
         self.counter.zero_()
         if self.hist is not None:
             self.hist.zero_()
+        if self.base is not None:
+            self.base.copy_(self.x)
         words = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
         self.seed.copy_(torch.from_numpy(words))
         return S

@@ -293,6 +293,57 @@ static int multistep_noise_launch(hipStream_t st, const float *x, const float *e
                                              cm_points);
 }
 
+// Deterministic encoder (refined DDIM inversion, DiffusionDiscretized.run_ddim_forward): one row of a leg n -> t from low
+// noise to high noise, one rounding per written operation:
+//   out = a0*base + a1*eps;   if (a2 != 0) base_out = out
+// (a0 = s = alpha_t/alpha_n, a1 = c = sigma_t - sigma_n*s, a2 = commit).  base is the state at the leg's low end, eps the
+// model's output at the current iterate (the predictor row evaluates it at base itself, every corrector row at the previous
+// row's out); the leg's last row commits its iterate as the next leg's base.  Coefficients from cur[1..3] where `cur` is given
+// (the captured step), else by value (the eager loop).  base_out is neither read nor written when a2 == 0.  cm_points as in
+// update_noise_kernel.  The tensors are not __restrict__: out may alias the buffer the model read (the chain's x) or base, and
+// base_out may alias base (a lane reads its quad of base and eps before it writes either output, no lane reads another's).
+__global__ void encode_kernel(const float *base, const float *eps, size_t numel, const float *__restrict__ cur, float a0,
+                              float a1, float a2, float *out, float *base_out, int cm_points) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = q * 4;
+  if (i >= numel) return;
+  if (cur) { a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; }
+  const bool commit = a2 != 0.f;
+  float bv[4], ev[4], o[4];
+  const bool full = i + 3 < numel;
+  if (full) {
+    const float4 t = *reinterpret_cast<const float4 *>(base + i);
+    bv[0] = t.x; bv[1] = t.y; bv[2] = t.z; bv[3] = t.w;
+  } else {
+    for (int j = 0; j < 4; ++j) bv[j] = i + j < numel ? base[i + j] : 0.f;
+  }
+  if (cm_points) {   // numel = B*N*4: every quad is full; eps is the denoiser's channel-major [B][4][N]
+    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
+  } else if (full) {
+    const float4 u = *reinterpret_cast<const float4 *>(eps + i);
+    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
+  } else {
+    for (int j = 0; j < 4; ++j) ev[j] = i + j < numel ? eps[i + j] : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(a0, bv[j]), mul_rn(a1, ev[j]));
+  if (full) {
+    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
+    if (commit) *reinterpret_cast<float4 *>(base_out + i) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; if (commit) base_out[i + j] = o[j]; }
+  }
+}
+
+static int encode_launch(hipStream_t st, const float *base, const float *eps, size_t numel, const float *cur, float a0, float a1,
+                         float a2, float *out, float *base_out, int cm_points) {
+  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
+  if (blocks > 0x7fffffffu) return LION_EINVAL;
+  return lion_launch<encode_kernel>((unsigned)blocks, 256, 0, st, base, eps, numel, cur, a0, a1, a2, out, base_out, cm_points);
+}
+
 // Forward-process draw out = m*x0 + s*z (sample_q, utils/diffusion_pvd.py:105-113) with the chain's generator: quad q of the
 // flat tensor takes Philox counter (q, LION_DIFFUSE_STEP_WORD, stream_id), whatever the pointers' alignment.  VEC: every pointer
 // is 16-byte aligned -> one 16-byte access per operand and full quad; else (and in the tail quad) element by element.
@@ -454,6 +505,28 @@ int lion_chain_update_multistep_noise_cm(const float *x, const float *eps_cm, co
   const float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, nullptr, (size_t)B * N * 4, cur, table, a,
                                 seed, 0, stream_id, out, hist_out, z_out, N);
+}
+
+int lion_ddim_encode_update(const float *base, const float *eps, size_t numel, float a0, float a1, float a2, float *out,
+                            float *base_out, lionStream_t stream) {
+  if (!base || !eps || !out || numel == 0) return LION_EINVAL;
+  if (!base_out && a2 != 0.f) return LION_EINVAL;
+  if (((((uintptr_t)base) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)base_out)) & 15) != 0) return LION_EINVAL;
+  return encode_launch(static_cast<hipStream_t>(stream), base, eps, numel, nullptr, a0, a1, a2, out, base_out, 0);
+}
+
+int lion_chain_update_encode(const float *base, const float *eps, size_t numel, const float *cur, float *out, float *base_out,
+                             lionStream_t stream) {
+  if (!base || !eps || !cur || !out || !base_out || numel == 0) return LION_EINVAL;
+  if (((((uintptr_t)base) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)base_out)) & 15) != 0) return LION_EINVAL;
+  return encode_launch(static_cast<hipStream_t>(stream), base, eps, numel, cur, 0.f, 0.f, 0.f, out, base_out, 0);
+}
+
+int lion_chain_update_encode_cm(const float *base, const float *eps_cm, int B, int N, const float *cur, float *out,
+                                float *base_out, lionStream_t stream) {
+  if (!base || !eps_cm || !cur || !out || !base_out || B <= 0 || N <= 0) return LION_EINVAL;
+  if (((((uintptr_t)base) | ((uintptr_t)out) | ((uintptr_t)base_out)) & 15) != 0) return LION_EINVAL;
+  return encode_launch(static_cast<hipStream_t>(stream), base, eps_cm, (size_t)B * N * 4, cur, 0.f, 0.f, 0.f, out, base_out, N);
 }
 
 int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s, const uint32_t *seed,

@@ -12,6 +12,8 @@ float32 schedule -- so for identical (x, eps_hat, z) the update is bit-identical
 ``lion_ddpm_update`` and the chain kernel share the arithmetic).  The noise STREAM differs by construction
 (Philox on the device vs torch's CPU generator): ``graph=False, noise='cpu'`` reproduces the reference's stream
 for seed-for-seed comparisons, ``graph=False`` alone the eager per-step loop.
+Beyond the reference: the few-step solvers ``run_dpm_solver`` and the deterministic encoder ``run_ddim_forward`` (a stub in the
+reference, :305-388), the inverse of the order-1 solver, on the same captured step.
 """
 from __future__ import annotations
 
@@ -291,6 +293,43 @@ class DiffusionDiscretized(object):
             h_prev = h
         return table.astype(dtype)
 
+    def encode_table(self, taus, refine=0, dtype=np.float32):
+        """[len(taus)*(1 + refine), 8] rows {t_model, s, c, commit, 0...} of the deterministic encoder (run_ddim_forward) over
+        the descending distinct indices `taus` that solver_schedule returns, walked from low noise to high noise -- what
+        lion_ddim_encode_update and the captured chain (chain.ENCODE) read:  x <- s*base + c*eps(x, t_model);  commit: base <- x.
+        With alpha = sqrt(ab), sigma = sqrt(1 - ab): the first leg takes the clean latent (alpha_low = 1, sigma_low = 0) to
+        index taus[-1] = 0 with s = alpha_0, c = sigma_0, the inverse of dpm_solver_table's final data-prediction row; every
+        later leg n -> t has s = alpha_t/alpha_n, c = sigma_t - sigma_n*s, the inverse of the order-1 row t -> n
+        (x_n = s'*x_t + c'*eps(x_t, t) solved for x_t: x_t = s*x_n + c*eps(x_t, t), an implicit equation).
+        Each leg is 1 + refine rows with the same (s, c).  Row 0, the predictor, evaluates the model where the state is known:
+        t_model = the lower index + 1 (1 on the first leg) and the model's input is base -- textbook DDIM inversion.  Rows
+        1..refine, the correctors, are fixed-point iterations of the implicit equation: t_model = the target index + 1 and the
+        model's input is the previous row's result.  commit = 1 on the leg's last row only.
+        All arithmetic in float64 on the float32 schedule widened; the result is cast to `dtype` once."""
+        refine = int(refine)
+        if refine < 0:
+            raise ValueError(f"encode_table: refine = {refine}")
+        taus = [int(t) for t in taus]
+        assert len(taus) >= 1 and taus[-1] == 0, "the last index is 0"
+        assert all(a > b for a, b in zip(taus, taus[1:])), "descending distinct indices"
+        ab, _ = self._half_logsnr()
+        alpha, sigma = np.sqrt(ab), np.sqrt(1.0 - ab)
+        table = np.zeros((len(taus) * (1 + refine), 8), np.float64)
+        low = None
+        for leg, t in enumerate(reversed(taus)):
+            if low is None:
+                s, c = alpha[t], sigma[t]
+            else:
+                s = alpha[t] / alpha[low]
+                c = sigma[t] - sigma[low] * s
+            rows = table[leg * (1 + refine):(leg + 1) * (1 + refine)]
+            rows[:, 0] = t + 1
+            rows[0, 0] = 1 if low is None else low + 1
+            rows[:, 1], rows[:, 2] = s, c
+            rows[-1, 3] = 1.0
+            low = t
+        return table.astype(dtype)
+
     def _noise(self, size, source, device):
         if source == 'cpu':  # the reference's stream: torch.randn(size).to(device), :465-466
             return torch.randn(size).to(device)
@@ -567,5 +606,61 @@ class DiffusionDiscretized(object):
                 x, hist = diffusion_ops.dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:7]])
             if keep_trajectory:
                 output_list.append(x)
+        model.train()
+        return x, output_list
+
+    @torch.no_grad()
+    def run_ddim_forward(self, dae, eps, ddim_step=20, ddim_skip_type='logsnr', condition_input=None, clip_feat=None, refine=0,
+                         graph=True, keep_trajectory=False, enable_autocast=False, conv_precision="fp32"):
+        """Deterministic few-step encoder: the latent ``eps`` [B, *shape] -> the noise x_T that regenerates it (the reference's
+        run_ddim_forward, utils/diffusion_pvd.py:305-388, is an unfinished stub of this; its name and leading arguments are kept).
+        Its decoder is ``run_dpm_solver(dae, B, shape, steps=ddim_step, order=1, skip_type=ddim_skip_type, x_noisy=x_T)``:
+        the legs of ``solver_schedule(ddim_step, ddim_skip_type)`` are walked from the clean latent up to index T-1, each leg
+        inverting the decoder's step over the same two indices (``encode_table``).
+        refine=0 is textbook DDIM inversion: one model evaluation per leg, at the leg's LOW end -- not the inverse of the
+        decoder, which evaluates at the high end.  refine=K adds K fixed-point iterations of the decoder step's implicit
+        inverse x_t = s*x_n + c*eps(x_t, t) per leg, each one more model evaluation: at most ddim_step*(1 + K) in all.  The
+        iteration contracts where |c|*Lip(eps) < 1; shown on a toy only, nothing is claimed for trained weights (DESIGN.md
+        4.6.5).
+        Returns (x_T, trajectory): trajectory the state after every leg (empty with keep_trajectory=False).  ``eps`` is never
+        written.  graph=True: replays of one captured step [prologue -> denoiser -> lion_chain_update_encode] with the
+        iterate and the leg's base in device memory (chain.ENCODE, a cache entry of its own).  Otherwise -- graph=False,
+        mixed_prediction models, autocast -- the eager loop on lion_ddim_encode_update; the two give the same bits.
+        conv_precision: as in run_ddim."""
+        with conv_ops.requested_precision(conv_precision):
+            return self._run_ddim_forward(dae, eps, ddim_step, ddim_skip_type, condition_input, clip_feat, refine, graph,
+                                          keep_trajectory, enable_autocast)
+
+    def _run_ddim_forward(self, model, eps, ddim_step, skip_type, condition_input, clip_feat, refine, graph, keep_trajectory,
+                          enable_autocast):
+        if not eps.is_cuda:
+            raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
+        table = self.encode_table(self.solver_schedule(ddim_step, skip_type), refine)
+        model.eval()
+        dev = self.device
+        num_samples, shape = eps.shape[0], list(eps.shape[1:])
+        start = eps.detach().to(dev).contiguous()
+        output_list = []
+        if graph and _chain.graphable(model, start, enable_autocast, {}):
+            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.ENCODE,
+                                  max(self._diffusion_steps, len(table)))
+            for i in range(ch.prepare(start, table, 0, condition_input, clip_feat)):   # seed 0: the step draws nothing
+                ch.replay()
+                if keep_trajectory and table[i, 3] != 0:
+                    output_list.append(ch.x.clone())
+            model.train()
+            return ch.x.clone(), output_list
+        x, base = start.clone(), start.clone()          # never the caller's tensor
+        for row in table:
+            timestep = torch.full((num_samples,), int(row[0]), dtype=torch.int64, device=dev)
+            mixing = self.get_mixing_component(x, timestep, enabled=getattr(model, 'mixed_prediction', False))
+            with torch.autocast("cuda", enabled=enable_autocast):
+                pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat)
+                eps_hat = _mixed(model, pred, mixing).float().contiguous()
+            commit = row[3] != 0
+            diffusion_ops.ddim_encode_update(base, eps_hat, float(row[1]), float(row[2]), commit, out=x,
+                                             base_out=base if commit else None)
+            if keep_trajectory and commit:
+                output_list.append(x.clone())
         model.train()
         return x, output_list

@@ -1,11 +1,12 @@
 """Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, the multistep solver
-step lion_dpmpp_update and its stochastic form lion_sde_dpmpp_update, and the forward-process draw lion_chain_diffuse."""
+step lion_dpmpp_update and its stochastic form lion_sde_dpmpp_update, the deterministic encoder's row lion_ddim_encode_update,
+and the forward-process draw lion_chain_diffuse."""
 import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "sde_dpmpp_update", "diffuse"]
+__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "sde_dpmpp_update", "ddim_encode_update", "diffuse"]
 
 
 def ddim_update(x, eps, z, s, c, sigma, out=None):
@@ -77,6 +78,21 @@ def sde_dpmpp_update(x, eps, hist, a0, a1, a2, a3, a4, a5, a6, noise=None, seed=
     _lib.call("lion_sde_dpmpp_update", x, eps, hist, noise, x.numel(), float(a0), float(a1), float(a2), float(a3), float(a4),
               float(a5), float(a6), words, int(step), int(stream_id), out, hist_out, z_out)
     return (out, hist_out, z_out) if return_noise else (out, hist_out)
+
+
+def ddim_encode_update(base, eps, s, c, commit, out=None, base_out=None):
+    """One row of the refined DDIM inversion (lion_ddim_encode_update; coefficients: DiffusionDiscretized.encode_table):
+    out = s*base + c*eps, and base_out = out where `commit` (the last row of a leg).  base_out is neither written nor allocated
+    without commit.  out may be base or the tensor the model read, base_out may be base.  Returns (out, base_out), base_out None
+    where nothing was committed and none was given."""
+    _lib.require_cuda(base, eps, out, base_out)
+    if eps.shape != base.shape:
+        raise ValueError(f"ddim_encode_update: eps {tuple(eps.shape)} for base {tuple(base.shape)}")
+    out = torch.empty_like(base) if out is None else out
+    if commit and base_out is None:
+        base_out = torch.empty_like(base)
+    _lib.call("lion_ddim_encode_update", base, eps, base.numel(), float(s), float(c), 1.0 if commit else 0.0, out, base_out)
+    return out, base_out
 
 
 def ddpm_update(x, eps, z, t_is_zero, k_outer, k_a, k_b, scale, temp, out=None):
