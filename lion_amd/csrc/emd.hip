@@ -212,8 +212,13 @@ __global__ __launch_bounds__(256) void emd_pass3_cost_kernel(const float *__rest
 //     pair, the next level's exponent is d' * (level' / level) (0.25, or 0 before the last level);
 //   * true squared distances for the cost come back as d' / s^2.
 // Sums keep their order (ascending l inside each wave's quarter of a tile, the four quarters merged in a fixed order).  The
-// weights differ from the literal expression by fp32 rounding of the exponent (<= 1e-5 relative), inside what v_exp_f32
-// itself imposes (tests: cost 1e-4, the materialised match 2e-3); lion_emd_approxmatch keeps the literal kernels.
+// weights differ from the literal expression by fp32 rounding of the exponent: x * s is rounded BEFORE the subtraction, so
+// the error of d' scales with s |x| and not with the distance.  For weights above 1e-9 and unit-cube coordinates that is up
+// to 9e-5 relative at the first level (s = 154), halving with every level (5e-6 at level -16, the literal kernels: 2e-6 to
+// 5e-6 at every level); it grows in proportion to the coordinate magnitude (3e-4 at |x| = 3.7).  fp32 emulation on the
+// host; tests/test_emd_numerics_gpu.py holds the resulting cost to 2e-4 of float64 on inputs certified as well conditioned
+// (tests/emd_ref.py), the literal path to 1e-4 and the materialised match to 2e-3.  lion_emd_approxmatch keeps the literal
+// kernels.
 __device__ __forceinline__ float sqd_fma(float ax, float ay, float az, float bx, float by, float bz) {
   const float dx = ax - bx, dy = ay - by, dz = az - bz;
   return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx));
