@@ -117,15 +117,26 @@ __global__ __launch_bounds__(256) void devox_fwd_kernel(const float *__restrict_
 // kernel: bit-exact vs the oracle.
 // ---------------------------------------------------------------------------------------------
 // SPLIT: r = 4k + 2 (the launcher asks for r^2 % 4 == 0 only), a z-row is not a whole number of 16-byte pieces.
-template <int LD, bool AFF, bool SPLIT>
+// ONE: the whole grid is one slab (XS == 1, every even r <= 20: the model's r = 8 and r = 16 calls).  These launches move
+// 8-84 MB and sat on a 10-15 us floor made of the prologue, not of bytes: row bitmap (two barriers behind a round trip to
+// the coordinates), an identity "sort" (four barriers), the coordinates loaded three times.  In this form the
+// coordinates are loaded once into registers, a lane's p-th point is tid + 256 p, and the first DMA group leaves at kernel
+// entry with EVERY row of its CI grids: no bitmap, no barrier in front of the slab loop's own.  The row filter does not
+// pay here even on clumped clouds at r = 16 (B = 32, (64, 1024, 16), us per call: with the bitmap built from the
+// registers 17.0 Gaussian / 17.5 clumped, without 13.4 / 11.8, before 19.1 / 20.0; profiles/small_grid_vox_devox_ab.txt).
+// ONE == false is the multi-slab code (r >= 22) as it was; SPLIT has no meaning without the filter (ONE: always false).
+template <int LD, bool AFF, bool SPLIT, bool ONE>
 __global__ __launch_bounds__(256) void devox_slab_kernel(
     const float *__restrict__ coords, const float *__restrict__ feat, int C, int N, int r, int PX,
-    int XS, int CT, int CI, int slab_floats, int training, float *__restrict__ out,
+    int XS_rt, int CT, int CI, int slab_floats, int training, float *__restrict__ out,
     int32_t *__restrict__ inds, float *__restrict__ wgts, const float *__restrict__ scale,
     const float *__restrict__ shift) {
+  static_assert(!(ONE && SPLIT), "the single-slab form fetches whole grids: there is no row-end rule to apply");
+  constexpr bool FILT = !ONE; // fetch only the z-rows some point reads
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *lds = reinterpret_cast<float *>(smem);
   constexpr int PP = 8;
+  const int XS = ONE ? 1 : XS_rt;
   const int tid = threadIdx.x, b = blockIdx.y, c0 = blockIdx.x * CT;
   const int nch = min(CT, C - c0);
   const int r2 = r * r, r3 = r2 * r;
@@ -161,18 +172,23 @@ __global__ __launch_bounds__(256) void devox_slab_kernel(
       // only the z-rows some point of the cloud interpolates from are fetched (43 % of them at N = 2048, r = 32;
       // a row is r floats = r/4 lanes of the 1 KiB wave instruction): inactive lanes move nothing, their LDS
       // bytes stay stale and are never read; a wave instruction without any needed row is skipped altogether
-      int row = (4 * f) / r;
-      if (XS == 1) row %= r2;
-      else row += row0;
-      bool want = f < n4 && ((need[row >> 5] >> (row & 31)) & 1u);
-      // SPLIT: every odd row starts in the middle of a piece whose first float belongs to the row before it, so the piece
-      // is needed when the row of either END is.  f < n4 keeps the last float inside the slab (XS == 1: CI whole grids,
-      // else <= PX + 1 planes: row < r^2).
-      if (SPLIT && !want && f < n4) {
-        int rowh = (4 * f + 3) / r;
-        if (XS == 1) rowh %= r2;
-        else rowh += row0;
-        want = (need[rowh >> 5] >> (rowh & 31)) & 1u;
+      bool want;
+      if (FILT) {
+        int row = (4 * f) / r;
+        if (XS == 1) row %= r2;
+        else row += row0;
+        want = f < n4 && ((need[row >> 5] >> (row & 31)) & 1u);
+        // SPLIT: every odd row starts in the middle of a piece whose first float belongs to the row before it, so the piece
+        // is needed when the row of either END is.  f < n4 keeps the last float inside the slab (XS == 1: CI whole grids,
+        // else <= PX + 1 planes: row < r^2).
+        if (SPLIT && !want && f < n4) {
+          int rowh = (4 * f + 3) / r;
+          if (XS == 1) rowh %= r2;
+          else rowh += row0;
+          want = (need[rowh >> 5] >> (rowh & 31)) & 1u;
+        }
+      } else {
+        want = f < n4; // every piece of the group; lanes beyond it move nothing and nobody reads their bytes
       }
       if (want) {
         unsigned keep;
@@ -181,53 +197,68 @@ __global__ __launch_bounds__(256) void devox_slab_kernel(
       }
     }
   };
-  // ---- which z-rows are read at all: the four (x, y) pairs of every point, with the reference's "hi = lo when the
-  // fraction is 0" rule (trilinear_devox.cu:64-66) ----
-  const int nwords = (r2 + 31) >> 5;
-  for (int w = tid; w < nwords; w += 256) need[w] = 0u;
-  __syncthreads();
-  for (int i = tid; i < N; i += 256) {
-    const float x = co[i], y = co[i + N];
-    const float xl = floorf(x), yl = floorf(y);
-    if (xl >= 0.f && yl >= 0.f && xl < (float)r && yl < (float)r) {
-      const int x0 = (int)xl, y0 = (int)yl;
-      const int x1 = min(x0 + (sub_rn(x, xl) > 0.0f ? 1 : 0), r - 1), y1 = min(y0 + (sub_rn(y, yl) > 0.0f ? 1 : 0), r - 1);
-      const int ra = x0 * r + y0, rb = x0 * r + y1, rc = x1 * r + y0, rd = x1 * r + y1;
-      atomicOr(&need[ra >> 5], 1u << (ra & 31));
-      atomicOr(&need[rb >> 5], 1u << (rb & 31));
-      atomicOr(&need[rc >> 5], 1u << (rc & 31));
-      atomicOr(&need[rd >> 5], 1u << (rd & 31));
+  float cx[PP], cy[PP], cz[PP]; // ONE: the coordinates of the lane's points, loaded once
+  if constexpr (ONE) {
+#pragma unroll
+    for (int p = 0; p < PP; ++p) {
+      const int i = tid + p * 256;
+      cx[p] = cy[p] = cz[p] = 0.f;
+      if (i < N) { cx[p] = co[i]; cy[p] = co[i + N]; cz[p] = co[i + 2 * N]; }
     }
-  }
-  __syncthreads();
-  issue(0); // in flight during the rest of the per-point setup
+    // Right behind the coordinate loads: one round trip covers both.  The per-point setup below does NOT run under the DMA:
+    // hipcc does not count the asm DMA instructions, so its vmcnt wait for the last coordinate (issued in front of them)
+    // also drains group 0.  The setup is ~100 ALU instructions per point slot; what was removed is the chain of dependent
+    // round trips and barriers in front of the DMA, not this wait.
+    issue(0);
+  } else {
+    // ---- which z-rows are read at all: the four (x, y) pairs of every point, with the reference's "hi = lo when the
+    // fraction is 0" rule (trilinear_devox.cu:64-66) ----
+    const int nwords = (r2 + 31) >> 5;
+    for (int w = tid; w < nwords; w += 256) need[w] = 0u;
+    __syncthreads();
+    for (int i = tid; i < N; i += 256) {
+      const float x = co[i], y = co[i + N];
+      const float xl = floorf(x), yl = floorf(y);
+      if (xl >= 0.f && yl >= 0.f && xl < (float)r && yl < (float)r) {
+        const int x0 = (int)xl, y0 = (int)yl;
+        const int x1 = min(x0 + (sub_rn(x, xl) > 0.0f ? 1 : 0), r - 1), y1 = min(y0 + (sub_rn(y, yl) > 0.0f ? 1 : 0), r - 1);
+        const int ra = x0 * r + y0, rb = x0 * r + y1, rc = x1 * r + y0, rd = x1 * r + y1;
+        atomicOr(&need[ra >> 5], 1u << (ra & 31));
+        atomicOr(&need[rb >> 5], 1u << (rb & 31));
+        atomicOr(&need[rc >> 5], 1u << (rc & 31));
+        atomicOr(&need[rd >> 5], 1u << (rd & 31));
+      }
+    }
+    __syncthreads();
+    issue(0); // in flight during the rest of the per-point setup
 
-  // ---- group the points by x-slab so that a wave's lanes are active together (a lane's p-th point is
-  // sorted[tid + 256 p]); the order inside a slab is irrelevant (points are independent) ----
-  for (int s2 = tid; s2 < XS; s2 += 256) scnt[s2] = 0;
-  __syncthreads();
-  int sl0[PP];
+    // ---- group the points by x-slab so that a wave's lanes are active together (a lane's p-th point is
+    // sorted[tid + 256 p]); the order inside a slab is irrelevant (points are independent) ----
+    for (int s2 = tid; s2 < XS; s2 += 256) scnt[s2] = 0;
+    __syncthreads();
+    int sl0[PP];
 #pragma unroll
-  for (int p = 0; p < PP; ++p) {
-    const int i = tid + p * 256;
-    sl0[p] = -1;
-    if (i < N) {
-      sl0[p] = min(max((int)floorf(co[i]) / PX, 0), XS - 1);
-      if (XS > 1) atomicAdd(&scnt[sl0[p]], 1);
+    for (int p = 0; p < PP; ++p) {
+      const int i = tid + p * 256;
+      sl0[p] = -1;
+      if (i < N) {
+        sl0[p] = min(max((int)floorf(co[i]) / PX, 0), XS - 1);
+        if (XS > 1) atomicAdd(&scnt[sl0[p]], 1);
+      }
     }
-  }
-  __syncthreads();
-  if (tid == 0) { // exclusive scan of <= 64 counters
-    int run = 0;
-    for (int s2 = 0; s2 < XS; ++s2) { const int c = scnt[s2]; scnt[s2] = run; run += c; }
-  }
-  __syncthreads();
+    __syncthreads();
+    if (tid == 0) { // exclusive scan of <= 64 counters
+      int run = 0;
+      for (int s2 = 0; s2 < XS; ++s2) { const int c = scnt[s2]; scnt[s2] = run; run += c; }
+    }
+    __syncthreads();
 #pragma unroll
-  for (int p = 0; p < PP; ++p) {
-    const int i = tid + p * 256;
-    if (i < N) sorted[XS > 1 ? atomicAdd(&scnt[sl0[p]], 1) : i] = (uint16_t)i;
+    for (int p = 0; p < PP; ++p) {
+      const int i = tid + p * 256;
+      if (i < N) sorted[XS > 1 ? atomicAdd(&scnt[sl0[p]], 1) : i] = (uint16_t)i;
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
   int ix0[PP], xsl[PP], pid[PP];
   float xd1[PP], yd1[PP], zd1[PP];
@@ -239,9 +270,9 @@ __global__ __launch_bounds__(256) void devox_slab_kernel(
     pid[p] = 0;
     xd1[p] = yd1[p] = zd1[p] = 0.f;
     if (k < N) {
-      const int i = sorted[k];
+      const int i = ONE ? k : (int)sorted[k];
       pid[p] = i;
-      const float x = co[i], y = co[i + N], z = co[i + 2 * N];
+      const float x = ONE ? cx[p] : co[i], y = ONE ? cy[p] : co[i + N], z = ONE ? cz[p] : co[i + 2 * N];
       const Corners kk = corners_of(x, y, z, r, r2);
       if (training && blockIdx.x == 0) {
 #pragma unroll
@@ -769,13 +800,20 @@ static int devox_launch(const float *coords, const float *feat, int B, int C, in
     int CT = 4 * CI;
     while (CT > CI && (long)B * lion_cdiv(C, CT) < 512) CT >>= 1;
     dim3 grid(lion_cdiv(C, CT), B);
-    auto slab = [&](auto LD) {
-      return lion_with_flags(scale != nullptr, (r & 3) != 0, [&](auto AFFINE, auto SPLIT) {
-        return lion_launch<devox_slab_kernel<decltype(LD)::value, decltype(AFFINE)::value, decltype(SPLIT)::value>>(
+    auto slab = [&](auto LD, auto SPLIT, auto ONE) {
+      return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
+        return lion_launch<devox_slab_kernel<decltype(LD)::value, decltype(AFFINE)::value, decltype(SPLIT)::value,
+                                             decltype(ONE)::value>>(
             grid, 256, lds, st, coords, feat, C, N, r, PX, XS, CT, CI, slab_floats, training, out, inds, wgts, scale, shift);
       });
     };
-    return ld <= 1 ? slab(IntC<1>{}) : ld <= 2 ? slab(IntC<2>{}) : ld <= 4 ? slab(IntC<4>{}) : slab(IntC<9>{});
+    // several slabs: PX + 1 = planes_max planes are more than 9216 - r^2 >= 4608 floats, so ld is always 9
+    if (XS > 1) {
+      if (ld != 9) return LION_EUNSUPPORTED;
+      return (r & 3) != 0 ? slab(IntC<9>{}, BoolC<true>{}, BoolC<false>{}) : slab(IntC<9>{}, BoolC<false>{}, BoolC<false>{});
+    }
+    return ld <= 1 ? slab(IntC<1>{}, BoolC<false>{}, BoolC<true>{}) : ld <= 2 ? slab(IntC<2>{}, BoolC<false>{}, BoolC<true>{})
+         : ld <= 4 ? slab(IntC<4>{}, BoolC<false>{}, BoolC<true>{}) : slab(IntC<9>{}, BoolC<false>{}, BoolC<true>{});
   }
   const int pt = lion_cdiv(N, 256);
   // channel tile: keep >= ~2048 workgroups in flight, amortise the corner computation

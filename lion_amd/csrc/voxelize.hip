@@ -436,6 +436,16 @@ __global__ __launch_bounds__(VT) void vox_fused_kernel(
                           arena_words, ch_cap);
 }
 
+// lion_voxel_scatter_read: is z-row `row` = d * r + h of a cloud's grid inside the halo (one voxel in d and h) of a tile with a
+// point within one voxel?  fl: the cloud's tile flags (lion_conv3d_tile_occupancy, margin 1), tiles of TD x TH z-rows, nth = r / TH.
+__device__ __forceinline__ bool vox_row_has_reader(const int32_t *fl, int row, int r, int TD, int TH, int nth) {
+  const int d = row / r, h = row % r;
+  int need = 0;
+  for (int dd = max(d - 1, 0); dd <= min(d + 1, r - 1); ++dd)
+    for (int hh = max(h - 1, 0); hh <= min(h + 1, r - 1); ++hh) need |= fl[(dd / TD) * nth + hh / TH] & 0xf;
+  return need != 0;
+}
+
 // vox_scatter_kernel: phases B + C from a stored plan.  LDS (dynamic): slot[SV] | ust[n_words] | arena.
 template <int NP, bool READ>
 __global__ __launch_bounds__(VT) void vox_scatter_kernel(
@@ -463,6 +473,53 @@ __global__ __launch_bounds__(VT) void vox_scatter_kernel(
   // one -- keeps the old assignment.  Same arithmetic per (voxel, channel): bit-identical.
   const int c_per = (C + CS - 1) / CS, cg_lo = cs * c_per, cg_hi = min(C, cg_lo + c_per);
   if (cg_lo >= cg_hi) return;
+  if constexpr (NP == 1) {
+    // Clouds of <= 1024 points: one point per thread, a slab has at most min(N, SV) <= 1024 occupied voxels -- one per thread --
+    // and nobody adopts chunks (below).  These launches move little and were bound by their prologue: headers -> barrier ->
+    // slot table -> barrier -> the occupied voxels' loads, whose count came from the header -> barrier.  Here everything the
+    // workgroup reads in front of phase B leaves in ONE round trip -- the cloud's headers, the point's (position, 1 / count),
+    // the occupied voxels' (start | count) and ids clamped to min(N, SV) instead of the header's count, for READ the tile
+    // flags around the slab's rows -- the slot table is initialised under it, and one barrier (that waits for no memory)
+    // separates the table from its occupied entries.  The headers stay in lanes: lane `slab` is read with a lane broadcast.
+    const int ls = tid & 63;
+    int l_pts = 0, l_occ = 0;
+    if (ls < S) {
+      const int32_t *hs = pl.hdr + ((size_t)b * S + ls) * 4;
+      l_pts = hs[0];
+      l_occ = hs[1];
+    }
+    const int i = min(tid, N - 1);
+    const int posw = tid < N ? pl.pos[(size_t)b * N + i] : -1;   // (slab field 0xffff: nobody's)
+    const float invw = pl.inv[(size_t)b * N + i];
+    const int uc = min(tid, min(N, SV) - 1);                     // past the slab's occupied voxels: loaded, not used
+    const int u_st = pl.ust[((size_t)b * S + slab) * n_words + uc], u_vl = pl.uvl[((size_t)b * S + slab) * n_words + uc];
+    if constexpr (READ) {
+      // (see the READ block below: a z-row outside the halo of every occupied tile gets slot -2) -- the thread that
+      // decides a row writes the row's slots itself (r in {16, 32}: whole 16-byte groups)
+      const int nth = r / TH, ntiles = (r / TD) * nth, row0 = (slab * SV) / r, nrows = SV / r;
+      const int32_t *fl = occ_flags + (size_t)b * ntiles;
+      for (int q = tid; q < nrows; q += VT) {
+        const int sv = vox_row_has_reader(fl, row0 + q, r, TD, TH, nth) ? -1 : -2;
+        for (int z = 0; z < r; z += 4) *reinterpret_cast<int4 *>(slot + q * r + z) = make_int4(sv, sv, sv, sv);
+      }
+    } else {
+      for (int v = tid; v < SV; v += VT) slot[v] = -1;
+    }
+    // the bare barrier: __syncthreads() carries a fence that would wait here for the loads in flight
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const int my_pts = __builtin_amdgcn_readlane(l_pts, slab), my_occ = __builtin_amdgcn_readlane(l_occ, slab);
+    if (tid < my_occ) {
+      ust[tid] = u_st;
+      slot[u_vl] = tid;
+    }
+    const bool mine = (posw >> 16) == slab;
+    const int posv[1] = {mine ? (posw & 0xffff) : -1};
+    const float invp[1] = {mine ? invw : 0.f};
+    // (the first barrier of vox_means_and_store stands between these writes and their readers)
+    vox_means_and_store<1, READ>(feat, out, b, C, N, r3, slab * SV, SV, cs, CS, my_pts, my_occ, posv, invp, slot, ust, arena,
+                                 arena_words, ch_cap, cg_lo, cg_hi);
+    return;
+  }
   // one round trip for the cloud's S headers: lane s of every wave holds slab s's (points, occupied voxels, channels per
   // chunk, chunks); the scans below read them with lane broadcasts
   int l_pts = 0, l_occ = 0, l_chm = 1, l_nc = 0;
@@ -552,13 +609,7 @@ __global__ __launch_bounds__(VT) void vox_scatter_kernel(
     __shared__ unsigned char rowneed[1024];   // rows of this slab (SV / r <= 1024)
     const int nth = r / TH, ntiles = (r / TD) * nth, row0 = (slab_u * SV) / r, nrows = SV / r;
     const int32_t *fl = occ_flags + (size_t)b * ntiles;
-    for (int q = tid; q < nrows; q += VT) {
-      const int d = (row0 + q) / r, h = (row0 + q) % r;
-      int need = 0;
-      for (int dd = max(d - 1, 0); dd <= min(d + 1, r - 1); ++dd)
-        for (int hh = max(h - 1, 0); hh <= min(h + 1, r - 1); ++hh) need |= fl[(dd / TD) * nth + hh / TH] & 0xf;
-      rowneed[q] = need != 0;
-    }
+    for (int q = tid; q < nrows; q += VT) rowneed[q] = vox_row_has_reader(fl, row0 + q, r, TD, TH, nth);
     __syncthreads();
     for (int v = tid; v < SV; v += VT) slot[v] = rowneed[v / r] ? -1 : -2;
   } else {
@@ -866,6 +917,11 @@ static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_b
   if (two_per_cu) {
     int CS = 1;
     while ((long)B * p.S * CS < 512 && C / (CS * 2) >= 8) CS *= 2;
+    // ... but a 1024-thread workgroup that stores fewer than 8192 floats is mostly launch and prologue: it takes twice the
+    // channels as long as one workgroup per CU remains.  r = 8, B = 32, C = 128 (512 workgroups of 8 channels -> 256 of 16):
+    // 10.3 -> 7.7 us per launch; a plain "256 workgroups" rule costs the r = 16 calls (8 slabs, 128 channels) 28 -> 34 us
+    // (profiles/small_grid_vox_devox_ab.txt).
+    while (CS > 1 && (long)p.SV * ((C + CS - 1) / CS) < 8192 && (long)B * p.S * (CS / 2) >= 256) CS /= 2;
     p.CS = CS;
   }
   // (the static LDS of the reader-aware instantiation -- its 1-KiB row map -- comes out of the same budget)
