@@ -8,7 +8,10 @@
 //   D = main + corr / 2048                                   (the dropped W_l * X_l term is 2^-22 relative)
 // costs 3 MFMAs of 32 cycles per K = 16 instead of 8 fp32 MFMAs of 64 cycles.  Measured error vs a float64
 // convolution: 2.6e-7 rms of the output rms (the fp32 MFMA chain's own: 5e-7 -- it rounds the accumulator 8x more
-// often); tests/test_conv_split_gpu.py holds it to the SAME bounds as the fp32 kernel.
+// often).  tests/test_conv_split_gpu.py holds the dense forms at model shapes and the adversarial dynamic ranges (on the
+// r = 16, CB = 2 tile) to the fp32 kernel's 5e-6 of max |y|; tests/test_conv3d_split_numerics_gpu.py holds every plan, form,
+// Cin edge, the dynamic ranges on the r = 8 kernel and the CB = 1 tile, and the sparse / constant + delta forms at the three
+// consumer-aware levels to the derived elementwise and per-tile bounds of tests/conv3d_split_ref.py.
 //
 // Range (fp16 has 5 exponent bits): both operands are block-scaled by exact powers of two.
 //   weights: one scale per tensor, chosen at pack time so that max |w| * 2^ew lies in [2^13, 2^14);

@@ -1,9 +1,16 @@
 """-m gpu: the split-operand 3x3x3 convolution (csrc/conv3d_split.hip: fp16 x 2 pieces on the 16-bit MFMA pipe, power-of-
 two block scaling) held to the SAME bounds as the exact-fp32 MFMA kernel -- max error < 5e-6 of the output's maximum
-against a float64 convolution of the same fp32 operands -- in every mode (plain, AdaGN+Swish prologue + GroupNorm sums,
-sparse, constant + delta), and on adversarial dynamic ranges where a naive fp16 cut would overflow, flush or lose the
-residual: values beyond 65504, 1e-30, nine decades inside one tensor, samples of very different magnitude in one batch,
-tiny / huge weights.  The fp32 kernel is the fallback (Cin % 16 != 0) and the reference arm of these tests."""
+against a float64 convolution of the same fp32 operands -- in the dense modes (plain, AdaGN+Swish prologue + GroupNorm
+sums) at model shapes, and on adversarial dynamic ranges where a naive fp16 cut would overflow, flush or lose the residual:
+values beyond 65504, 1e-30, nine decades inside one tensor, samples of very different magnitude in one batch, tiny / huge
+weights -- these on ONE plan of the tile kernel (64 -> 64, r = 16: (4, 4, 16) tiles, CB = 2); and the whole denoiser with
+the split kernel against the fp32 kernel (sparse / delta modes active, to 1e-4).  The fp32 kernel is the fallback
+(Cin % 16 != 0) and the reference arm of these tests.
+What is NOT here: every plan (r = 8 pipelined kernel, CB = 1 / 2 tiles) in its four forms, the edges of Cin, the dynamic
+ranges on the r = 8 kernel and the CB = 1 tile, and the sparse and constant + delta forms at the three consumer-aware levels,
+all per element / per tile under derived bounds -- tests/test_conv3d_split_numerics_gpu.py (bounds, plan and emulation:
+tests/conv3d_split_ref.py, tests/test_conv3d_split_reference_cpu.py); one sparse launch with more items than resident
+workgroups -- tests/test_conv3d_numerics_gpu.py; sparse == dense at model level -- tests/test_hip_parity_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F
