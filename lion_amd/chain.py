@@ -4,8 +4,7 @@
 One denoiser evaluation of the local prior is ~500 kernel launches; the reference's samplers
 (utils/diffusion_pvd.py:224-303, :390-473) additionally issue ~10 elementwise launches, a ``torch.full`` and a
 host-side ``randn`` + H2D copy per step.  Here a captured step holds
-    lion_chain_begin_step  ->  denoiser forward  ->  lion_chain_update_noise   (DPMPP: lion_chain_update_multistep[_noise];
-                                                                                 ENCODE: lion_chain_update_encode)
+    lion_chain_begin_step  ->  denoiser forward  ->  the mode's update kernel (UPDATE below)
 and a chain of S steps is S replays of it.  Two things live here, apart:
   * ``CapturedStep``: warm-up, capture and replay of ANY step given as a callable -- the one capture path of the package
     (this chain, ode.OdeGraph, graph.GraphedDenoiser).  One hipGraph for models without set abstraction (the global prior);
@@ -26,18 +25,24 @@ import torch
 
 from . import _lib, _wcache
 
-DDIM, DDPM = 0, 1
-# the deterministic multistep solver DPM-Solver++(2M) (DiffusionDiscretized.run_dpm_solver): the captured step ends with
-# lion_chain_update_multistep instead of lion_chain_update_noise, and the chain also owns `hist`, the previous step's data prediction
-DPMPP = 2
-# its stochastic form SDE-DPM-Solver++(2M) (run_dpm_solver(stochastic=True)): the captured step ends with
-# lion_chain_update_multistep_noise, which draws the step's noise like lion_chain_update_noise and reads its scale from column 7
-# of the schedule table; the chain owns `hist` like DPMPP and records its noise like DDIM / DDPM
-SDE_DPMPP = 3
-# the deterministic encoder (DiffusionDiscretized.run_ddim_forward: refined DDIM inversion, low noise -> high noise): the captured
-# step ends with lion_chain_update_encode, x <- a0*base + a1*eps and, on a leg's last row, base <- x; the chain owns `base`, the
-# state at the current leg's low end, beside `x`, the iterate the model reads.  No noise: neither the seed nor `z` is read.
-ENCODE = 4
+# The chain's modes.  DDIM / DDPM: run_ddim / the ancestral chain and its tails.  DPMPP: the deterministic multistep solver
+# DPM-Solver++(2M) (run_dpm_solver); the chain also owns `hist`, the previous step's data prediction.  SDE_DPMPP: its stochastic
+# form (run_dpm_solver(stochastic=True)), which draws the step's noise like DDIM / DDPM and reads its scale from column 7 of the
+# schedule table.  ENCODE: the deterministic encoder (run_ddim_forward: refined DDIM inversion, low noise -> high noise),
+# x <- a0*base + a1*eps and, on a leg's last row, base <- x; the chain owns `base`, the state at the current leg's low end, beside
+# `x`, the iterate the model reads.  DPMPP and ENCODE draw nothing: neither the seed nor `z` is read.
+DDIM, DDPM, DPMPP, SDE_DPMPP, ENCODE = range(5)
+# The kernel that ends a mode's captured step: the entry point and its arguments in order.  A name is that buffer of the chain
+# (`z`: None unless the noise is recorded), a number goes as it is (the update's mode; Philox stream 0), "eps" is the model's
+# output and "size" the element count -- where the model hands back its channel-major output (`cm_out`) the entry point is the
+# "_cm" one of the same name and takes (num_samples, n_pts) there instead.
+UPDATE = {
+    DDIM: ("lion_chain_update_noise", (DDIM, "x", "eps", "size", "cur", "seed", 0, "x", "z")),
+    DDPM: ("lion_chain_update_noise", (DDPM, "x", "eps", "size", "cur", "seed", 0, "x", "z")),
+    DPMPP: ("lion_chain_update_multistep", ("x", "eps", "hist", "size", "cur", "x", "hist")),
+    SDE_DPMPP: ("lion_chain_update_multistep_noise", ("x", "eps", "hist", "size", "cur", "table", "seed", 0, "x", "hist", "z")),
+    ENCODE: ("lion_chain_update_encode", ("base", "eps", "size", "cur", "x", "base")),
+}
 # tests: a list here makes every chain run append (start latent, [the noise each step drew]) -- what an eager loop needs
 # to repeat a graphed chain draw for draw (run_ddim(given_noise=...)); chains are then captured with the noise output on
 RECORD = None
@@ -227,7 +232,7 @@ class GraphedChain:
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.seed = torch.zeros(2, dtype=torch.int32, device=dev)   # two 32-bit words of the Philox key
         self.cur = torch.zeros(8, device=dev)
-        self.z = torch.zeros(size, device=dev) if record_noise else None   # tests: the noise each step used
+        self.z = torch.zeros(size, device=dev) if record_noise and mode != ENCODE else None   # tests: the noise each step used
         self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
         self.base = torch.zeros(size, device=dev) if mode == ENCODE else None   # ENCODE: the state at the leg's low end
         # identity rows until run() uploads a schedule: the warm-up / capture passes must run on finite values (an
@@ -260,35 +265,15 @@ class GraphedChain:
             else:
                 _lib.call("lion_chain_begin_step", self.table, self.capacity, self.counter, self.t, num_samples, self.cur)
             if self.cm_out:
-                eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, channel_major_out=True,
-                            **extra).float().contiguous()
-                assert tuple(eps.shape) == (num_samples, n_cls, n_pts)
-                if mode == DPMPP:
-                    _lib.call("lion_chain_update_multistep_cm", self.x, eps, self.hist, num_samples, n_pts, self.cur, self.x,
-                              self.hist)
-                    return
-                if mode == SDE_DPMPP:
-                    _lib.call("lion_chain_update_multistep_noise_cm", self.x, eps, self.hist, num_samples, n_pts, self.cur,
-                              self.table, self.seed, 0, self.x, self.hist, self.z)
-                    return
-                if mode == ENCODE:
-                    _lib.call("lion_chain_update_encode_cm", self.base, eps, num_samples, n_pts, self.cur, self.x, self.base)
-                    return
-                _lib.call("lion_chain_update_noise_cm", mode, self.x, eps, num_samples, n_pts, self.cur, self.seed, 0, self.x,
-                          self.z)
-                return
+                extra["channel_major_out"] = True
             eps = model(x=self.x, t=self.t, condition_input=self.cond, clip_feat=self.clip, **extra).float().contiguous()
-            if mode == DPMPP:
-                _lib.call("lion_chain_update_multistep", self.x, eps, self.hist, self.x.numel(), self.cur, self.x, self.hist)
-                return
-            if mode == SDE_DPMPP:
-                _lib.call("lion_chain_update_multistep_noise", self.x, eps, self.hist, self.x.numel(), self.cur, self.table,
-                          self.seed, 0, self.x, self.hist, self.z)
-                return
-            if mode == ENCODE:
-                _lib.call("lion_chain_update_encode", self.base, eps, self.x.numel(), self.cur, self.x, self.base)
-                return
-            _lib.call("lion_chain_update_noise", mode, self.x, eps, self.x.numel(), self.cur, self.seed, 0, self.x, self.z)
+            assert not self.cm_out or tuple(eps.shape) == (num_samples, n_cls, n_pts)
+            entry, spec = UPDATE[mode]
+            given = {"eps": [eps], "size": [num_samples, n_pts] if self.cm_out else [self.x.numel()]}
+            args = []
+            for a in spec:
+                args += given[a] if a in given else [getattr(self, a) if isinstance(a, str) else a]
+            _lib.call(entry + ("_cm" if self.cm_out else ""), *args)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
 
     def matches(self, condition_input, clip_feat):
@@ -296,10 +281,12 @@ class GraphedChain:
 
     @torch.no_grad()
     def run(self, x_init, table: np.ndarray, seed: int, condition_input=None, clip_feat=None, trajectory=None,
-            trajectory_before_last=False, noise_trajectory=None, state_hook=None):
+            trajectory_before_last=False, noise_trajectory=None, state_hook=None, trajectory_rows=None):
         """x_init: the chain's start; table [S, 8] float32 rows {t_model, a0..a5, a6} (a6: SDE_DPMPP's noise scale, 0 in
-        every other mode).  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after every step (before the last
-        step's update if `trajectory_before_last`, as run_denoising_diffusion reports it).
+        every other mode).  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after
+        every step (before the last step's update if `trajectory_before_last`, as run_denoising_diffusion reports it); with
+        `trajectory_rows(i)`, a predicate on the step's index, only after the steps it holds for (the encoder: a leg's last
+        row).
         `state_hook(i, x)`: called before step i's replay with the chain's latent buffer, which it may overwrite IN PLACE
         with launches on the current stream (no host synchronisation): inpainting / known-region replacement, or a
         benchmark forcing the states a trained model would visit (bench.py's forced clouds)."""
@@ -315,7 +302,8 @@ class GraphedChain:
             self.replay()
             if noise_trajectory is not None and self.z is not None:
                 noise_trajectory.append(self.z.clone())
-            if trajectory is not None and not (trajectory_before_last and i == S - 1):
+            if trajectory is not None and not (trajectory_before_last and i == S - 1) \
+                    and (trajectory_rows is None or trajectory_rows(i)):
                 trajectory.append(self.x.clone())
         return self.x.clone()
 

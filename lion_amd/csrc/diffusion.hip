@@ -72,6 +72,39 @@ __device__ __forceinline__ void normal4(uint64_t quad, uint32_t step, uint32_t s
   }
 }
 
+// ---- quad I/O: lane q of an update kernel owns elements i = 4q .. 4q+3 of every flat tensor ------------------------------
+// `full`: the quad lies below numel and the pointer is 16-byte aligned -> one 16-byte access; else element by element, the
+// elements at or past numel read as 0 and are not written.
+__device__ __forceinline__ void load_quad(const float *p, size_t i, size_t numel, bool full, float v[4]) {
+  if (full) {
+    const float4 t = *reinterpret_cast<const float4 *>(p + i);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    for (int j = 0; j < 4; ++j) v[j] = i + j < numel ? p[i + j] : 0.f;
+  }
+}
+
+// eps is flat like x, or (cm_points = N != 0) the denoiser's channel-major output [B][4][N] beside the point-major latent
+// x [B][N][4]: quad q = (b, n) takes its four channels from four rows -- the permute(0, 2, 1).contiguous() copy of the model's
+// output folded into this read.  numel = B*N*4 there: every quad is full.
+__device__ __forceinline__ void load_eps_quad(const float *eps, size_t q, size_t numel, bool full, int cm_points, float v[4]) {
+  if (cm_points) {
+    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
+  } else {
+    load_quad(eps, q * 4, numel, full, v);
+  }
+}
+
+__device__ __forceinline__ void store_quad(float *p, size_t i, size_t numel, bool full, const float v[4]) {
+  if (full) {
+    *reinterpret_cast<float4 *>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int j = 0; j < 4 && i + j < numel; ++j) p[i + j] = v[j];
+  }
+}
+
 __global__ void begin_step_kernel(const float *__restrict__ table, int n_steps, int32_t *counter,
                                   float *__restrict__ t_out, int B, float *__restrict__ cur,
                                   const float *__restrict__ temb_table, int temb_width, float *__restrict__ temb_out) {
@@ -108,21 +141,8 @@ __global__ void update_noise_kernel(const float *__restrict__ x, const float *__
   normal4(q, step, stream_id, seed, z);
   float xv[4], ev[4], o[4];
   const bool full = i + 3 < numel;
-  if (cm_points) {
-    // x is [B][N][4] (point-major latent), eps the denoiser's channel-major output [B][4][N]: quad q = (b, n) takes its four
-    // channels from four rows -- the permute(0, 2, 1).contiguous() copy of the model's output folded into this read
-    const float4 t = *reinterpret_cast<const float4 *>(x + i);
-    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
-  } else if (full) {
-    const float4 t = *reinterpret_cast<const float4 *>(x + i), u = *reinterpret_cast<const float4 *>(eps + i);
-    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
-  } else {
-    for (int j = 0; j < 4; ++j) { xv[j] = i + j < numel ? x[i + j] : 0.f; ev[j] = i + j < numel ? eps[i + j] : 0.f; }
-  }
+  load_quad(x, i, numel, full, xv);
+  load_eps_quad(eps, q, numel, full, cm_points, ev);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (MODE == 0) {
@@ -133,17 +153,32 @@ __global__ void update_noise_kernel(const float *__restrict__ x, const float *__
       o[j] = add_rn(mul_rn(a0, sub_rn(xv[j], div_rn(mul_rn(a1, ev[j]), a2))), mul_rn(mul_rn(a3, z[j]), a4));
     }
   }
-  if (full) {
-    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    if (z_out) *reinterpret_cast<float4 *>(z_out + i) = make_float4(z[0], z[1], z[2], z[3]);
-  } else {
-    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; if (z_out) z_out[i + j] = z[j]; }
-  }
+  store_quad(out, i, numel, full, o);
+  if (z_out) store_quad(z_out, i, numel, full, z);
 }
 
-static int update_noise_launch(int mode, unsigned blocks, hipStream_t st, const float *x, const float *eps, size_t numel,
+// ---- host side of the quad kernels ---------------------------------------------------------------------------------------
+// every pointer is 16-byte aligned (torch allocations are 256-byte aligned); NULL counts as aligned
+static bool aligned16(std::initializer_list<const void *> ptrs) {
+  uintptr_t bits = 0;
+  for (const void *p : ptrs) bits |= (uintptr_t)p;
+  return (bits & 15) == 0;
+}
+
+// numel elements, one quad per lane, 256 lanes per block: LION_OK and the grid, or LION_EINVAL (no elements, or more blocks
+// than a grid's x dimension holds)
+static int quad_blocks(size_t numel, unsigned *blocks) {
+  const size_t quads = (numel + 3) / 4, n = (quads + 255) / 256;
+  if (numel == 0 || n > 0x7fffffffu) return LION_EINVAL;
+  *blocks = (unsigned)n;
+  return LION_OK;
+}
+
+static int update_noise_launch(int mode, hipStream_t st, const float *x, const float *eps, size_t numel,
                                const float *cur, const uint32_t *seed, uint32_t stream_id, float *out, float *z_out,
                                int cm_points) {
+  unsigned blocks;
+  if (quad_blocks(numel, &blocks) != LION_OK) return LION_EINVAL;
   return mode == 0 ? lion_launch<update_noise_kernel<0>>(blocks, 256, 0, st, x, eps, numel, cur, seed, stream_id, out, z_out,
                                                          cm_points)
                    : lion_launch<update_noise_kernel<1>>(blocks, 256, 0, st, x, eps, numel, cur, seed, stream_id, out, z_out,
@@ -152,118 +187,31 @@ static int update_noise_launch(int mode, unsigned blocks, hipStream_t st, const 
 
 // DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2) in data-prediction form, one rounding per written operation:
 //   x0 = a0*(x - a1*eps);   D = a5 == 0 ? a4*x0 : a4*x0 + a5*hist;   out = a2*x + a3*D;   hist_out = x0
-// (a = {1/alpha_t, sigma_t, sigma_n/sigma_t, -alpha_n*expm1(-h), 1 + 1/(2r), -1/(2r)}).  The coefficients come from cur[1..6]
-// in device memory where `cur` is given (the captured step), else from the by-value copies (the eager loop).  hist is NOT read
-// when a5 == 0 (first step, order 1, last step): it may then be NULL or hold anything.  No noise.  cm_points as in
-// update_noise_kernel.  The tensors are not __restrict__: out may alias x and hist_out may alias hist (a lane reads its quad of
-// both before it writes either, no lane reads another's).
-__global__ void multistep_kernel(const float *x, const float *eps, const float *hist, size_t numel,
-                                 const float *__restrict__ cur, float a0, float a1, float a2, float a3, float a4, float a5,
-                                 float *out, float *hist_out, int cm_points) {
+// (a = {1/alpha_t, sigma_t, sigma_n/sigma_t, -alpha_n*expm1(-h), 1 + 1/(2r), -1/(2r)}).  hist is NOT read when a5 == 0 (first
+// step, order 1, last step): it may then be NULL or hold anything.  The tensors are not __restrict__: out may alias x and
+// hist_out may alias hist (a lane reads every quad it needs before its first store, no lane reads another's).
+// NOISE (the stochastic form below): out gains + a6*z where a6 != 0; without it z_in, a6, the seed, step, stream_id and z_out
+// are not looked at and nothing of that path is compiled in.
+template <bool NOISE>
+__device__ __forceinline__ void multistep_body(const float *x, const float *eps, const float *hist, const float *z_in,
+                                               size_t numel, float a0, float a1, float a2, float a3, float a4, float a5,
+                                               float a6, const uint32_t *__restrict__ seed_words, uint32_t step,
+                                               uint32_t stream_id, float *out, float *hist_out, float *z_out, int cm_points) {
   const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = q * 4;
   if (i >= numel) return;
-  if (cur) { a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; a3 = cur[4]; a4 = cur[5]; a5 = cur[6]; }
-  const bool second = a5 != 0.f;
-  float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, o[4], p[4];
-  const bool full = i + 3 < numel;
-  if (full) {
-    const float4 t = *reinterpret_cast<const float4 *>(x + i);
-    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-    if (second) {
-      const float4 h = *reinterpret_cast<const float4 *>(hist + i);
-      hv[0] = h.x; hv[1] = h.y; hv[2] = h.z; hv[3] = h.w;
-    }
-  } else {
-    for (int j = 0; j < 4; ++j) { xv[j] = i + j < numel ? x[i + j] : 0.f; hv[j] = second && i + j < numel ? hist[i + j] : 0.f; }
-  }
-  if (cm_points) {   // numel = B*N*4: every quad is full; eps is the denoiser's channel-major [B][4][N]
-    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
-  } else if (full) {
-    const float4 u = *reinterpret_cast<const float4 *>(eps + i);
-    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
-  } else {
-    for (int j = 0; j < 4; ++j) ev[j] = i + j < numel ? eps[i + j] : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    p[j] = mul_rn(a0, sub_rn(xv[j], mul_rn(a1, ev[j])));
-    float d = mul_rn(a4, p[j]);
-    if (second) d = add_rn(d, mul_rn(a5, hv[j]));
-    o[j] = add_rn(mul_rn(a2, xv[j]), mul_rn(a3, d));
-  }
-  if (full) {
-    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4 *>(hist_out + i) = make_float4(p[0], p[1], p[2], p[3]);
-  } else {
-    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; hist_out[i + j] = p[j]; }
-  }
-}
-
-static int multistep_launch(hipStream_t st, const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
-                            const float a[6], float *out, float *hist_out, int cm_points) {
-  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
-  if (blocks > 0x7fffffffu) return LION_EINVAL;
-  return lion_launch<multistep_kernel>((unsigned)blocks, 256, 0, st, x, eps, hist, numel, cur, a[0], a[1], a[2], a[3], a[4],
-                                       a[5], out, hist_out, cm_points);
-}
-
-// SDE-DPM-Solver++(2M) (Lu et al. 2022, the SDE form of Algorithm 2): multistep_kernel's reads and its first three operations,
-// then one Gaussian term, one rounding per written operation:
-//   x0 = a0*(x - a1*eps);   D = a5 == 0 ? a4*x0 : a4*x0 + a5*hist;   hist_out = x0
-//   out = a6 != 0 ? (a2*x + a3*D) + a6*z : a2*x + a3*D
-// (a2 = (sigma_n/sigma_t)*exp(-h), a3 = -alpha_n*expm1(-2h), a6 = sigma_n*sqrt(-expm1(-2h))).  With `cur` (the captured step)
-// a0..a5 are cur[1..6], the step word is cur[7] (the step's index, as begin_step leaves it) and a6 = table[8*step + 7]; else
-// all come by value (the eager loop).  z = z_in where given, else normal4 at counter (quad, step word, stream_id) under the
-// seed in device memory: update_noise_kernel's counters.  Nothing is drawn and neither z_in nor the seed is read when a6 == 0;
-// z_out (may be NULL) then receives zeros, else the z that was used.  hist, cm_points and aliasing as in multistep_kernel.
-__global__ void multistep_noise_kernel(const float *x, const float *eps, const float *hist, const float *z_in, size_t numel,
-                                       const float *__restrict__ cur, const float *__restrict__ table, float a0, float a1,
-                                       float a2, float a3, float a4, float a5, float a6,
-                                       const uint32_t *__restrict__ seed_words, uint32_t step, uint32_t stream_id, float *out,
-                                       float *hist_out, float *z_out, int cm_points) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = q * 4;
-  if (i >= numel) return;
-  if (cur) {
-    a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; a3 = cur[4]; a4 = cur[5]; a5 = cur[6];
-    step = (uint32_t)__float_as_int(cur[7]);
-    a6 = table[(size_t)step * 8 + 7];
-  }
-  const bool second = a5 != 0.f, noisy = a6 != 0.f;
+  const bool second = a5 != 0.f, noisy = NOISE && a6 != 0.f;
   float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, o[4], p[4];
   const bool full = i + 3 < numel;
-  if (full) {
-    const float4 t = *reinterpret_cast<const float4 *>(x + i);
-    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-    if (second) {
-      const float4 h = *reinterpret_cast<const float4 *>(hist + i);
-      hv[0] = h.x; hv[1] = h.y; hv[2] = h.z; hv[3] = h.w;
-    }
-  } else {
-    for (int j = 0; j < 4; ++j) { xv[j] = i + j < numel ? x[i + j] : 0.f; hv[j] = second && i + j < numel ? hist[i + j] : 0.f; }
-  }
-  if (cm_points) {   // numel = B*N*4: every quad is full; eps is the denoiser's channel-major [B][4][N]
-    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
-  } else if (full) {
-    const float4 u = *reinterpret_cast<const float4 *>(eps + i);
-    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
-  } else {
-    for (int j = 0; j < 4; ++j) ev[j] = i + j < numel ? eps[i + j] : 0.f;
-  }
+  load_quad(x, i, numel, full, xv);
+  if (second) load_quad(hist, i, numel, full, hv);
+  load_eps_quad(eps, q, numel, full, cm_points, ev);
   if (noisy) {
-    if (!z_in) {
+    if (z_in) {
+      load_quad(z_in, i, numel, full, z);
+    } else {
       const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
       normal4(q, step, stream_id, seed, z);
-    } else if (full) {
-      const float4 t = *reinterpret_cast<const float4 *>(z_in + i);
-      z[0] = t.x; z[1] = t.y; z[2] = t.z; z[3] = t.w;
-    } else {
-      for (int j = 0; j < 4; ++j) z[j] = i + j < numel ? z_in[i + j] : 0.f;
     }
   }
 #pragma unroll
@@ -274,21 +222,58 @@ __global__ void multistep_noise_kernel(const float *x, const float *eps, const f
     o[j] = add_rn(mul_rn(a2, xv[j]), mul_rn(a3, d));
     if (noisy) o[j] = add_rn(o[j], mul_rn(a6, z[j]));
   }
-  if (full) {
-    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4 *>(hist_out + i) = make_float4(p[0], p[1], p[2], p[3]);
-    if (z_out) *reinterpret_cast<float4 *>(z_out + i) = make_float4(z[0], z[1], z[2], z[3]);
-  } else {
-    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; hist_out[i + j] = p[j]; if (z_out) z_out[i + j] = z[j]; }
+  store_quad(out, i, numel, full, o);
+  store_quad(hist_out, i, numel, full, p);
+  if (NOISE && z_out) store_quad(z_out, i, numel, full, z);
+}
+
+// The deterministic solver's step: no noise.  The coefficients come from cur[1..6] in device memory where `cur` is given (the
+// captured step), else from the by-value copies (the eager loop).
+__global__ void multistep_kernel(const float *x, const float *eps, const float *hist, size_t numel,
+                                 const float *__restrict__ cur, float a0, float a1, float a2, float a3, float a4, float a5,
+                                 float *out, float *hist_out, int cm_points) {
+  if (cur) { a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; a3 = cur[4]; a4 = cur[5]; a5 = cur[6]; }
+  multistep_body<false>(x, eps, hist, nullptr, numel, a0, a1, a2, a3, a4, a5, 0.f, nullptr, 0, 0, out, hist_out, nullptr,
+                        cm_points);
+}
+
+static int multistep_launch(hipStream_t st, const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
+                            const float a[6], float *out, float *hist_out, int cm_points) {
+  unsigned blocks;
+  if (quad_blocks(numel, &blocks) != LION_OK) return LION_EINVAL;
+  return lion_launch<multistep_kernel>(blocks, 256, 0, st, x, eps, hist, numel, cur, a[0], a[1], a[2], a[3], a[4],
+                                       a[5], out, hist_out, cm_points);
+}
+
+// SDE-DPM-Solver++(2M) (Lu et al. 2022, the SDE form of Algorithm 2): the multistep body's reads and its first three
+// operations, then one Gaussian term, one rounding per written operation:
+//   x0 = a0*(x - a1*eps);   D = a5 == 0 ? a4*x0 : a4*x0 + a5*hist;   hist_out = x0
+//   out = a6 != 0 ? (a2*x + a3*D) + a6*z : a2*x + a3*D
+// (a2 = (sigma_n/sigma_t)*exp(-h), a3 = -alpha_n*expm1(-2h), a6 = sigma_n*sqrt(-expm1(-2h))).  With `cur` (the captured step)
+// a0..a5 are cur[1..6], the step word is cur[7] (the step's index, as begin_step leaves it) and a6 = table[8*step + 7]; else
+// all come by value (the eager loop).  z = z_in where given, else normal4 at counter (quad, step word, stream_id) under the
+// seed in device memory: update_noise_kernel's counters.  Nothing is drawn and neither z_in nor the seed is read when a6 == 0;
+// z_out (may be NULL) then receives zeros, else the z that was used.  hist and aliasing as in the multistep body.
+__global__ void multistep_noise_kernel(const float *x, const float *eps, const float *hist, const float *z_in, size_t numel,
+                                       const float *__restrict__ cur, const float *__restrict__ table, float a0, float a1,
+                                       float a2, float a3, float a4, float a5, float a6,
+                                       const uint32_t *__restrict__ seed_words, uint32_t step, uint32_t stream_id, float *out,
+                                       float *hist_out, float *z_out, int cm_points) {
+  if (cur) {
+    a0 = cur[1]; a1 = cur[2]; a2 = cur[3]; a3 = cur[4]; a4 = cur[5]; a5 = cur[6];
+    step = (uint32_t)__float_as_int(cur[7]);
+    a6 = table[(size_t)step * 8 + 7];
   }
+  multistep_body<true>(x, eps, hist, z_in, numel, a0, a1, a2, a3, a4, a5, a6, seed_words, step, stream_id, out, hist_out, z_out,
+                       cm_points);
 }
 
 static int multistep_noise_launch(hipStream_t st, const float *x, const float *eps, const float *hist, const float *z_in,
                                   size_t numel, const float *cur, const float *table, const float a[7], const uint32_t *seed,
                                   uint32_t step, uint32_t stream_id, float *out, float *hist_out, float *z_out, int cm_points) {
-  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
-  if (blocks > 0x7fffffffu) return LION_EINVAL;
-  return lion_launch<multistep_noise_kernel>((unsigned)blocks, 256, 0, st, x, eps, hist, z_in, numel, cur, table, a[0], a[1],
+  unsigned blocks;
+  if (quad_blocks(numel, &blocks) != LION_OK) return LION_EINVAL;
+  return lion_launch<multistep_noise_kernel>(blocks, 256, 0, st, x, eps, hist, z_in, numel, cur, table, a[0], a[1],
                                              a[2], a[3], a[4], a[5], a[6], seed, step, stream_id, out, hist_out, z_out,
                                              cm_points);
 }
@@ -299,8 +284,8 @@ static int multistep_noise_launch(hipStream_t st, const float *x, const float *e
 // (a0 = s = alpha_t/alpha_n, a1 = c = sigma_t - sigma_n*s, a2 = commit).  base is the state at the leg's low end, eps the
 // model's output at the current iterate (the predictor row evaluates it at base itself, every corrector row at the previous
 // row's out); the leg's last row commits its iterate as the next leg's base.  Coefficients from cur[1..3] where `cur` is given
-// (the captured step), else by value (the eager loop).  base_out is neither read nor written when a2 == 0.  cm_points as in
-// update_noise_kernel.  The tensors are not __restrict__: out may alias the buffer the model read (the chain's x) or base, and
+// (the captured step), else by value (the eager loop).  base_out is neither read nor written when a2 == 0.
+// The tensors are not __restrict__: out may alias the buffer the model read (the chain's x) or base, and
 // base_out may alias base (a lane reads its quad of base and eps before it writes either output, no lane reads another's).
 __global__ void encode_kernel(const float *base, const float *eps, size_t numel, const float *__restrict__ cur, float a0,
                               float a1, float a2, float *out, float *base_out, int cm_points) {
@@ -311,42 +296,24 @@ __global__ void encode_kernel(const float *base, const float *eps, size_t numel,
   const bool commit = a2 != 0.f;
   float bv[4], ev[4], o[4];
   const bool full = i + 3 < numel;
-  if (full) {
-    const float4 t = *reinterpret_cast<const float4 *>(base + i);
-    bv[0] = t.x; bv[1] = t.y; bv[2] = t.z; bv[3] = t.w;
-  } else {
-    for (int j = 0; j < 4; ++j) bv[j] = i + j < numel ? base[i + j] : 0.f;
-  }
-  if (cm_points) {   // numel = B*N*4: every quad is full; eps is the denoiser's channel-major [B][4][N]
-    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ev[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
-  } else if (full) {
-    const float4 u = *reinterpret_cast<const float4 *>(eps + i);
-    ev[0] = u.x; ev[1] = u.y; ev[2] = u.z; ev[3] = u.w;
-  } else {
-    for (int j = 0; j < 4; ++j) ev[j] = i + j < numel ? eps[i + j] : 0.f;
-  }
+  load_quad(base, i, numel, full, bv);
+  load_eps_quad(eps, q, numel, full, cm_points, ev);
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(a0, bv[j]), mul_rn(a1, ev[j]));
-  if (full) {
-    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    if (commit) *reinterpret_cast<float4 *>(base_out + i) = make_float4(o[0], o[1], o[2], o[3]);
-  } else {
-    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; if (commit) base_out[i + j] = o[j]; }
-  }
+  store_quad(out, i, numel, full, o);
+  if (commit) store_quad(base_out, i, numel, full, o);
 }
 
 static int encode_launch(hipStream_t st, const float *base, const float *eps, size_t numel, const float *cur, float a0, float a1,
                          float a2, float *out, float *base_out, int cm_points) {
-  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
-  if (blocks > 0x7fffffffu) return LION_EINVAL;
-  return lion_launch<encode_kernel>((unsigned)blocks, 256, 0, st, base, eps, numel, cur, a0, a1, a2, out, base_out, cm_points);
+  unsigned blocks;
+  if (quad_blocks(numel, &blocks) != LION_OK) return LION_EINVAL;
+  return lion_launch<encode_kernel>(blocks, 256, 0, st, base, eps, numel, cur, a0, a1, a2, out, base_out, cm_points);
 }
 
 // Forward-process draw out = m*x0 + s*z (sample_q, utils/diffusion_pvd.py:105-113) with the chain's generator: quad q of the
 // flat tensor takes Philox counter (q, LION_DIFFUSE_STEP_WORD, stream_id), whatever the pointers' alignment.  VEC: every pointer
-// is 16-byte aligned -> one 16-byte access per operand and full quad; else (and in the tail quad) element by element.
+// is 16-byte aligned, so that a quad below numel is `full`; without it every quad goes element by element.
 // The tensors are not __restrict__: out may alias x0 (a lane reads its quad before it writes it, no lane reads another's).
 template <bool VEC>
 __global__ void diffuse_kernel(const float *x0, const float *z_in, size_t numel, float m, float s,
@@ -357,30 +324,16 @@ __global__ void diffuse_kernel(const float *x0, const float *z_in, size_t numel,
   const bool full = VEC && i + 3 < numel;
   float xv[4], z[4], o[4];
   if (z_in) {
-    if (full) {
-      const float4 t = *reinterpret_cast<const float4 *>(z_in + i);
-      z[0] = t.x; z[1] = t.y; z[2] = t.z; z[3] = t.w;
-    } else {
-      for (int j = 0; j < 4; ++j) z[j] = i + j < numel ? z_in[i + j] : 0.f;
-    }
+    load_quad(z_in, i, numel, full, z);
   } else {
     const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
     normal4(q, LION_DIFFUSE_STEP_WORD, stream_id, seed, z);
   }
-  if (full) {
-    const float4 t = *reinterpret_cast<const float4 *>(x0 + i);
-    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-  } else {
-    for (int j = 0; j < 4; ++j) xv[j] = i + j < numel ? x0[i + j] : 0.f;
-  }
+  load_quad(x0, i, numel, full, xv);
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(m, xv[j]), mul_rn(s, z[j]));
-  if (full) {
-    *reinterpret_cast<float4 *>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    if (z_out) *reinterpret_cast<float4 *>(z_out + i) = make_float4(z[0], z[1], z[2], z[3]);
-  } else {
-    for (int j = 0; j < 4 && i + j < numel; ++j) { out[i + j] = o[j]; if (z_out) z_out[i + j] = z[j]; }
-  }
+  store_quad(out, i, numel, full, o);
+  if (z_out) store_quad(z_out, i, numel, full, z);
 }
 
 } // namespace
@@ -389,12 +342,11 @@ extern "C" {
 
 int lion_ddim_update(const float *x, const float *eps, const float *z, size_t numel, float s,
                      float c, float sigma, float *out, lionStream_t stream) {
-  if (!x || !eps || !out || numel == 0) return LION_EINVAL;
+  unsigned blocks;
+  if (!x || !eps || !out || quad_blocks(numel, &blocks) != LION_OK) return LION_EINVAL;
   if (!z && sigma != 0.f) return LION_EINVAL;
-  const bool aligned = ((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)z)) & 15) == 0;
-  if (!aligned) return LION_EINVAL; // torch allocations are 256-byte aligned
-  const size_t quads = (numel + 3) / 4;
-  return lion_launch<ddim_kernel>((unsigned)((quads + 255) / 256), 256, 0, static_cast<hipStream_t>(stream), x, eps, z,
+  if (!aligned16({x, eps, out, z})) return LION_EINVAL;
+  return lion_launch<ddim_kernel>(blocks, 256, 0, static_cast<hipStream_t>(stream), x, eps, z,
                                   numel, s, c, sigma, out);
 }
 
@@ -425,39 +377,32 @@ int lion_chain_begin_step_temb(const float *table, int n_steps, int32_t *counter
 int lion_chain_update_noise(int mode, const float *x, const float *eps, size_t numel, const float *cur,
                             const uint32_t *seed, uint32_t stream_id, float *out, float *z_out,
                             lionStream_t stream) {
-  if (!x || !eps || !cur || !seed || !out || numel == 0 || (mode != 0 && mode != 1)) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)z_out)) & 15) != 0) return LION_EINVAL;
-  const size_t quads = (numel + 3) / 4;
-  const unsigned blocks = (unsigned)((quads + 255) / 256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return update_noise_launch(mode, blocks, st, x, eps, numel, cur, seed, stream_id, out, z_out, 0);
+  if (!x || !eps || !cur || !seed || !out || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!aligned16({x, eps, out, z_out})) return LION_EINVAL;
+  return update_noise_launch(mode, static_cast<hipStream_t>(stream), x, eps, numel, cur, seed, stream_id, out, z_out, 0);
 }
 
 int lion_chain_update_noise_cm(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
                                const uint32_t *seed, uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
   if (!x || !eps_cm || !cur || !seed || !out || B <= 0 || N <= 0 || (mode != 0 && mode != 1)) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)z_out)) & 15) != 0) return LION_EINVAL;
-  const size_t numel = (size_t)B * N * 4, quads = (size_t)B * N;
-  const unsigned blocks = (unsigned)((quads + 255) / 256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return update_noise_launch(mode, blocks, st, x, eps_cm, numel, cur, seed, stream_id, out, z_out, N);
+  if (!aligned16({x, out, z_out})) return LION_EINVAL;
+  return update_noise_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, (size_t)B * N * 4, cur, seed, stream_id, out,
+                             z_out, N);
 }
 
 int lion_dpmpp_update(const float *x, const float *eps, const float *hist, size_t numel, float a0, float a1, float a2,
                       float a3, float a4, float a5, float *out, float *hist_out, lionStream_t stream) {
-  if (!x || !eps || !out || !hist_out || numel == 0) return LION_EINVAL;
+  if (!x || !eps || !out || !hist_out) return LION_EINVAL;
   if (!hist && a5 != 0.f) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0)
-    return LION_EINVAL;
+  if (!aligned16({x, eps, hist, out, hist_out})) return LION_EINVAL;
   const float a[6] = {a0, a1, a2, a3, a4, a5};
   return multistep_launch(static_cast<hipStream_t>(stream), x, eps, hist, numel, nullptr, a, out, hist_out, 0);
 }
 
 int lion_chain_update_multistep(const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
                                 float *out, float *hist_out, lionStream_t stream) {
-  if (!x || !eps || !hist || !cur || !out || !hist_out || numel == 0) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0)
-    return LION_EINVAL;
+  if (!x || !eps || !hist || !cur || !out || !hist_out) return LION_EINVAL;
+  if (!aligned16({x, eps, hist, out, hist_out})) return LION_EINVAL;
   const float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   return multistep_launch(static_cast<hipStream_t>(stream), x, eps, hist, numel, cur, a, out, hist_out, 0);
 }
@@ -465,7 +410,7 @@ int lion_chain_update_multistep(const float *x, const float *eps, const float *h
 int lion_chain_update_multistep_cm(const float *x, const float *eps_cm, const float *hist, int B, int N, const float *cur,
                                    float *out, float *hist_out, lionStream_t stream) {
   if (!x || !eps_cm || !hist || !cur || !out || !hist_out || B <= 0 || N <= 0) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out)) & 15) != 0) return LION_EINVAL;
+  if (!aligned16({x, hist, out, hist_out})) return LION_EINVAL;
   const float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   return multistep_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, (size_t)B * N * 4, cur, a, out, hist_out, N);
 }
@@ -473,12 +418,10 @@ int lion_chain_update_multistep_cm(const float *x, const float *eps_cm, const fl
 int lion_sde_dpmpp_update(const float *x, const float *eps, const float *hist, const float *z_in, size_t numel, float a0,
                           float a1, float a2, float a3, float a4, float a5, float a6, const uint32_t *seed, uint32_t step_word,
                           uint32_t stream_id, float *out, float *hist_out, float *z_out, lionStream_t stream) {
-  if (!x || !eps || !out || !hist_out || numel == 0) return LION_EINVAL;
+  if (!x || !eps || !out || !hist_out) return LION_EINVAL;
   if (!hist && a5 != 0.f) return LION_EINVAL;
   if (!z_in && !seed && a6 != 0.f) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)z_in) | ((uintptr_t)out) | ((uintptr_t)hist_out) |
-        ((uintptr_t)z_out)) & 15) != 0)
-    return LION_EINVAL;
+  if (!aligned16({x, eps, hist, z_in, out, hist_out, z_out})) return LION_EINVAL;
   const float a[7] = {a0, a1, a2, a3, a4, a5, a6};
   return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps, hist, z_in, numel, nullptr, nullptr, a, seed,
                                 step_word, stream_id, out, hist_out, z_out, 0);
@@ -487,10 +430,8 @@ int lion_sde_dpmpp_update(const float *x, const float *eps, const float *hist, c
 int lion_chain_update_multistep_noise(const float *x, const float *eps, const float *hist, size_t numel, const float *cur,
                                       const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
                                       float *hist_out, float *z_out, lionStream_t stream) {
-  if (!x || !eps || !hist || !cur || !table || !seed || !out || !hist_out || numel == 0) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)eps) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out) | ((uintptr_t)z_out)) &
-       15) != 0)
-    return LION_EINVAL;
+  if (!x || !eps || !hist || !cur || !table || !seed || !out || !hist_out) return LION_EINVAL;
+  if (!aligned16({x, eps, hist, out, hist_out, z_out})) return LION_EINVAL;
   const float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps, hist, nullptr, numel, cur, table, a, seed, 0,
                                 stream_id, out, hist_out, z_out, 0);
@@ -500,8 +441,7 @@ int lion_chain_update_multistep_noise_cm(const float *x, const float *eps_cm, co
                                          const float *table, const uint32_t *seed, uint32_t stream_id, float *out,
                                          float *hist_out, float *z_out, lionStream_t stream) {
   if (!x || !eps_cm || !hist || !cur || !table || !seed || !out || !hist_out || B <= 0 || N <= 0) return LION_EINVAL;
-  if (((((uintptr_t)x) | ((uintptr_t)hist) | ((uintptr_t)out) | ((uintptr_t)hist_out) | ((uintptr_t)z_out)) & 15) != 0)
-    return LION_EINVAL;
+  if (!aligned16({x, hist, out, hist_out, z_out})) return LION_EINVAL;
   const float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   return multistep_noise_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, nullptr, (size_t)B * N * 4, cur, table, a,
                                 seed, 0, stream_id, out, hist_out, z_out, N);
@@ -509,36 +449,34 @@ int lion_chain_update_multistep_noise_cm(const float *x, const float *eps_cm, co
 
 int lion_ddim_encode_update(const float *base, const float *eps, size_t numel, float a0, float a1, float a2, float *out,
                             float *base_out, lionStream_t stream) {
-  if (!base || !eps || !out || numel == 0) return LION_EINVAL;
+  if (!base || !eps || !out) return LION_EINVAL;
   if (!base_out && a2 != 0.f) return LION_EINVAL;
-  if (((((uintptr_t)base) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)base_out)) & 15) != 0) return LION_EINVAL;
+  if (!aligned16({base, eps, out, base_out})) return LION_EINVAL;
   return encode_launch(static_cast<hipStream_t>(stream), base, eps, numel, nullptr, a0, a1, a2, out, base_out, 0);
 }
 
 int lion_chain_update_encode(const float *base, const float *eps, size_t numel, const float *cur, float *out, float *base_out,
                              lionStream_t stream) {
-  if (!base || !eps || !cur || !out || !base_out || numel == 0) return LION_EINVAL;
-  if (((((uintptr_t)base) | ((uintptr_t)eps) | ((uintptr_t)out) | ((uintptr_t)base_out)) & 15) != 0) return LION_EINVAL;
+  if (!base || !eps || !cur || !out || !base_out) return LION_EINVAL;
+  if (!aligned16({base, eps, out, base_out})) return LION_EINVAL;
   return encode_launch(static_cast<hipStream_t>(stream), base, eps, numel, cur, 0.f, 0.f, 0.f, out, base_out, 0);
 }
 
 int lion_chain_update_encode_cm(const float *base, const float *eps_cm, int B, int N, const float *cur, float *out,
                                 float *base_out, lionStream_t stream) {
   if (!base || !eps_cm || !cur || !out || !base_out || B <= 0 || N <= 0) return LION_EINVAL;
-  if (((((uintptr_t)base) | ((uintptr_t)out) | ((uintptr_t)base_out)) & 15) != 0) return LION_EINVAL;
+  if (!aligned16({base, out, base_out})) return LION_EINVAL;
   return encode_launch(static_cast<hipStream_t>(stream), base, eps_cm, (size_t)B * N * 4, cur, 0.f, 0.f, 0.f, out, base_out, N);
 }
 
 int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s, const uint32_t *seed,
                        uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
-  if (!x0 || !out || numel == 0 || (!z_in && !seed)) return LION_EINVAL;
-  const size_t quads = (numel + 3) / 4, blocks = (quads + 255) / 256;
-  if (blocks > 0x7fffffffu) return LION_EINVAL;
+  unsigned blocks;
+  if (!x0 || !out || (!z_in && !seed) || quad_blocks(numel, &blocks) != LION_OK) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = ((((uintptr_t)x0) | ((uintptr_t)z_in) | ((uintptr_t)out) | ((uintptr_t)z_out)) & 15) == 0;
-  return vec ? lion_launch<diffuse_kernel<true>>((unsigned)blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out, z_out)
-             : lion_launch<diffuse_kernel<false>>((unsigned)blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out,
-                                                  z_out);
+  return aligned16({x0, z_in, out, z_out})
+             ? lion_launch<diffuse_kernel<true>>(blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out, z_out)
+             : lion_launch<diffuse_kernel<false>>(blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out, z_out);
 }
 
 } // extern "C"

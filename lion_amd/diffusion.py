@@ -17,6 +17,8 @@ reference, :305-388), the inverse of the order-1 solver, on the same captured st
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 
@@ -47,6 +49,18 @@ def make_beta_schedule(schedule, start, end, n_timestep):
     else:
         raise NotImplementedError(schedule)
     return torch.from_numpy(np.asarray(betas, dtype=np.float64))
+
+
+@contextlib.contextmanager
+def _sampling(model, conv_precision):
+    """one sampler call: the requested conv precision, the model in eval mode; on the way out model.train(), unconditionally
+    as the reference does -- also when an exception passes through"""
+    with conv_ops.requested_precision(conv_precision):
+        model.eval()
+        try:
+            yield
+        finally:
+            model.train()
 
 
 def _mixed(model, pred, mixing_component):
@@ -336,6 +350,23 @@ class DiffusionDiscretized(object):
         return torch.randn(size, device=device)
 
     # ---- samplers ------------------------------------------------------------------------------
+    def _eps_hat(self, model, x, t_model, condition_input, clip_feat, enable_autocast, kwargs):
+        """one model evaluation of an eager loop: the noise prediction at x for the model's timestep t_model (schedule index
+        + 1) on every sample, mixed with x's component where the model asks for it; float32, contiguous"""
+        timestep = torch.full((x.shape[0],), t_model, dtype=torch.int64, device=self.device)
+        mixing = self.get_mixing_component(x, timestep, enabled=getattr(model, 'mixed_prediction', False))
+        with torch.autocast("cuda", enabled=enable_autocast):
+            pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat, **kwargs)
+            return _mixed(model, pred, mixing).float().contiguous()
+
+    def _replay(self, model, num_samples, shape, mode, x, table, seed, condition_input, clip_feat, capacity=None, **run):
+        """the graphed branch of every sampler: the captured chain of (model, mode, batch shape) from this object's cache, run
+        from x over `table`; seed None: one is drawn with chain.draw_seed() once the chain is there; `run`: GraphedChain.run's
+        keywords.  Returns the final latent."""
+        ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, self.device, mode,
+                              self._diffusion_steps if capacity is None else capacity)
+        return ch.run(x, table, _chain.draw_seed() if seed is None else seed, condition_input, clip_feat, **run)
+
     @torch.no_grad()
     def run_denoising_diffusion(self, model, num_samples, shape, temp=1.0, enable_autocast=False,
                                 is_image=False, prior_var=1.0, condition_input=None, given_noise=None,
@@ -344,55 +375,37 @@ class DiffusionDiscretized(object):
         """Ancestral DDPM sampling, T model evaluations (reference :224-303).  ``noise_scale(t)`` overrides the
         per-step noise standard deviation sqrt(beta_t) (LION.sample's scheduler variance).
         conv_precision="half": the denoiser's voxel convolutions run at reduced precision (conv_ops.PRECISION)."""
-        with conv_ops.requested_precision(conv_precision):
-            return self._run_denoising_diffusion(model, num_samples, shape, temp, enable_autocast, is_image, prior_var,
-                                                 condition_input, given_noise, clip_feat, cls_emb, grid_emb, graph,
-                                                 keep_trajectory, noise_scale)
-
-    def _run_denoising_diffusion(self, model, num_samples, shape, temp, enable_autocast, is_image, prior_var, condition_input,
-                                 given_noise, clip_feat, cls_emb, grid_emb, graph, keep_trajectory, noise_scale):
-        model.eval()
-        dev = self.device
-        size = [num_samples] + list(shape)
-        x_noisy = torch.randn(size=size, device=dev) if given_noise is None else given_noise[0].to(dev)
-        x_noisy = x_noisy.contiguous()
-        output_list = {'pred_x': []}
-        kwargs = {'grid_emb': grid_emb} if grid_emb is not None else {}
-        if cls_emb is not None:
-            condition_input = cls_emb if condition_input is None else torch.cat([condition_input, cls_emb], dim=1)
-        x_image = None
-        if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
+        with _sampling(model, conv_precision):
+            dev = self.device
+            size = [num_samples] + list(shape)
+            x_noisy = torch.randn(size=size, device=dev) if given_noise is None else given_noise[0].to(dev)
+            x_noisy = x_noisy.contiguous()
+            output_list = {'pred_x': []}
+            kwargs = {'grid_emb': grid_emb} if grid_emb is not None else {}
+            if cls_emb is not None:
+                condition_input = cls_emb if condition_input is None else torch.cat([condition_input, cls_emb], dim=1)
             T = self._diffusion_steps
-            table = self.ddpm_table(T, temp, noise_scale)
-            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DDPM, T)
-            x_image = ch.run(x_noisy, table, _chain.draw_seed(), condition_input, clip_feat,
-                             trajectory=output_list['pred_x'] if keep_trajectory else None,
-                             trajectory_before_last=True)
+            if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
+                x_image = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, self.ddpm_table(T, temp, noise_scale),
+                                       None, condition_input, clip_feat,
+                                       trajectory=output_list['pred_x'] if keep_trajectory else None,
+                                       trajectory_before_last=True)
+            else:
+                x_image = self._ancestral_steps(model, x_noisy, T, temp, enable_autocast, condition_input, given_noise,
+                                                clip_feat, kwargs, output_list['pred_x'])
             if is_image:
                 x_image = (x_image.clamp(min=-1., max=1.) + 1.0) / 2.0
-            model.train()
             return x_image, output_list
-        x_image = self._ancestral_steps(model, x_noisy, self._diffusion_steps, temp, enable_autocast, condition_input,
-                                        given_noise, clip_feat, kwargs, output_list['pred_x'])
-        if is_image:
-            x_image = (x_image.clamp(min=-1., max=1.) + 1.0) / 2.0
-        model.train()
-        return x_image, output_list
 
     def _ancestral_steps(self, model, x_noisy, t_from, temp, enable_autocast, condition_input, given_noise, clip_feat, kwargs,
                          states, generator=None):
         """the eager ancestral steps t = t_from-1 ... 0 from x_noisy; returns the posterior mean of the step at t = 0.  The noise
         of step t is given_noise[1][t] where given, else a device draw (from `generator` if one is passed).  `states` (a list,
         or None) receives the state after every step -- for t = 0 the state BEFORE it once more, as the reference reports it."""
-        dev, size, num_samples = self.device, list(x_noisy.shape), x_noisy.shape[0]
+        dev, size = self.device, list(x_noisy.shape)
         x_image = None
         for t in reversed(range(0, t_from)):
-            timestep = torch.full((num_samples,), t + 1, dtype=torch.int64, device=dev)
-            mixing = self.get_mixing_component(x_noisy, timestep, enabled=getattr(model, 'mixed_prediction', False))
-            with torch.autocast("cuda", enabled=enable_autocast):
-                pred = model(x=x_noisy, t=timestep.float(), condition_input=condition_input,
-                             clip_feat=clip_feat, **kwargs)
-                eps_hat = _mixed(model, pred, mixing).float().contiguous()
+            eps_hat = self._eps_hat(model, x_noisy, t + 1, condition_input, clip_feat, enable_autocast, kwargs)
             is0, k_outer, k_a, k_b, scale = self.ddpm_coefficients(t)
             if is0:
                 x_image = diffusion_ops.ddpm_update(x_noisy, eps_hat, None, True, k_outer, k_a, k_b, scale, temp)
@@ -425,7 +438,7 @@ class DiffusionDiscretized(object):
     @torch.no_grad()
     def run_denoising_diffusion_from_t(self, model, num_samples, shape, time_start, x_noisy, temp=1.0, enable_autocast=False,
                                        is_image=False, prior_var=1.0, condition_input=None, given_noise=None, clip_feat=None,
-                                       graph=True, keep_trajectory=True, conv_precision="fp32"):
+                                       graph=True, keep_trajectory=True, conv_precision="fp32", *, seed=None):
         """The tail of the ancestral chain from ``x_noisy`` (reference :504-563): the steps t = time_start-1 ... 0, the last of
         which returns the posterior mean; 1 <= time_start <= T, and time_start = T is the whole chain from a given start.
         Returns (x, output_list): output_list is the reference's plain list of the state after every step, whose last entry
@@ -435,14 +448,9 @@ class DiffusionDiscretized(object):
         is_image and prior_var are accepted and unused, as in the reference.
         graph=True: the tail is replayed on the captured chain of run_denoising_diffusion for this model and batch shape --
         the same cache entry, so a model that has sampled is not captured again -- with the schedule table's last
-        time_start rows; the per-step noise is then the chain's Philox stream (key from chain.draw_seed())."""
-        with conv_ops.requested_precision(conv_precision):
-            return self._denoise_from_t(model, num_samples, shape, time_start, x_noisy, temp, enable_autocast, condition_input,
-                                        given_noise, clip_feat, graph, keep_trajectory, None)
-
-    def _denoise_from_t(self, model, num_samples, shape, time_start, x_noisy, temp, enable_autocast, condition_input,
-                        given_noise, clip_feat, graph, keep_trajectory, seed):
-        """seed (editing.diffuse_denoise): the 64-bit key of the tail's noise, in place of a draw from torch's global generator"""
+        time_start rows; the per-step noise is then the chain's Philox stream.
+        seed (editing.diffuse_denoise): the 64-bit key of the tail's noise -- the chain's Philox key, or the seed of the eager
+        loop's device generator -- in place of a draw from torch's global generators (graphed: chain.draw_seed())."""
         if isinstance(time_start, bool) or not isinstance(time_start, (int, np.integer)) \
                 or not 0 <= time_start <= self._diffusion_steps:
             raise ValueError(f"run_denoising_diffusion_from_t: time_start = {time_start!r} outside [0, {self._diffusion_steps}]")
@@ -453,21 +461,18 @@ class DiffusionDiscretized(object):
             raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
         if list(x_noisy.shape) != [num_samples] + list(shape):
             raise ValueError(f"run_denoising_diffusion_from_t: x_noisy {tuple(x_noisy.shape)} for {[num_samples] + list(shape)}")
-        model.eval()
-        dev = self.device
-        x_noisy = x_noisy.to(dev).contiguous()
-        states = output_list if keep_trajectory else None
-        if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, {}):
-            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DDPM,
-                                  self._diffusion_steps)
-            x = ch.run(x_noisy, self.ddpm_table(int(time_start), temp), _chain.draw_seed() if seed is None else seed,
-                       condition_input, clip_feat, trajectory=states, trajectory_before_last=True)
-        else:
-            gen = None if seed is None else torch.Generator(device=dev).manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
-            x = self._ancestral_steps(model, x_noisy, int(time_start), temp, enable_autocast, condition_input, given_noise,
-                                      clip_feat, {}, states, generator=gen)
-        model.train()
-        return x, output_list
+        with _sampling(model, conv_precision):
+            dev = self.device
+            x_noisy = x_noisy.to(dev).contiguous()
+            states = output_list if keep_trajectory else None
+            if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, {}):
+                x = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, self.ddpm_table(int(time_start), temp), seed,
+                                 condition_input, clip_feat, trajectory=states, trajectory_before_last=True)
+            else:
+                gen = None if seed is None else torch.Generator(device=dev).manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
+                x = self._ancestral_steps(model, x_noisy, int(time_start), temp, enable_autocast, condition_input, given_noise,
+                                          clip_feat, {}, states, generator=gen)
+            return x, output_list
 
     @torch.no_grad()
     def run_ddim(self, model, num_samples, shape, temp=1.0, enable_autocast=False, is_image=True,
@@ -484,56 +489,39 @@ class DiffusionDiscretized(object):
         conv_precision="half": the supported reduced-precision mode -- the denoiser's voxel convolutions at r = 16 / 32 run
         one fp16 product per operand pair on the project's own kernel, inside the captured chain (conv_ops.PRECISION;
         DESIGN.md 4.3).  enable_autocast is unrelated to it and keeps its behaviour."""
-        with conv_ops.requested_precision(conv_precision):
-            return self._run_ddim(model, num_samples, shape, temp, enable_autocast, is_image, prior_var, condition_input,
-                                  ddim_step, skip_type, kappa, clip_feat, grid_emb, x_noisy, dae_index, noise,
-                                  keep_trajectory, graph, given_noise, state_hook)
-
-    def _run_ddim(self, model, num_samples, shape, temp, enable_autocast, is_image, prior_var, condition_input, ddim_step,
-                  skip_type, kappa, clip_feat, grid_emb, x_noisy, dae_index, noise, keep_trajectory, graph, given_noise,
-                  state_hook):
-        model.eval()
-        dev = self.device
-        size = [num_samples] + list(shape)
-        if given_noise is not None:
-            x_noisy, noise = given_noise[0], 'given'
-        if x_noisy is None:
-            x_noisy = torch.randn(size=size).to(dev) if noise == 'cpu' else torch.randn(size=size, device=dev)
-        x_noisy = x_noisy.to(dev).contiguous()
-        steps = self.ddim_schedule(self._diffusion_steps, ddim_step, skip_type)
-        kwargs = {'grid_emb': grid_emb} if grid_emb is not None else {}
-        output_list = []
-        if graph and noise == 'device' and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
-            table = self.ddim_table(steps, kappa)
-            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.DDIM,
-                                  self._diffusion_steps)
-            x_noisy = ch.run(x_noisy, table, _chain.draw_seed(), condition_input, clip_feat,
-                             trajectory=output_list if keep_trajectory else None, state_hook=state_hook)
-            model.train()
+        with _sampling(model, conv_precision):
+            dev = self.device
+            size = [num_samples] + list(shape)
+            if given_noise is not None:
+                x_noisy, noise = given_noise[0], 'given'
+            if x_noisy is None:
+                x_noisy = torch.randn(size=size).to(dev) if noise == 'cpu' else torch.randn(size=size, device=dev)
+            x_noisy = x_noisy.to(dev).contiguous()
+            steps = self.ddim_schedule(self._diffusion_steps, ddim_step, skip_type)
+            kwargs = {'grid_emb': grid_emb} if grid_emb is not None else {}
+            output_list = []
+            if graph and noise == 'device' and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
+                x_noisy = self._replay(model, num_samples, shape, _chain.DDIM, x_noisy, self.ddim_table(steps, kappa), None,
+                                       condition_input, clip_feat, trajectory=output_list if keep_trajectory else None,
+                                       state_hook=state_hook)
+                return x_noisy, output_list
+            for i, t in enumerate(steps):
+                last = i == len(steps) - 1
+                if last:
+                    assert t == 0
+                if state_hook is not None:
+                    state_hook(i, x_noisy)
+                s, c, sigma = self.ddim_coefficients(t, None if last else steps[i + 1], kappa)
+                eps_hat = self._eps_hat(model, x_noisy, t + 1, condition_input, clip_feat, enable_autocast, kwargs)
+                # the reference draws (and adds, scaled by sigma == 0) noise on the last step as well
+                if noise == 'given':
+                    z = given_noise[1][i].to(dev).contiguous() if sigma != 0.0 else None
+                else:
+                    z = self._noise(size, noise, dev).contiguous() if (sigma != 0.0 or noise == 'cpu') else None
+                x_noisy = diffusion_ops.ddim_update(x_noisy, eps_hat, z if sigma != 0.0 else None, s, c, sigma)
+                if keep_trajectory:
+                    output_list.append(x_noisy)
             return x_noisy, output_list
-        for i, t in enumerate(steps):
-            last = i == len(steps) - 1
-            if last:
-                assert t == 0
-            if state_hook is not None:
-                state_hook(i, x_noisy)
-            timestep = torch.full((num_samples,), t + 1, dtype=torch.int64, device=dev)
-            mixing = self.get_mixing_component(x_noisy, timestep, enabled=getattr(model, 'mixed_prediction', False))
-            s, c, sigma = self.ddim_coefficients(t, None if last else steps[i + 1], kappa)
-            with torch.autocast("cuda", enabled=enable_autocast):
-                pred = model(x=x_noisy, t=timestep.float(), condition_input=condition_input,
-                             clip_feat=clip_feat, **kwargs)
-                eps_hat = _mixed(model, pred, mixing).float().contiguous()
-            # the reference draws (and adds, scaled by sigma == 0) noise on the last step as well
-            if noise == 'given':
-                z = given_noise[1][i].to(dev).contiguous() if sigma != 0.0 else None
-            else:
-                z = self._noise(size, noise, dev).contiguous() if (sigma != 0.0 or noise == 'cpu') else None
-            x_noisy = diffusion_ops.ddim_update(x_noisy, eps_hat, z if sigma != 0.0 else None, s, c, sigma)
-            if keep_trajectory:
-                output_list.append(x_noisy)
-        model.train()
-        return x_noisy, output_list
 
     @torch.no_grad()
     def run_dpm_solver(self, model, num_samples, shape, steps=20, order=2, skip_type='logsnr', x_noisy=None,
@@ -562,52 +550,37 @@ class DiffusionDiscretized(object):
         t_start (an index in 1 ... T-1; needs x_noisy, else ValueError): the tail of the chain from x_noisy, taken as a draw
         of the marginal at index t_start (DiffusionDiscretized.diffuse(x0, t_start)), over
         solver_schedule(steps, skip_type, t_start).  Either solver runs it."""
-        with conv_ops.requested_precision(conv_precision):
-            return self._run_dpm_solver(model, num_samples, shape, steps, order, skip_type, x_noisy, condition_input, clip_feat,
-                                        enable_autocast, keep_trajectory, graph, state_hook, stochastic, t_start, seed)
-
-    def _run_dpm_solver(self, model, num_samples, shape, steps, order, skip_type, x_noisy, condition_input, clip_feat,
-                        enable_autocast, keep_trajectory, graph, state_hook, stochastic=False, t_start=None, seed=None):
         if t_start is not None and x_noisy is None:
             raise ValueError("run_dpm_solver: t_start needs x_noisy, the state at that index")
         taus = self.solver_schedule(steps, skip_type, t_start)
         table = self.dpm_solver_table(taus, order, stochastic=bool(stochastic))
         if stochastic:
             seed = _chain.draw_seed() if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        model.eval()
-        dev = self.device
-        size = [num_samples] + list(shape)
-        if x_noisy is None:
-            x_noisy = torch.randn(size=size, device=dev)
-        x_noisy = x_noisy.to(dev).contiguous()
-        output_list = []
-        if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
-            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev,
-                                  _chain.SDE_DPMPP if stochastic else _chain.DPMPP, self._diffusion_steps)
-            x = ch.run(x_noisy, table, seed if stochastic else 0, condition_input, clip_feat,
-                       trajectory=output_list if keep_trajectory else None,
-                       state_hook=state_hook)   # seed 0: the deterministic step draws nothing
-            model.train()
+        with _sampling(model, conv_precision):
+            dev = self.device
+            if x_noisy is None:
+                x_noisy = torch.randn(size=[num_samples] + list(shape), device=dev)
+            x_noisy = x_noisy.to(dev).contiguous()
+            output_list = []
+            if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
+                x = self._replay(model, num_samples, shape, _chain.SDE_DPMPP if stochastic else _chain.DPMPP, x_noisy, table,
+                                 seed if stochastic else 0, condition_input, clip_feat,   # 0: the deterministic step draws nothing
+                                 trajectory=output_list if keep_trajectory else None, state_hook=state_hook)
+                return x, output_list
+            x, hist = x_noisy.clone(), None     # the hook may overwrite the latent in place: never the caller's tensor
+            words = diffusion_ops.seed_words(seed, dev) if stochastic else None
+            for i, t in enumerate(taus):
+                if state_hook is not None:
+                    state_hook(i, x)
+                eps_hat = self._eps_hat(model, x, t + 1, condition_input, clip_feat, enable_autocast, {})
+                if stochastic:   # step i of the captured chain: counter word i, stream 0
+                    x, hist = diffusion_ops.sde_dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:8]], seed=words,
+                                                             step=i)
+                else:
+                    x, hist = diffusion_ops.dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:7]])
+                if keep_trajectory:
+                    output_list.append(x)
             return x, output_list
-        x, hist = x_noisy.clone(), None     # the hook may overwrite the latent in place: never the caller's tensor
-        words = diffusion_ops.seed_words(seed, dev) if stochastic else None
-        for i, t in enumerate(taus):
-            if state_hook is not None:
-                state_hook(i, x)
-            timestep = torch.full((num_samples,), t + 1, dtype=torch.int64, device=dev)
-            mixing = self.get_mixing_component(x, timestep, enabled=getattr(model, 'mixed_prediction', False))
-            with torch.autocast("cuda", enabled=enable_autocast):
-                pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat)
-                eps_hat = _mixed(model, pred, mixing).float().contiguous()
-            if stochastic:   # step i of the captured chain: counter word i, stream 0
-                x, hist = diffusion_ops.sde_dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:8]], seed=words,
-                                                         step=i)
-            else:
-                x, hist = diffusion_ops.dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:7]])
-            if keep_trajectory:
-                output_list.append(x)
-        model.train()
-        return x, output_list
 
     @torch.no_grad()
     def run_ddim_forward(self, dae, eps, ddim_step=20, ddim_skip_type='logsnr', condition_input=None, clip_feat=None, refine=0,
@@ -627,40 +600,25 @@ class DiffusionDiscretized(object):
         iterate and the leg's base in device memory (chain.ENCODE, a cache entry of its own).  Otherwise -- graph=False,
         mixed_prediction models, autocast -- the eager loop on lion_ddim_encode_update; the two give the same bits.
         conv_precision: as in run_ddim."""
-        with conv_ops.requested_precision(conv_precision):
-            return self._run_ddim_forward(dae, eps, ddim_step, ddim_skip_type, condition_input, clip_feat, refine, graph,
-                                          keep_trajectory, enable_autocast)
-
-    def _run_ddim_forward(self, model, eps, ddim_step, skip_type, condition_input, clip_feat, refine, graph, keep_trajectory,
-                          enable_autocast):
         if not eps.is_cuda:
             raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
-        table = self.encode_table(self.solver_schedule(ddim_step, skip_type), refine)
-        model.eval()
-        dev = self.device
-        num_samples, shape = eps.shape[0], list(eps.shape[1:])
-        start = eps.detach().to(dev).contiguous()
-        output_list = []
-        if graph and _chain.graphable(model, start, enable_autocast, {}):
-            ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, dev, _chain.ENCODE,
-                                  max(self._diffusion_steps, len(table)))
-            for i in range(ch.prepare(start, table, 0, condition_input, clip_feat)):   # seed 0: the step draws nothing
-                ch.replay()
-                if keep_trajectory and table[i, 3] != 0:
-                    output_list.append(ch.x.clone())
-            model.train()
-            return ch.x.clone(), output_list
-        x, base = start.clone(), start.clone()          # never the caller's tensor
-        for row in table:
-            timestep = torch.full((num_samples,), int(row[0]), dtype=torch.int64, device=dev)
-            mixing = self.get_mixing_component(x, timestep, enabled=getattr(model, 'mixed_prediction', False))
-            with torch.autocast("cuda", enabled=enable_autocast):
-                pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat)
-                eps_hat = _mixed(model, pred, mixing).float().contiguous()
-            commit = row[3] != 0
-            diffusion_ops.ddim_encode_update(base, eps_hat, float(row[1]), float(row[2]), commit, out=x,
-                                             base_out=base if commit else None)
-            if keep_trajectory and commit:
-                output_list.append(x.clone())
-        model.train()
-        return x, output_list
+        table = self.encode_table(self.solver_schedule(ddim_step, ddim_skip_type), refine)
+        with _sampling(dae, conv_precision):
+            num_samples, shape = eps.shape[0], list(eps.shape[1:])
+            start = eps.detach().to(self.device).contiguous()
+            output_list = []
+            if graph and _chain.graphable(dae, start, enable_autocast, {}):
+                x = self._replay(dae, num_samples, shape, _chain.ENCODE, start, table, 0, condition_input, clip_feat,
+                                 capacity=max(self._diffusion_steps, len(table)),   # seed 0: the step draws nothing
+                                 trajectory=output_list if keep_trajectory else None,
+                                 trajectory_rows=lambda i: table[i, 3] != 0)
+                return x, output_list
+            x, base = start.clone(), start.clone()          # never the caller's tensor
+            for row in table:
+                eps_hat = self._eps_hat(dae, x, int(row[0]), condition_input, clip_feat, enable_autocast, {})
+                commit = row[3] != 0
+                diffusion_ops.ddim_encode_update(base, eps_hat, float(row[1]), float(row[2]), commit, out=x,
+                                                 base_out=base if commit else None)
+                if keep_trajectory and commit:
+                    output_list.append(x.clone())
+            return x, output_list

@@ -15,7 +15,6 @@ import numbers
 import torch
 
 from . import chain as _chain
-from . import conv_ops
 
 _MASK64 = 0xFFFFFFFFFFFFFFFF
 
@@ -98,9 +97,10 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
                                               t_start=pair[i], seed=seeds["chain_" + which])
         else:
             visited[i] = list(range(pair[i] - 1, -1, -1))
-            with conv_ops.requested_precision(conv_precision):
-                eps, _ = diffusion._denoise_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp, False, condition_input, None,
-                                                   clip_feat, graph, False, seeds["chain_" + which])
+            eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp=temp,
+                                                              condition_input=condition_input, clip_feat=clip_feat, graph=graph,
+                                                              keep_trajectory=False, conv_precision=conv_precision,
+                                                              seed=seeds["chain_" + which])
         if keep_first:
             eps[0:1] = eps_ori[0:1]
         return eps.contiguous()

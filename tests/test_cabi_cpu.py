@@ -7,23 +7,21 @@ import re
 import pytest
 import torch
 
+import abi_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared():
-    txt = open(os.path.join(ROOT, "include", "lion_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = abi_check.header()
     return sorted(set(re.findall(r"\b(lion_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_library_exports_every_declared_symbol():
     from lion_amd import _lib
-    assert os.path.exists(_lib.SO_PATH), "run __graft_entry__.build() first"
-    lib = ctypes.CDLL(_lib.SO_PATH)
     names = _declared()
     assert len(names) >= 20
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/lion_hip.h but not exported"
+    abi_check.declared_bound_and_exported(names, returns=r"\w+")
     # and the ctypes table binds exactly the declared set
     assert sorted(_lib.SIGNATURES) == names
     assert _lib.load().lion_abi_version() == 1

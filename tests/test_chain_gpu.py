@@ -66,7 +66,7 @@ def _call_update(mode, x, eps, row, step, seed, want_z=True):
     return out, z
 
 
-@pytest.mark.parametrize("numel", [32 * 8192, 32 * 128, 1001])
+@pytest.mark.parametrize("numel", [1, 3, 5, 1001, 32 * 128, 32 * 8192])
 def test_chain_update_noise(numel):
     from lion_amd.diffusion_ops import ddim_update, ddpm_update
     g = torch.Generator(device="cuda").manual_seed(numel)

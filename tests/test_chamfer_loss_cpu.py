@@ -1,11 +1,11 @@
 """CPU suite: the Chamfer reconstruction losses ('chamfer', 'cd_sum' of utils/model_helper.py:43-52) are wired through every
 layer -- header, ctypes table, library, lion_amd.chamfer3d, loss_fn -- and, like every other operator, have no CPU path."""
-import ctypes
 import os
-import re
 
 import pytest
 import torch
+
+import abi_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lion_chamfer_loss_reduce", "lion_chamfer_loss_backward")
@@ -13,13 +13,7 @@ NEW = ("lion_chamfer_loss_reduce", "lion_chamfer_loss_backward")
 
 def test_both_symbols_are_declared_bound_and_exported():
     from lion_amd import _lib, chamfer3d
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lion_hip.h")).read(), flags=re.S)
-    lib = ctypes.CDLL(_lib.SO_PATH)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"{name} not declared in include/lion_hip.h"
-        assert name in _lib.SIGNATURES, f"{name} not bound in _lib.SIGNATURES"
-        assert hasattr(lib, name), f"{name} not exported by the library"
-        assert getattr(_lib.load(), name).argtypes == _lib.SIGNATURES[name][1]
+    abi_check.declared_bound_and_exported(NEW)
     assert "ChamferLossFunction" in chamfer3d.__all__ and "chamfer_loss" in chamfer3d.__all__
     # bad arguments are refused on the host, before any launch: NULL pointers, empty clouds, both gradients NULL
     l = _lib.load()

@@ -5,10 +5,11 @@ nonlinear toy; and the round-trip error ladder over the refinement count on the 
 expression)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
+
+import abi_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lion_ddim_encode_update", "lion_chain_update_encode", "lion_chain_update_encode_cm")
@@ -25,13 +26,7 @@ def _diffusion(sched="linear", T=1000):
 
 def test_three_symbols_are_declared_bound_and_exported():
     from lion_amd import _lib, chain, diffusion_ops
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lion_hip.h")).read(), flags=re.S)
-    lib = ctypes.CDLL(_lib.SO_PATH)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"{name} not declared in include/lion_hip.h"
-        assert name in _lib.SIGNATURES, f"{name} not bound in _lib.SIGNATURES"
-        assert hasattr(lib, name), f"{name} not exported by the library"
-        assert getattr(_lib.load(), name).argtypes == _lib.SIGNATURES[name][1]
+    abi_check.declared_bound_and_exported(NEW)
     assert "ddim_encode_update" in diffusion_ops.__all__
     assert chain.ENCODE == 4 and {chain.DDIM, chain.DDPM, chain.DPMPP, chain.SDE_DPMPP} == {0, 1, 2, 3}
 

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -22,8 +24,7 @@ def _diffusion(T=1000):
 
 def test_chain_diffuse_is_declared_bound_and_exported():
     from lion_amd import _lib
-    txt = open(os.path.join(ROOT, "include", "lion_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = abi_check.header()
     found = re.findall(r"\bint\s+lion_chain_diffuse\s*\(([^)]*)\)\s*;", txt)
     assert len(found) == 1, "lion_chain_diffuse: one prototype in include/lion_hip.h"
     params = [" ".join(p.split()) for p in found[0].split(",")]
@@ -34,7 +35,7 @@ def test_chain_diffuse_is_declared_bound_and_exported():
     res, args = _lib.SIGNATURES["lion_chain_diffuse"]
     assert res is ctypes.c_int and len(args) == len(kinds)
     assert all(a is ctype[k] for a, k in zip(args, kinds))
-    assert hasattr(ctypes.CDLL(_lib.SO_PATH), "lion_chain_diffuse")
+    abi_check.declared_bound_and_exported(["lion_chain_diffuse"])
     # the step word of the draw's counter is stated in the header, and no chain step can have it (a step index is an int)
     word = re.search(r"#define\s+LION_DIFFUSE_STEP_WORD\s+(0x[0-9A-Fa-f]+)u?\b", open(os.path.join(ROOT, "include", "lion_hip.h")).read())
     assert word and int(word.group(1), 16) > 0x7FFFFFFF

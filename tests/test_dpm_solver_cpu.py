@@ -4,10 +4,11 @@ arguments on the host; the schedule and the coefficient table against restatemen
 error on an ODE with a closed-form solution against DDIM's (float64 numpy, the kernel's four expressions)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
+
+import abi_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lion_dpmpp_update", "lion_chain_update_multistep", "lion_chain_update_multistep_cm")
@@ -24,13 +25,7 @@ def _diffusion(sched="linear", T=1000):
 
 def test_three_symbols_are_declared_bound_and_exported():
     from lion_amd import _lib, chain, diffusion_ops
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lion_hip.h")).read(), flags=re.S)
-    lib = ctypes.CDLL(_lib.SO_PATH)
-    for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"{name} not declared in include/lion_hip.h"
-        assert name in _lib.SIGNATURES, f"{name} not bound in _lib.SIGNATURES"
-        assert hasattr(lib, name), f"{name} not exported by the library"
-        assert getattr(_lib.load(), name).argtypes == _lib.SIGNATURES[name][1]
+    abi_check.declared_bound_and_exported(NEW)
     assert "dpmpp_update" in diffusion_ops.__all__ and chain.DPMPP == 2 and {chain.DDIM, chain.DDPM} == {0, 1}
     # bad arguments are refused on the host, before any launch (no GPU here: a launch would be a positive HIP error)
     l = _lib.load()

@@ -4,10 +4,11 @@ tail schedule in float64, the C ABI's argument checks on the host, and the solve
 covariance propagation -- nothing is sampled, so nothing here has statistical noise."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
+
+import abi_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lion_sde_dpmpp_update", "lion_chain_update_multistep_noise", "lion_chain_update_multistep_noise_cm")
@@ -121,13 +122,8 @@ def test_logsnr_tail_is_the_nearest_index_to_uniform_lambda_below_the_start():
 # ---- C ABI ---------------------------------------------------------------------------------------------------------------------
 def test_three_symbols_are_declared_bound_exported_and_refuse_bad_arguments():
     from lion_amd import _lib, chain, diffusion_ops
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lion_hip.h")).read(), flags=re.S)
-    lib = ctypes.CDLL(_lib.SO_PATH)
+    abi_check.declared_bound_and_exported(NEW)
     for name in NEW:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"{name} not declared in include/lion_hip.h"
-        assert name in _lib.SIGNATURES, f"{name} not bound in _lib.SIGNATURES"
-        assert hasattr(lib, name), f"{name} not exported by the library"
-        assert getattr(_lib.load(), name).argtypes == _lib.SIGNATURES[name][1]
         assert name in open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "sde_dpmpp_update" in diffusion_ops.__all__
     assert chain.SDE_DPMPP == 3 and (chain.DDIM, chain.DDPM, chain.DPMPP) == (0, 1, 2)
