@@ -433,6 +433,14 @@ int lion_skinny_finish(const float *A, int ks_a, const float *bias_a, const floa
 int lion_skinny_gemm_se_finish(const float *pin, int ks_in, const float *bias_in, int act_in, const float *wp, int nb, int Cin,
                                int Cout, const float *A, int ks_a, const float *bias_a, const float *resid, float *y,
                                lionStream_t stream);
+/* For tests only: the two entry points above through the plain kernel (operand loads behind the weight loads, two chunks
+ * ahead), which the library itself runs only for ks_in > 8.  Same arguments; the public entry points -- every load of a
+ * round requested before the first wait -- equal them bit for bit (tests/test_skinny_roundtrips_gpu.py). */
+int lion_internal_skinny_gemm_plain(const float *pin, int ks_in, const float *bias_in, int act_in, const float *addT,
+                                    const float *wp, int nb, int Cin, int Cout, float *pout, lionStream_t stream);
+int lion_internal_skinny_gemm_se_finish_plain(const float *pin, int ks_in, const float *bias_in, int act_in, const float *wp,
+                                              int nb, int Cin, int Cout, const float *A, int ks_a, const float *bias_a,
+                                              const float *resid, float *y, lionStream_t stream);
 /* activations of the global denoiser [B, C, 1, 1] <-> the channel-major [ceil(B/32)][C][32] form its layers work on
  * (models/score_sde/resnet.py:195-218 keeps [B, C, 1, 1]); a / b: two tensors per launch (either may be NULL), row strides
  * lda / ldb in floats (0 = one row broadcast over the batch: the time embedding of a chain step). */
@@ -531,6 +539,11 @@ int lion_internal_pwconv_walk(const float *x, const float *wp, const float *bias
  * softmax over the N points of every k row, ctx = softmax(k) v^T (D x D), out = ctx^T q.  D = 32 (every
  * LinearAttention of the models); one workgroup per (batch, head), fp32 MFMA. */
 int lion_linear_attention_core(const float *qkv, int B, int H, int D, int N, float *out, lionStream_t stream);
+/* For tests only: the kernel lion_linear_attention_core takes at N points, with (aligned != 0) or without 16-byte aligned
+ * qkv and out -- 0 the plain kernel (N % 4 != 0 or unaligned), 1 k resident in LDS (N <= 1024), 2 streaming -- and the
+ * plain kernel at any shape, which the other two equal bit for bit (tests/test_attention_roundtrips_gpu.py). */
+int lion_internal_linear_attention_path(int N, int aligned);
+int lion_internal_linear_attention_core_plain(const float *qkv, int B, int H, int D, int N, float *out, lionStream_t stream);
 /* its gradient (training): gout f32[B, H*D, N] -> gqkv f32[B, 3*H*D, N] (softmax backward included; the row dot product
  * sum_n p gp is the 32 x 32 contraction sum_e gctx[d][e] ctx[d][e]: no second sweep over the points). */
 int lion_linear_attention_core_backward(const float *qkv, const float *gout, int B, int H, int D, int N, float *gqkv,

@@ -73,6 +73,8 @@ SIGNATURES = {
     "lion_skinny_splits": (_i, [_i, _i]),
     "lion_skinny_gemm": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "lion_skinny_gemm_se_finish": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "lion_internal_skinny_gemm_plain": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "lion_internal_skinny_gemm_se_finish_plain": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "lion_skinny_finish": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "lion_to_channel_major": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "lion_from_channel_major": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -96,6 +98,8 @@ SIGNATURES = {
     "lion_pwconv_split_grouped_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lion_internal_pwconv_walk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "lion_linear_attention_core": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "lion_internal_linear_attention_path": (_i, [_i, _i]),
+    "lion_internal_linear_attention_core_plain": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "lion_linear_attention_core_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lion_linear_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "lion_affine_swish": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),

@@ -148,6 +148,132 @@ __global__ __launch_bounds__(1024) void skinny_gemm_kernel(const float *__restri
   pout[((size_t)(ks * NB + nb) * Cout + o0 + (tid >> 5)) * 32 + (tid & 31)] = s;
 }
 
+// The same layer with ONE memory round trip per round (skinny_gemm_kernel above stays as the plain form: the fallback for
+// ks_in > 8 and the twin the tests compare with).  In skinny_gemm_kernel the L2-resident operand loads queue behind the
+// four HBM weight loads (vector memory returns in order), chunks 2 and 3 are requested only after chunk 0's data is
+// there, partials 4..7 are loaded and waited for chunk by chunk, and the FIN tail's inputs are requested after the
+// reduction.  Here a wave requests, before its first wait, the FIN tail's inputs (once), then the operand partials,
+// bias_in and addT of the live chunks of a group of CG chunks, then the round's four weight loads; the partial sums,
+// bias and ReLU run while the weights are on their way.  A chunk that is dead for the whole wave (no k-step below s_hi)
+// requests nothing: its operand is the +0 the plain kernel's select leaves.  QN = ks_in partials are unrolled (ADD: with addT); CG = 4
+// where (QN + addT) * 4 chunks fit 64 destination registers (the 128 of a 1024-thread workgroup), else 2, and the second
+// group of a round is then requested when the first has been reduced (the released model's ks_in = 8 slices have two
+// live chunks).  Arithmetic, MFMA sequence, K partition, LDS slices and fences are those of the plain kernel, operation
+// for operation, the + 0.f of its absent partials and absent addT included (they turn a -0 into +0).
+template <bool FIN, int QN, int CG, bool ADD>
+__global__ __launch_bounds__(1024) void skinny_gemm_ahead_kernel(const float *__restrict__ pin, const float *__restrict__ bias_in,
+                                                                 int act_in, const float *__restrict__ addT,
+                                                                 const float *__restrict__ wp, int Cin, int Cout,
+                                                                 float *__restrict__ pout, const float *__restrict__ fa, int ks_a,
+                                                                 const float *__restrict__ bias_a,
+                                                                 const float *__restrict__ resid) {
+  extern __shared__ __attribute__((aligned(16))) float smem[]; // [16][1024]: operand slices, then partial tiles
+  float(*part)[1024] = reinterpret_cast<float(*)[1024]>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int o0 = blockIdx.x * 32, ks = blockIdx.y, KS = gridDim.y, nb = blockIdx.z, NB = gridDim.z;
+  const int cl = lane & 31, kh = lane >> 5;
+  const int ksteps = (Cin + 1) >> 1;
+  const int ksteps4 = (ksteps + 3) >> 2;
+  const float4 *wt4 = reinterpret_cast<const float4 *>(wp + (size_t)blockIdx.x * (ksteps4 * 8) * 32);
+  const size_t in_stride = (size_t)NB * Cin * 32;
+  const float *xb = pin + (size_t)nb * Cin * 32;
+  const float *ab = ADD ? addT + (size_t)nb * Cin * 32 : nullptr; // ADD: addT != NULL (the launcher)
+  const int per = ((ksteps + KS * 16 - 1) / (KS * 16) + 3) & ~3;
+  const int s_lo = min(ksteps, (ks * 16 + wave) * per), s_hi = min(ksteps, s_lo + per);
+  // FIN: the tail's inputs of this thread's output element, requested ahead of everything else
+  const size_t fn = (size_t)NB * Cout * 32, fi = ((size_t)nb * Cout + o0 + (tid >> 5)) * 32 + (tid & 31);
+  float fq[4] = {0.f, 0.f, 0.f, 0.f}, fb = 0.f, fr = 0.f;
+  if (FIN) {
+    if (bias_a) fb = bias_a[o0 + (tid >> 5)];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) fq[q] = fa[(size_t)min(q, ks_a - 1) * fn + fi]; // q >= ks_a: re-read, not added
+    fr = resid[fi];
+  }
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int r0 = 0; r0 < per; r0 += 16) {
+    const int s0 = s_lo + r0;
+    float4 a4[4];
+#pragma unroll
+    for (int gg = 0; gg < 4; gg += CG) {
+      float4 x4[CG][QN], t4[CG];
+      float bq[CG];
+#pragma unroll
+      for (int c = 0; c < CG; ++c) {
+        const int g = gg + c;
+        bq[c] = 0.f;
+        t4[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int q = 0; q < QN; ++q) x4[c][q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (s0 + 4 * g < s_hi) { // wave-uniform: some lane of the chunk is live
+          const int kc = min(2 * (s0 + 4 * g) + (lane >> 3), Cin - 1);
+          const unsigned off = (unsigned)kc * 32u + (unsigned)(lane & 7) * 4u;
+          if (bias_in) bq[c] = bias_in[kc];
+          if (ADD) t4[c] = *reinterpret_cast<const float4 *>(ab + off);
+#pragma unroll
+          for (int q = 0; q < QN; ++q) x4[c][q] = *reinterpret_cast<const float4 *>(xb + q * in_stride + off);
+        }
+      }
+      if (gg == 0) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          a4[g] = ld_stream(&wt4[((size_t)(min(s0 + 4 * g, ksteps4 * 4 - 4) >> 2) * 2 + kh) * 32 + cl]);
+      }
+#pragma unroll
+      for (int c = 0; c < CG; ++c) {
+        const int g = gg + c;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (s0 + 4 * g < s_hi) {
+          const int k = 2 * (s0 + 4 * g) + (lane >> 3);
+          v = make_float4(bq[c], bq[c], bq[c], bq[c]);
+#pragma unroll
+          for (int q = 0; q < (QN > 4 ? QN : 4); ++q) { // fixed order; an absent partial of the first four adds +0
+            const float4 t = q < QN ? x4[c][q < QN ? q : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+            v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+          }
+          if (act_in == 1) { v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w); }
+          v.x += t4[c].x; v.y += t4[c].y; v.z += t4[c].z; v.w += t4[c].w;
+          const bool live = k < Cin && (k >> 1) < s_hi;
+          if (!live) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        *reinterpret_cast<float4 *>(&part[wave][g * 256 + lane * 4]) = v;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int u = 4 * g + e;
+          const float a = e == 0 ? a4[g].x : e == 1 ? a4[g].y : e == 2 ? a4[g].z : a4[g].w;
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, part[wave][(2 * u + kh) * 32 + cl], acc, 0, 0, 0);
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // next round rewrites the slice after these reads
+    __builtin_amdgcn_wave_barrier();
+  }
+  float a = fb;
+  if (FIN) { // the tail's own sum does not depend on the GEMM: ready before the barriers
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a = q < ks_a ? a + fq[q] : a;
+    for (int q = 4; q < ks_a; ++q) a += fa[(size_t)q * fn + fi];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 16; ++i) part[wave][((i & 3) + 8 * (i >> 2) + 4 * kh) * 32 + cl] = acc[i];
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) s += part[w][tid];
+  if (FIN) {
+    float g = 0.f;
+    g += s;
+    pout[fi] = fr + relu_keep_nan(a) * (1.0f / (1.0f + expf(-g)));
+    return;
+  }
+  pout[((size_t)(ks * NB + nb) * Cout + o0 + (tid >> 5)) * 32 + (tid & 31)] = s;
+}
+
 // mode 0: y = sum_q A[q] + bias_a                               (last layer)
 // mode 1: y = resid + relu(sum_q A[q] + bias_a) * sigmoid(sum_q Bp[q])   (ResBlockSEDrop tail, resnet.py:77-86)
 __global__ __launch_bounds__(256) void skinny_finish_kernel(const float *__restrict__ A, int ks_a,
@@ -200,6 +326,56 @@ __global__ void skinny_pack_kernel(const float *__restrict__ w, int Cout, int Ci
   wp[i] = k < Cin ? w[(size_t)(t * 32 + j) * Cin + k] : 0.f;
 }
 
+// One launcher for both forms of a layer.  plain: skinny_gemm_kernel; otherwise the round-trip form wherever it exists
+// (ks_in <= 8, operand offsets below 2^32 floats).
+template <bool FIN>
+int skinny_launch(bool plain, dim3 grid, hipStream_t st, const float *pin, int ks_in, const float *bias_in, int act_in,
+                  const float *addT, const float *wp, int Cin, int Cout, float *pout, const float *fa, int ks_a,
+                  const float *bias_a, const float *resid) {
+  const size_t lds = (size_t)16 * 1024 * 4;
+  if (plain || ks_in > 8 || Cin > (1 << 26))
+    return lion_launch<skinny_gemm_kernel<FIN>>(grid, 1024, lds, st, pin, ks_in, bias_in, act_in, addT, wp, Cin, Cout, pout,
+                                                fa, ks_a, bias_a, resid);
+  const bool add = !FIN && addT;
+  auto go = [&](auto Q) { // CG: 4 chunks at once where (partials + addT) x 4 chunks fit the 64 destination registers
+    return lion_with_flags(add, [&](auto A) {
+      constexpr bool ADD = !FIN && decltype(A)::value;
+      constexpr int QN = decltype(Q)::value, CG = QN + (ADD ? 1 : 0) <= 4 ? 4 : 2;
+      return lion_launch<skinny_gemm_ahead_kernel<FIN, QN, CG, ADD>>(grid, 1024, lds, st, pin, bias_in, act_in, addT, wp, Cin,
+                                                                    Cout, pout, fa, ks_a, bias_a, resid);
+    });
+  };
+  switch (ks_in) {
+  case 1: return go(IntC<1>{});
+  case 2: return go(IntC<2>{});
+  case 3: return go(IntC<3>{});
+  case 4: return go(IntC<4>{});
+  case 5: return go(IntC<5>{});
+  case 6: return go(IntC<6>{});
+  case 7: return go(IntC<7>{});
+  default: return go(IntC<8>{});
+  }
+}
+
+int skinny_gemm_entry(bool plain, const float *pin, int ks_in, const float *bias_in, int act_in, const float *addT,
+                      const float *wp, int nb, int Cin, int Cout, float *pout, lionStream_t stream) {
+  if (!pin || !wp || !pout || nb <= 0 || Cin <= 0 || Cout <= 0 || ks_in < 1 || act_in < 0 || act_in > 1)
+    return LION_EINVAL;
+  if (Cout % 32 != 0) return LION_EUNSUPPORTED;
+  return skinny_launch<false>(plain, dim3(Cout / 32, lion_skinny_splits(Cin, Cout), nb), static_cast<hipStream_t>(stream), pin,
+                              ks_in, bias_in, act_in, addT, wp, Cin, Cout, pout, nullptr, 0, nullptr, nullptr);
+}
+
+int skinny_se_finish_entry(bool plain, const float *pin, int ks_in, const float *bias_in, int act_in, const float *wp, int nb,
+                           int Cin, int Cout, const float *A, int ks_a, const float *bias_a, const float *resid, float *y,
+                           lionStream_t stream) {
+  if (!pin || !wp || !A || !resid || !y || nb <= 0 || Cin <= 0 || Cout <= 0 || ks_in < 1 || ks_a < 1 || act_in < 0 || act_in > 1)
+    return LION_EINVAL;
+  if (Cout % 32 != 0 || lion_skinny_splits(Cin, Cout) != 1) return LION_EUNSUPPORTED;
+  return skinny_launch<true>(plain, dim3(Cout / 32, 1, nb), static_cast<hipStream_t>(stream), pin, ks_in, bias_in, act_in,
+                             nullptr, wp, Cin, Cout, y, A, ks_a, bias_a, resid);
+}
+
 } // namespace
 
 extern "C" {
@@ -230,13 +406,12 @@ int lion_skinny_splits(int Cin, int Cout) {
 // bias_in f32[Cin] or NULL, act_in 0 none / 1 relu, addT f32[nb][Cin][32] or NULL; wp = lion_skinny_pack_weights.
 int lion_skinny_gemm(const float *pin, int ks_in, const float *bias_in, int act_in, const float *addT,
                      const float *wp, int nb, int Cin, int Cout, float *pout, lionStream_t stream) {
-  if (!pin || !wp || !pout || nb <= 0 || Cin <= 0 || Cout <= 0 || ks_in < 1 || act_in < 0 || act_in > 1)
-    return LION_EINVAL;
-  if (Cout % 32 != 0) return LION_EUNSUPPORTED;
-  const size_t lds = (size_t)16 * 1024 * 4;
-  return lion_launch<skinny_gemm_kernel<false>>(dim3(Cout / 32, lion_skinny_splits(Cin, Cout), nb), 1024, lds,
-                                                static_cast<hipStream_t>(stream), pin, ks_in, bias_in, act_in, addT, wp,
-                                                Cin, Cout, pout, nullptr, 0, nullptr, nullptr);
+  return skinny_gemm_entry(false, pin, ks_in, bias_in, act_in, addT, wp, nb, Cin, Cout, pout, stream);
+}
+// For tests only: the same layer through skinny_gemm_kernel, the plain form (what lion_skinny_gemm runs for ks_in > 8).
+int lion_internal_skinny_gemm_plain(const float *pin, int ks_in, const float *bias_in, int act_in, const float *addT,
+                                    const float *wp, int nb, int Cin, int Cout, float *pout, lionStream_t stream) {
+  return skinny_gemm_entry(true, pin, ks_in, bias_in, act_in, addT, wp, nb, Cin, Cout, pout, stream);
 }
 
 // The block's last GEMM with its tail: y f32[nb][Cout][32] = resid + relu(sum_q A[q] + bias_a) * sigmoid(W act_in(sum pin + bias_in)),
@@ -245,13 +420,12 @@ int lion_skinny_gemm(const float *pin, int ks_in, const float *bias_in, int act_
 int lion_skinny_gemm_se_finish(const float *pin, int ks_in, const float *bias_in, int act_in, const float *wp, int nb, int Cin,
                                int Cout, const float *A, int ks_a, const float *bias_a, const float *resid, float *y,
                                lionStream_t stream) {
-  if (!pin || !wp || !A || !resid || !y || nb <= 0 || Cin <= 0 || Cout <= 0 || ks_in < 1 || ks_a < 1 || act_in < 0 || act_in > 1)
-    return LION_EINVAL;
-  if (Cout % 32 != 0 || lion_skinny_splits(Cin, Cout) != 1) return LION_EUNSUPPORTED;
-  const size_t lds = (size_t)16 * 1024 * 4;
-  return lion_launch<skinny_gemm_kernel<true>>(dim3(Cout / 32, 1, nb), 1024, lds, static_cast<hipStream_t>(stream), pin,
-                                               ks_in, bias_in, act_in, nullptr, wp, Cin, Cout, y, A, ks_a, bias_a,
-                                               resid);
+  return skinny_se_finish_entry(false, pin, ks_in, bias_in, act_in, wp, nb, Cin, Cout, A, ks_a, bias_a, resid, y, stream);
+}
+int lion_internal_skinny_gemm_se_finish_plain(const float *pin, int ks_in, const float *bias_in, int act_in, const float *wp,
+                                              int nb, int Cin, int Cout, const float *A, int ks_a, const float *bias_a,
+                                              const float *resid, float *y, lionStream_t stream) {
+  return skinny_se_finish_entry(true, pin, ks_in, bias_in, act_in, wp, nb, Cin, Cout, A, ks_a, bias_a, resid, y, stream);
 }
 
 // y f32[nb][C][32] from partials: mode 0: sum_q A[q] + bias_a; mode 1: resid + relu(sum_q A[q] + bias_a) *
