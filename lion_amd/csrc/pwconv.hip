@@ -585,54 +585,74 @@ static int pw_grid_x(int tiles, int gy, int B, const PwSched &o) {
   return lion_cdiv(tiles, walk);
 }
 
-template <int CB, int VB>
-static int launch_pw(const float *x, const float *wp, const float *bias, float *y, int B, int Cin, int Cout, int L,
-                     const float *pa, const float *pb, float *stats, hipStream_t st, const PwSched &o = {}) {
-  const int Cpad = pw_pad(Cout), tiles = lion_cdiv(L, 4 * VB * 32);
-  const dim3 grid(pw_grid_x(tiles, Cpad / (CB * 32), B, o), Cpad / (CB * 32), B);
-  // weights through LDS only when a workgroup's column tile is one of many (the staging is then amortised by the L2)
-  const bool wlds = o.wlds < 0 ? (long)tiles * B >= 2048 : o.wlds != 0;
-  const size_t lds = pw_lds(CB, Cin, pa != nullptr, wlds);
-  return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
-    return lion_with_flags(wlds, [&](auto WLDS) {
-      return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, decltype(WLDS)::value>>(
-          grid, 256, lds, st, x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, nullptr, nullptr);
-    });
-  });
+// The one switch on the plan: cb -> f(IntC<CB>{}, IntC<VB>{}) for the four tiles pw_plan hands out.
+template <typename F> static int pw_with_plan(const PwPlan &p, F f) {
+  switch (p.cb) {
+  case 1: return f(IntC<1>{}, IntC<4>{});
+  case 2: return f(IntC<2>{}, IntC<4>{});
+  case 4: return f(IntC<4>{}, IntC<2>{});
+  case 8: return f(IntC<8>{}, IntC<1>{});
+  default: return LION_EUNSUPPORTED; // pw_plan found no tile
+  }
 }
 
-// the gathered-operand form: launch_pw's grid, LDS and weights-through-LDS choice, no prologue
-template <int CB, int VB>
-static int launch_pw_grouped(const PwGather &g, const float *wp, const float *bias, float *y, int B, int Cin, int Cout, int L,
-                             float *stats, hipStream_t st, const PwSched &o = {}) {
-  const int Cpad = pw_pad(Cout), tiles = lion_cdiv(L, 4 * VB * 32);
-  const dim3 grid(pw_grid_x(tiles, Cpad / (CB * 32), B, o), Cpad / (CB * 32), B);
-  const bool wlds = o.wlds < 0 ? (long)tiles * B >= 2048 : o.wlds != 0;
-  const size_t lds = pw_lds(CB, Cin, false, wlds);
-  return lion_with_flags(stats != nullptr, wlds, [&](auto ST, auto WLDS) {
-    return lion_launch<pwconv_kernel<CB, VB, false, decltype(ST)::value, decltype(WLDS)::value, 0, PwGather>>(
-        grid, 256, lds, st, nullptr, wp, bias, y, Cin, pw_stride(Cout), Cout, L, nullptr, nullptr, stats, nullptr, nullptr, g);
-  });
-}
-
-// the two passes of the "activated maximum without the layer's output" form (OUT = 1, OUT = 2): large activations only
-// (weights through LDS), same tiling and the same column tiles of the statistics as launch_pw
-template <int CB, int VB>
-static int launch_pw_max(const float *x, const float *wp, const float *bias, float *ymax, int B, int Cin, int Cout, int L,
-                         const float *pa, const float *pb, float *stats, const float *oa, const float *ob, hipStream_t st,
-                         const PwSched &o = {}) {
-  const int Cpad = pw_pad(Cout), tiles = lion_cdiv(L, 4 * VB * 32);
-  const dim3 grid(pw_grid_x(tiles, Cpad / (CB * 32), B, o), Cpad / (CB * 32), B);
-  if (o.wlds < 0 && (long)tiles * B < 2048) return LION_EUNSUPPORTED;
-  const bool wlds = o.wlds != 0;
-  const size_t lds = pw_lds(CB, Cin, pa != nullptr, wlds);
-  // first pass (no out_a): OUT = 1 with the statistics; second pass: OUT = 2 without them
-  return lion_with_flags(pa != nullptr, oa != nullptr, [&](auto PRO, auto SECOND) {
-    return lion_with_flags(wlds, [&](auto WLDS) {
+// What an entry point asks of a launcher.  The form is a compile-time tag, so that only the kernels a form can need exist:
+//   PW_STORE   x is a tensor, y is stored (prologue and statistics as given);
+//   PW_GATHER  the operand is `g` (x unused): no prologue, y is stored;
+//   PW_MAX     the two passes of the "activated maximum without the layer's output" form: oa == nullptr -> OUT = 1, the
+//              statistics and nothing else; oa set -> OUT = 2, the maximum into y (= ymax) and no statistics.
+enum PwForm { PW_STORE, PW_GATHER, PW_MAX };
+struct PwCall {
+  const float *x, *wp, *bias;
+  float *y, *stats;
+  int B, Cin, Cout, L;
+  hipStream_t st;
+  const float *pa = nullptr, *pb = nullptr, *oa = nullptr, *ob = nullptr;
+  PwGather g = {};
+  PwSched o = {};
+};
+// form and the call's flags -> f(PRO, STATS, OUT, gather...), the template arguments after the tile and the trailing
+// kernel argument: the kernels' static_asserts reject a combination that no form has
+template <PwForm FORM, typename F> static int pw_with_form(const PwCall &c, F f) {
+  if constexpr (FORM == PW_GATHER) {
+    return lion_with_flags(c.stats != nullptr, [&](auto ST) { return f(BoolC<false>{}, ST, IntC<0>{}, c.g); });
+  } else if constexpr (FORM == PW_MAX) {
+    return lion_with_flags(c.pa != nullptr, c.oa != nullptr, [&](auto PRO, auto SECOND) {
       constexpr bool second = decltype(SECOND)::value;
-      return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, !second, decltype(WLDS)::value, second ? 2 : 1>>(
-          grid, 256, lds, st, x, wp, bias, ymax, Cin, pw_stride(Cout), Cout, L, pa, pb, stats, oa, ob);
+      return f(PRO, BoolC<!second>{}, IntC<second ? 2 : 1>{});
     });
+  } else {
+    return lion_with_flags(c.pa != nullptr, c.stats != nullptr, [&](auto PRO, auto ST) { return f(PRO, ST, IntC<0>{}); });
+  }
+}
+
+template <PwForm FORM, int CB, int VB> static int launch_pw(const PwCall &c, IntC<CB>, IntC<VB>) {
+  const int gy = pw_pad(c.Cout) / (CB * 32), tiles = lion_cdiv(c.L, 4 * VB * 32);
+  const dim3 grid(pw_grid_x(tiles, gy, c.B, c.o), gy, c.B);
+  // weights through LDS only when a workgroup's column tile is one of many (the staging is then amortised by the L2); the
+  // max form is for large activations only and refuses the others, whoever calls
+  const bool many = (long)tiles * c.B >= 2048;
+  if (FORM == PW_MAX && c.o.wlds < 0 && !many) return LION_EUNSUPPORTED;
+  const bool wlds = c.o.wlds < 0 ? many : c.o.wlds != 0;
+  const size_t lds = pw_lds(CB, c.Cin, c.pa != nullptr, wlds);
+  return pw_with_form<FORM>(c, [&](auto PRO, auto ST, auto OUT, auto... gather) {
+    return lion_with_flags(wlds, [&](auto WLDS) {
+      return lion_launch<pwconv_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, decltype(WLDS)::value,
+                                       decltype(OUT)::value, decltype(gather)...>>(
+          grid, 256, lds, c.st, c.x, c.wp, c.bias, c.y, c.Cin, pw_stride(c.Cout), c.Cout, c.L, c.pa, c.pb, c.stats, c.oa, c.ob,
+          gather...);
+    });
+  });
+}
+
+// pwconv_small_kernel (L <= PW_SMALL_L; PW_STORE or PW_GATHER): one workgroup per 32 columns x 64 channels
+template <PwForm FORM> static int launch_pw_small(const PwCall &c) {
+  const dim3 grid(lion_cdiv(c.L, 32), pw_stride(c.Cout) / 64, c.B);
+  const size_t lds = c.pa ? (size_t)2 * c.Cin * 4 : 0;
+  if (lds > 64 * 1024) return LION_EUNSUPPORTED;
+  return pw_with_form<FORM>(c, [&](auto PRO, auto ST, auto, auto... gather) {
+    return lion_launch<pwconv_small_kernel<decltype(PRO)::value, decltype(ST)::value, decltype(gather)...>>(
+        grid, 256, lds, c.st, c.x, c.wp, c.bias, c.y, c.Cin, pw_stride(c.Cout), c.Cout, c.L, c.pa, c.pb, c.stats, gather...);
   });
 }
 
@@ -654,13 +674,8 @@ int lion_pwconv_forward_max(const float *x, const float *wp, const float *bias, 
   if (L % 32 != 0 || L <= PW_SMALL_L || L >= PW_MAX_L) return LION_EUNSUPPORTED;
   const PwPlan p = pw_plan(Cout, Cin);
   if (!p.cb) return LION_EUNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (p.cb) {
-  case 1: return launch_pw_max<1, 4>(x, wp, bias, ymax, B, Cin, Cout, L, pro_a, pro_b, stats, out_a, out_b, st);
-  case 2: return launch_pw_max<2, 4>(x, wp, bias, ymax, B, Cin, Cout, L, pro_a, pro_b, stats, out_a, out_b, st);
-  case 4: return launch_pw_max<4, 2>(x, wp, bias, ymax, B, Cin, Cout, L, pro_a, pro_b, stats, out_a, out_b, st);
-  default: return launch_pw_max<8, 1>(x, wp, bias, ymax, B, Cin, Cout, L, pro_a, pro_b, stats, out_a, out_b, st);
-  }
+  const PwCall c{x, wp, bias, ymax, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream), pro_a, pro_b, out_a, out_b};
+  return pw_with_plan(p, [&](auto CB, auto VB) { return launch_pw<PW_MAX>(c, CB, VB); });
 }
 
 size_t lion_pwconv_packed_floats(int Cout, int Cin) { return (size_t)((Cin + 1) / 2 * 2) * pw_stride(Cout); }
@@ -688,24 +703,11 @@ int lion_pwconv_forward(const float *x, const float *wp, const float *bias, int 
                         const float *pro_a, const float *pro_b, float *y, float *stats, lionStream_t stream) {
   if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0) return LION_EINVAL;
   if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (L <= PW_SMALL_L) {
-    const dim3 grid(lion_cdiv(L, 32), pw_stride(Cout) / 64, B);
-    const size_t lds = pro_a ? (size_t)2 * Cin * 4 : 0;
-    if (lds > 64 * 1024) return LION_EUNSUPPORTED;
-    return lion_with_flags(pro_a != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
-      return lion_launch<pwconv_small_kernel<decltype(PRO)::value, decltype(ST)::value>>(
-          grid, 256, lds, st, x, wp, bias, y, Cin, pw_stride(Cout), Cout, L, pro_a, pro_b, stats);
-    });
-  }
+  const PwCall c{x, wp, bias, y, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream), pro_a, pro_b};
+  if (L <= PW_SMALL_L) return launch_pw_small<PW_STORE>(c);
   const PwPlan p = pw_plan(Cout, Cin);
   if (!p.cb || L >= PW_MAX_L) return LION_EUNSUPPORTED;
-  switch (p.cb) {
-  case 1: return launch_pw<1, 4>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  case 2: return launch_pw<2, 4>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  case 4: return launch_pw<4, 2>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  default: return launch_pw<8, 1>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  }
+  return pw_with_plan(p, [&](auto CB, auto VB) { return launch_pw<PW_STORE>(c, CB, VB); });
 }
 
 // lion_group_points_forward followed by lion_pwconv_forward (no prologue) without the [B, 3 + C, M, U] tensor between them:
@@ -719,23 +721,12 @@ int lion_pwconv_grouped_forward(const float *coords, const float *centers, const
   if (C > 0 && !feat) return LION_EINVAL;
   if ((long)M * U >= (1L << 31) || (long)C * N >= (1L << 31)) return LION_EUNSUPPORTED;
   const int Cin = 3 + C, L = M * U;
-  const PwGather g{coords, centers, C > 0 ? feat : nullptr, idx, C, N, U};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (L <= PW_SMALL_L) {
-    const dim3 grid(lion_cdiv(L, 32), pw_stride(Cout) / 64, B);
-    return lion_with_flags(stats != nullptr, [&](auto ST) {
-      return lion_launch<pwconv_small_kernel<false, decltype(ST)::value, PwGather>>(
-          grid, 256, 0, st, nullptr, wp, bias, y, Cin, pw_stride(Cout), Cout, L, nullptr, nullptr, stats, g);
-    });
-  }
+  PwCall c{nullptr, wp, bias, y, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream)};
+  c.g = PwGather{coords, centers, C > 0 ? feat : nullptr, idx, C, N, U};
+  if (L <= PW_SMALL_L) return launch_pw_small<PW_GATHER>(c);
   const PwPlan p = pw_plan(Cout, Cin);
   if (!p.cb || L >= PW_MAX_L || N >= PW_MAX_L) return LION_EUNSUPPORTED;
-  switch (p.cb) {
-  case 1: return launch_pw_grouped<1, 4>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
-  case 2: return launch_pw_grouped<2, 4>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
-  case 4: return launch_pw_grouped<4, 2>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
-  default: return launch_pw_grouped<8, 1>(g, wp, bias, y, B, Cin, Cout, L, stats, st);
-  }
+  return pw_with_plan(p, [&](auto CB, auto VB) { return launch_pw<PW_GATHER>(c, CB, VB); });
 }
 
 // For tests only: pwconv_kernel itself at ANY L (the entry points above hand L <= 4096 to pwconv_small_kernel and refuse
@@ -757,21 +748,14 @@ int lion_internal_pwconv_walk(const float *x, const float *wp, const float *bias
   if ((maxform && L % 32 != 0) || L >= PW_MAX_L || (grouped && N >= PW_MAX_L)) return LION_EUNSUPPORTED;
   const PwPlan p = pw_plan(Cout, Cin);
   if (!p.cb) return LION_EUNSUPPORTED;
-  const PwSched o{max_wg, lds_weights};
-  const PwGather g{coords, centers, Cin > 3 ? feat : nullptr, idx, Cin - 3, N, U};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  auto run = [&](auto CBc, auto VBc) {
-    constexpr int CB = decltype(CBc)::value, VB = decltype(VBc)::value;
-    if (grouped) return launch_pw_grouped<CB, VB>(g, wp, bias, y, B, Cin, Cout, L, stats, st, o);
-    if (maxform) return launch_pw_max<CB, VB>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, out_a, out_b, st, o);
-    return launch_pw<CB, VB>(x, wp, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st, o);
-  };
-  switch (p.cb) {
-  case 1: return run(IntC<1>{}, IntC<4>{});
-  case 2: return run(IntC<2>{}, IntC<4>{});
-  case 4: return run(IntC<4>{}, IntC<2>{});
-  default: return run(IntC<8>{}, IntC<1>{});
-  }
+  const PwCall c{grouped ? nullptr : x, wp, bias, y, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream),
+                 pro_a, pro_b, out_a, out_b, PwGather{coords, centers, Cin > 3 ? feat : nullptr, idx, Cin - 3, N, U},
+                 PwSched{max_wg, lds_weights}};
+  return pw_with_plan(p, [&](auto CB, auto VB) {
+    if (grouped) return launch_pw<PW_GATHER>(c, CB, VB);
+    if (maxform) return launch_pw<PW_MAX>(c, CB, VB);
+    return launch_pw<PW_STORE>(c, CB, VB);
+  });
 }
 
 // y f32[B,O] = act(x f32[B,K] W^T + bias), wp = lion_pwconv_pack_weights(W f32[O,K]) (k-major, O padded to 32);

@@ -474,31 +474,53 @@ static PwSplitPlan pws_plan(int Cout) {
 }
 static size_t pws_halfs(int Cout, int Cin) { return (size_t)((Cin + KS - 1) / KS) * 4 * pws_pad(Cout) * 8; }
 
-template <int CB, int VB, int NR, bool WIDE>
-static int launch_pws(const float *x, const u4 *wp, const float *wtail, const float *bias, float *y, int B, int Cin,
-                      int Cout, int L, const float *pa, const float *pb, float *stats, hipStream_t st) {
-  const int Cpad = pws_pad(Cout), nchunks = (Cin + KS - 1) / KS;
-  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
-  const size_t ring = (size_t)NR * (4 * CB * 32 * 16 + (WIDE ? KS * 128 * VB * 4 : 0)), tile = (size_t)4 * 32 * 36 * 4; // weight ring, reused by the statistics
-  const size_t lds = (ring > tile ? ring : tile) + (size_t)((pa ? 2 * nchunks * KS : 0) + CB * 32 + 8 * CB * 32 * 2) * 4;
-  return lion_with_flags(pa != nullptr, stats != nullptr, [&](auto PRO, auto ST) {
-    return lion_launch<pwconv_split_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, NR, WIDE>>(
-        grid, 256, lds, st, x, wp, wtail, bias, y, Cin, Cpad, Cout, L, pa, pb, stats);
-  });
+// The one switch on the plan: cb -> f(IntC<CB>{}, IntC<VB>{}) for the three tiles pws_plan hands out.
+template <typename F> static int pws_with_plan(const PwSplitPlan &p, F f) {
+  switch (p.cb) {
+  case 4: return f(IntC<4>{}, IntC<1>{});
+  case 2: return f(IntC<2>{}, IntC<2>{});
+  case 1: return f(IntC<1>{}, IntC<2>{});
+  default: return LION_EUNSUPPORTED;
+  }
 }
 
-// the gathered-operand form: launch_pws's grid and LDS for the 4-byte path, no prologue
-template <int CB, int VB, int NR>
-static int launch_pws_grouped(const PwGather &g, const u4 *wp, const float *wtail, const float *bias, float *y, int B, int Cin,
-                              int Cout, int L, float *stats, hipStream_t st) {
-  const int Cpad = pws_pad(Cout);
-  const dim3 grid(lion_cdiv(L, 4 * VB * 32), Cpad / (CB * 32), B);
-  const size_t ring = (size_t)NR * (4 * CB * 32 * 16), tile = (size_t)4 * 32 * 36 * 4;
-  const size_t lds = (ring > tile ? ring : tile) + (size_t)(CB * 32 + 8 * CB * 32 * 2) * 4;
-  return lion_with_flags(stats != nullptr, [&](auto ST) {
-    return lion_launch<pwconv_split_kernel<CB, VB, false, decltype(ST)::value, NR, false, PwGather>>(
-        grid, 256, lds, st, nullptr, wp, wtail, bias, y, Cin, Cpad, Cout, L, nullptr, nullptr, stats, g);
-  });
+// The form of a call, a compile-time tag: the 4-byte transport, the 16-byte transport (WIDE), or the gathered operand `g`
+// (x unused, 4-byte transport, no prologue).  With the plan it decides the ring depth (the macros above).
+enum PwsForm { PWS_NARROW, PWS_WIDE, PWS_GATHER };
+constexpr int pws_ring_depth(PwsForm form, int cb) {
+  if (form == PWS_WIDE) return cb == 4 ? PWS_NR_W41 : cb == 2 ? PWS_NR_W22 : PWS_NR_W12;
+  if (form == PWS_GATHER) return cb == 2 ? PWS_NR_G22 : PWS_NR_G;
+  return PWS_NR;
+}
+struct PwsCall {
+  const float *x;
+  const uint16_t *wp; // the packed pieces, then the tail
+  const float *bias;
+  float *y, *stats;
+  int B, Cin, Cout, L;
+  hipStream_t st;
+  const float *pa = nullptr, *pb = nullptr;
+  PwGather g = {};
+};
+
+template <PwsForm FORM, int CB, int VB> static int launch_pws(const PwsCall &c, IntC<CB>, IntC<VB>) {
+  constexpr int NR = pws_ring_depth(FORM, CB);
+  constexpr bool WIDE = FORM == PWS_WIDE;
+  const int Cpad = pws_pad(c.Cout), nchunks = (c.Cin + KS - 1) / KS;
+  const dim3 grid(lion_cdiv(c.L, 4 * VB * 32), Cpad / (CB * 32), c.B);
+  // a ring slot: the chunk's weight slice and (WIDE) its activation rows; the statistics reuse the ring
+  const size_t ring = (size_t)NR * (4 * CB * 32 * 16 + (WIDE ? KS * 128 * VB * 4 : 0)), tile = (size_t)4 * 32 * 36 * 4;
+  const size_t lds = (ring > tile ? ring : tile) + (size_t)((c.pa ? 2 * nchunks * KS : 0) + CB * 32 + 8 * CB * 32 * 2) * 4;
+  const u4 *w4 = reinterpret_cast<const u4 *>(c.wp);
+  const float *wtail = reinterpret_cast<const float *>(c.wp + pws_halfs(c.Cout, c.Cin));
+  auto go = [&](auto PRO, auto ST, auto... gather) {
+    return lion_launch<pwconv_split_kernel<CB, VB, decltype(PRO)::value, decltype(ST)::value, NR, WIDE, decltype(gather)...>>(
+        grid, 256, lds, c.st, c.x, w4, wtail, c.bias, c.y, c.Cin, Cpad, c.Cout, c.L, c.pa, c.pb, c.stats, gather...);
+  };
+  if constexpr (FORM == PWS_GATHER)
+    return lion_with_flags(c.stats != nullptr, [&](auto ST) { return go(BoolC<false>{}, ST, c.g); });
+  else
+    return lion_with_flags(c.pa != nullptr, c.stats != nullptr, go);
 }
 
 } // namespace
@@ -553,27 +575,12 @@ int lion_pwconv_split_forward(const float *x, const uint16_t *wp, const float *b
   if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0) return LION_EINVAL;
   if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
   if ((long)Cin * L >= (1L << 29) || Cin > 4096) return LION_EUNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const u4 *w4 = reinterpret_cast<const u4 *>(wp);
-  const float *wtail = reinterpret_cast<const float *>(wp + pws_halfs(Cout, Cin));
-  const PwSplitPlan p = pws_plan(Cout);
+  const PwsCall c{x, wp, bias, y, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream), pro_a, pro_b};
   // the 16-byte transport needs whole 16-byte pieces per row: L % 4 == 0 (which also aligns every row and batch stride)
   // and 16-byte aligned x and y; everything else runs the 4-byte path
   const bool wide = L % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
-  if (wide) {
-    switch (p.cb) {
-    case 4: return launch_pws<4, 1, PWS_NR_W41, true>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-    case 2: return launch_pws<2, 2, PWS_NR_W22, true>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-    case 1: return launch_pws<1, 2, PWS_NR_W12, true>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-    default: return LION_EUNSUPPORTED;
-    }
-  }
-  switch (p.cb) {
-  case 4: return launch_pws<4, 1, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  case 2: return launch_pws<2, 2, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  case 1: return launch_pws<1, 2, PWS_NR, false>(x, w4, wtail, bias, y, B, Cin, Cout, L, pro_a, pro_b, stats, st);
-  default: return LION_EUNSUPPORTED;
-  }
+  if (wide) return pws_with_plan(pws_plan(Cout), [&](auto CB, auto VB) { return launch_pws<PWS_WIDE>(c, CB, VB); });
+  return pws_with_plan(pws_plan(Cout), [&](auto CB, auto VB) { return launch_pws<PWS_NARROW>(c, CB, VB); });
 }
 
 // lion_group_points_forward followed by lion_pwconv_split_forward (no prologue) without the [B, 3 + C, M, U] tensor between
@@ -587,16 +594,9 @@ int lion_pwconv_split_grouped_forward(const float *coords, const float *centers,
   const long Cin_l = 3L + C, L_l = (long)M * U;
   if (Cin_l * L_l >= (1L << 29) || Cin_l > 4096 || Cin_l * N >= (1L << 29)) return LION_EUNSUPPORTED; // 32-bit byte offsets
   const int Cin = (int)Cin_l, L = (int)L_l;
-  const PwGather g{coords, centers, C > 0 ? feat : nullptr, idx, C, N, U};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const u4 *w4 = reinterpret_cast<const u4 *>(wp);
-  const float *wtail = reinterpret_cast<const float *>(wp + pws_halfs(Cout, Cin));
-  switch (pws_plan(Cout).cb) {
-  case 4: return launch_pws_grouped<4, 1, PWS_NR_G>(g, w4, wtail, bias, y, B, Cin, Cout, L, stats, st);
-  case 2: return launch_pws_grouped<2, 2, PWS_NR_G22>(g, w4, wtail, bias, y, B, Cin, Cout, L, stats, st);
-  case 1: return launch_pws_grouped<1, 2, PWS_NR_G>(g, w4, wtail, bias, y, B, Cin, Cout, L, stats, st);
-  default: return LION_EUNSUPPORTED;
-  }
+  PwsCall c{nullptr, wp, bias, y, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream)};
+  c.g = PwGather{coords, centers, C > 0 ? feat : nullptr, idx, C, N, U};
+  return pws_with_plan(pws_plan(Cout), [&](auto CB, auto VB) { return launch_pws<PWS_GATHER>(c, CB, VB); });
 }
 
 } // extern "C"

@@ -2,6 +2,7 @@
 conv -> AdaGN -> Swish -> conv -> AdaGN -> SE3d -> devoxelize with no stand-alone pass over the grid.
 Thin wrappers over lion_conv3d_k3_fused_forward / lion_groupnorm_fold /
 lion_trilinear_devoxelize_affine_forward (include/lion_hip.h)."""
+import collections
 import os
 
 import torch
@@ -68,6 +69,16 @@ class FoldSpec:
         return a, b_
 
 
+def _pro_pair(pro):
+    """prologue (A, Bs) | None -> two contiguous tensors or (None, None)"""
+    return (None, None) if pro is None else (pro[0].contiguous(), pro[1].contiguous())
+
+
+def _bias(bias):
+    """a layer's bias | None -> contiguous and detached, or None"""
+    return None if bias is None else bias.detach().contiguous()
+
+
 def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, split=None, fold=None):
     """x [B,Cin,r,r,r] -> (y [B,Cout,r,r,r], stats [B,Cout,T,2] | None).  pro = (A, Bs) applies
     swish(x*A+Bs) to the input on the fly.
@@ -95,17 +106,16 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
     x = x.contiguous()
     wp = conv_ops.split_packed_weight(conv.weight) if use_split else packed_weight(conv.weight)
     y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
-    pa = pb = pbias = tconst = None
-    if pro is not None:
-        pa, pb = pro[0].contiguous(), pro[1].contiguous()
-    bias = conv.bias.detach().contiguous() if conv.bias is not None else None
+    pbias = tconst = None
+    pa, pb = _pro_pair(pro)
+    bias = _bias(conv.bias)
     sparse = occ is not None and r >= 16
     if sparse and pro is not None:
         if prev_conv is None or cin > 256:
             sparse = False
         else:
             ws = border_weight_sums(conv.weight)
-            pbias = prev_conv.bias.detach().contiguous() if prev_conv.bias is not None else None
+            pbias = _bias(prev_conv.bias)
             tconst = torch.empty((b, 27, cout), device=x.device, dtype=torch.float32)
             _lib.call("lion_conv3d_const_response", ws, bias, pbias, pa, pb, b, cin, cout, tconst)
     stats = None
@@ -237,6 +247,31 @@ def pw_use_split(split, b, cin, cout, L):
     return bool(split) and can
 
 
+PwRoute = collections.namedtuple("PwRoute", "split forward grouped stat_tiles cache pack")
+_PW_ROUTES = {
+    False: PwRoute(False, "lion_pwconv_forward", "lion_pwconv_grouped_forward", "lion_pwconv_stat_tiles", _PW_CACHE, _pw_pack),
+    True: PwRoute(True, "lion_pwconv_split_forward", "lion_pwconv_split_grouped_forward", "lion_pwconv_split_stat_tiles",
+                  _PW_SPLIT_CACHE, _pw_split_pack)}
+
+
+def pw_route(b, cin, cout, L, split=None):
+    """the kernels a 1x1 convolution of this shape runs on (split as pw_use_split): the entry points .forward / .grouped, the
+    tile-count query .stat_tiles of their statistics, the packed weights' .cache and .pack (uncached).  No tensors, no library."""
+    return _PW_ROUTES[pw_use_split(split, b, cin, cout, L)]
+
+
+def _pw_stats(route, b, cin, cout, L, like):
+    """the empty tile-sums tensor [B,Cout,T,2] of a launch on `route`, on like's device"""
+    tiles = getattr(_lib.load(), route.stat_tiles)(cout, cin, L)
+    return torch.empty((b, cout, tiles, 2), device=like.device, dtype=torch.float32)
+
+
+def is_plain_1x1(conv):
+    """a pointwise layer: one group, kernel size 1, stride 1, no padding"""
+    return (conv.groups == 1 and all(k == 1 for k in conv.kernel_size) and all(s == 1 for s in conv.stride)
+            and all(p == 0 for p in conv.padding))
+
+
 def pw_supported(conv, x):
     """every kernel-size-1 Conv1d / Conv2d whose weight tile fits LDS (all of the released models'): large
     activations (set-abstraction MLPs) for the bytes, short ones (L = 16..256 points, classifier, attention
@@ -245,8 +280,7 @@ def pw_supported(conv, x):
         L = x[0, 0].numel()
         if not (conv.out_channels in (32, 64, 128, 256) and L >= 1024 and x.shape[0] * L * conv.out_channels >= (1 << 22)):
             return False
-    return (conv.groups == 1 and all(k == 1 for k in conv.kernel_size) and all(s == 1 for s in conv.stride)
-            and all(p == 0 for p in conv.padding) and x.is_cuda and x.dtype == torch.float32 and x[0, 0].numel() > 0
+    return (is_plain_1x1(conv) and x.is_cuda and x.dtype == torch.float32 and x[0, 0].numel() > 0
             and _lib.load().lion_pwconv_stat_tiles(conv.out_channels, conv.in_channels, x[0, 0].numel()) > 0)
 
 
@@ -254,22 +288,15 @@ def pwconv_fused(x, conv, pro=None, want_stats=True, split=None):
     """1x1 conv of a [B,Cin,*] activation on the MFMA kernel: y [B,Cout,*] and its GroupNorm tile sums
     [B,Cout,T,2]; pro = (A, Bs) applies swish(x*A+Bs) (the previous layer's AdaGN + Swish) in flight.
     split: see pw_use_split (None = the split-operand kernel for long activations, the fp32 MFMA kernels for short)."""
-    lib = _lib.load()
     x = x.contiguous()
     b, cin = x.shape[:2]
     L = x[0, 0].numel()
     cout = conv.out_channels
-    use_split = pw_use_split(split, b, cin, cout, L)
-    wp = _PW_SPLIT_CACHE.get(conv.weight) if use_split else pw_packed_weight(conv.weight)
+    route = pw_route(b, cin, cout, L, split)
     y = torch.empty((b, cout) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-    tiles = (lib.lion_pwconv_split_stat_tiles if use_split else lib.lion_pwconv_stat_tiles)(cout, cin, L)
-    stats = torch.empty((b, cout, tiles, 2), device=x.device, dtype=torch.float32) if want_stats else None
-    pa = pb = None
-    if pro is not None:
-        pa, pb = pro[0].contiguous(), pro[1].contiguous()
-    bias = conv.bias.detach().contiguous() if conv.bias is not None else None
-    _lib.call("lion_pwconv_split_forward" if use_split else "lion_pwconv_forward",
-              x, wp, bias, b, cin, cout, L, pa, pb, y, stats)
+    stats = _pw_stats(route, b, cin, cout, L, x) if want_stats else None
+    pa, pb = _pro_pair(pro)
+    _lib.call(route.forward, x, route.cache.get(conv.weight), _bias(conv.bias), b, cin, cout, L, pa, pb, y, stats)
     return y, stats
 
 
@@ -296,10 +323,8 @@ def pwconv_max_recompute(x, conv, gn, style, pro):
     if tiles <= 0:
         return None
     stats = torch.empty((b, cout, tiles, 2), device=x.device, dtype=torch.float32)
-    pa = pb = None
-    if pro is not None:
-        pa, pb = pro[0].contiguous(), pro[1].contiguous()
-    bias = conv.bias.detach().contiguous() if conv.bias is not None else None
+    pa, pb = _pro_pair(pro)
+    bias = _bias(conv.bias)
     if not _lib.call("lion_pwconv_forward_max", x, wp, bias, b, cin, cout, L, pa, pb, None, None, stats, None,
                      unsupported_ok=True):   # pass 1: the sums
         return None   # LION_EUNSUPPORTED: the caller takes the stored-output path
@@ -322,21 +347,19 @@ def pwconv_raw(x, w2d, bias=None, cached_param=None, transposed=False):
     L = x[0, 0].numel()
     if not (x.is_cuda and x.dtype == torch.float32 and L > 0 and lib.lion_pwconv_stat_tiles(cout, cin, L) > 0):
         return None
-    use_split = pw_use_split(None, b, cin, cout, L)
-    if transposed and use_split and cached_param is not None:
-        wf = _PW_SPLIT_CACHE.get(cached_param)
+    route = pw_route(b, cin, cout, L)
+    if transposed and route.split and cached_param is not None:
+        wf = route.cache.get(cached_param)
         wp = torch.empty((lib.lion_pwconv_split_packed_halfs(cout, cin),), device=x.device, dtype=torch.int16)
         _lib.call("lion_pwconv_split_pack_weights_t", w2d.detach().contiguous(), cin, cout, wf, wp)
     elif transposed:
-        wp = (_pw_split_pack if use_split else _pw_pack)(w2d.detach().t().contiguous())
+        wp = route.pack(w2d.detach().t().contiguous())
     elif cached_param is not None:
-        wp = _PW_SPLIT_CACHE.get(cached_param) if use_split else _PW_CACHE.get(cached_param)
+        wp = route.cache.get(cached_param)
     else:
-        wp = (_pw_split_pack if use_split else _pw_pack)(w2d)
+        wp = route.pack(w2d)
     y = torch.empty((b, cout) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-    bias_c = bias.detach().contiguous() if bias is not None else None
-    _lib.call("lion_pwconv_split_forward" if use_split else "lion_pwconv_forward",
-              x, wp, bias_c, b, cin, cout, L, None, None, y, None)
+    _lib.call(route.forward, x, wp, _bias(bias), b, cin, cout, L, None, None, y, None)
     return y
 
 
@@ -390,8 +413,7 @@ def pw_grouped_supported(conv, gp):
     b, cin, m, u = gp.shape
     L = m * u
     co = gp.coords
-    return (PW_ALL and conv.in_channels == cin and conv.groups == 1 and all(k == 1 for k in conv.kernel_size)
-            and all(s == 1 for s in conv.stride) and all(p == 0 for p in conv.padding)
+    return (PW_ALL and conv.in_channels == cin and is_plain_1x1(conv)
             and co.is_cuda and co.dtype == torch.float32 and (gp.feat is None or gp.feat.dtype == torch.float32) and L > 0
             and cin * co.shape[2] < (1 << 29)
             and _lib.load().lion_pwconv_stat_tiles(conv.out_channels, cin, L) > 0)
@@ -401,19 +423,15 @@ def pwconv_grouped_fused(gp, conv, want_stats=True):
     """pwconv_fused(gp.materialize(), conv) without the grouped tensor: the kernel gathers its operand through gp.idx
     (lion_pwconv_grouped_forward / lion_pwconv_split_grouped_forward).  Same routing as pwconv_fused takes for this
     (B, Cin, Cout, L), same kernels: y [B,Cout,M,U] and the tile sums are bit-identical."""
-    lib = _lib.load()
     b, cin, m, u = gp.shape
     L = m * u
     cout = conv.out_channels
-    use_split = pw_use_split(None, b, cin, cout, L)
-    wp = _PW_SPLIT_CACHE.get(conv.weight) if use_split else pw_packed_weight(conv.weight)
+    route = pw_route(b, cin, cout, L)
     y = torch.empty((b, cout, m, u), device=gp.coords.device, dtype=torch.float32)
-    tiles = (lib.lion_pwconv_split_stat_tiles if use_split else lib.lion_pwconv_stat_tiles)(cout, cin, L)
-    stats = torch.empty((b, cout, tiles, 2), device=y.device, dtype=torch.float32) if want_stats else None
-    bias = conv.bias.detach().contiguous() if conv.bias is not None else None
-    _lib.call("lion_pwconv_split_grouped_forward" if use_split else "lion_pwconv_grouped_forward",
-              gp.coords.contiguous(), gp.centers.contiguous(), None if gp.feat is None else gp.feat.contiguous(),
-              gp.idx.contiguous(), wp, bias, b, cin - 3, gp.coords.shape[2], m, u, cout, y, stats)
+    stats = _pw_stats(route, b, cin, cout, L, y) if want_stats else None
+    _lib.call(route.grouped, gp.coords.contiguous(), gp.centers.contiguous(), None if gp.feat is None else gp.feat.contiguous(),
+              gp.idx.contiguous(), route.cache.get(conv.weight), _bias(conv.bias), b, cin - 3, gp.coords.shape[2], m, u, cout, y,
+              stats)
     return y, stats
 
 
@@ -425,8 +443,7 @@ def linear_rows(x, weight, bias=None, act=0, slope=0.0):
     o = weight.shape[0]
     wp = pw_packed_weight(weight)
     y = torch.empty((b, o), device=x.device, dtype=torch.float32)
-    bias_c = bias.detach().contiguous() if bias is not None else None
-    _lib.call("lion_linear_forward", x, wp, bias_c, b, k, o, int(act), float(slope), y)
+    _lib.call("lion_linear_forward", x, wp, _bias(bias), b, k, o, int(act), float(slope), y)
     return y
 
 

@@ -234,8 +234,7 @@ def conv1x1(conv, x):
     if train_ops.pwconv_trainable(conv, x):  # training: forward, data / weight / bias gradients on own kernels
         return train_ops.pwconv(conv, x)
     from .. import _fallback
-    if (x.is_cuda and torch.is_grad_enabled() and all(k == 1 for k in conv.kernel_size) and all(s == 1 for s in conv.stride)
-            and all(p == 0 for p in conv.padding) and conv.groups == 1):
+    if x.is_cuda and torch.is_grad_enabled() and fused_ops.is_plain_1x1(conv):
         _fallback.note("pvcnn2_ada.conv1x1 (training matmul)", f"{tuple(conv.weight.shape)} on {tuple(x.shape)}")
         y = torch.matmul(conv.weight.flatten(1), x.flatten(2))
         if conv.bias is not None:
@@ -249,9 +248,7 @@ def route_1x1_convs(module):
     """give every kernel-size-1 Conv1d / Conv2d under `module` the matrix-product forward above (an instance
     attribute: parameters, state_dict keys and module types are untouched)."""
     for m in module.modules():
-        if (isinstance(m, (nn.Conv1d, nn.Conv2d)) and all(k == 1 for k in m.kernel_size) and m.groups == 1
-                and all(s == 1 for s in m.stride) and all(p == 0 for p in m.padding)
-                and "forward" not in m.__dict__):
+        if isinstance(m, (nn.Conv1d, nn.Conv2d)) and fused_ops.is_plain_1x1(m) and "forward" not in m.__dict__:
             m.forward = functools.partial(conv1x1, m)
     return module
 

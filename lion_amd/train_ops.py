@@ -525,8 +525,7 @@ class _PwConv(torch.autograd.Function):
 
 def pwconv_trainable(conv, x) -> bool:
     from . import fused_ops
-    if not (PWCONV and usable(x) and conv.groups == 1 and all(k == 1 for k in conv.kernel_size) and all(s == 1 for s in conv.stride)
-            and all(p == 0 for p in conv.padding)):
+    if not (PWCONV and usable(x) and fused_ops.is_plain_1x1(conv)):
         return False
     lib = _lib.load()
     L = x[0, 0].numel()

@@ -24,3 +24,18 @@ def test_pointwise_split_policy():
         assert not pol(None, 1, 128, 128, 2048)           # B = 1 demo config
     assert pol(True, 1, 128, 128, 16) and not pol(False, 32, 192, 128, 2048)
     assert not pol(True, 2, 4096, 64, 1 << 18)            # Cin * L beyond the 32-bit byte offsets of the kernel
+
+
+def test_pointwise_route_follows_the_policy():
+    """pw_route names the split entry points exactly where pw_use_split says so, and only entry points the library has"""
+    from lion_amd import _lib
+    shapes = [(32, 192, 128, 2048), (32, 320, 256, 512), (32, 256, 128, 128), (32, 35, 32, 32768), (32, 64, 128, 8192),
+              (1, 128, 128, 2048), (1, 128, 128, 16), (2, 4096, 64, 1 << 18)]     # those of test_pointwise_split_policy
+    for shape in shapes:
+        for split in (None, True, False):
+            route = fused_ops.pw_route(*shape, split=split)
+            use = fused_ops.pw_use_split(split, *shape)
+            names = [v for v in route if isinstance(v, str)]
+            assert route.split == use and len(names) == 3, (shape, split)
+            for name in names:
+                assert name in _lib.SIGNATURES and ("_split_" in name) == use, (shape, split, name)
