@@ -6,6 +6,8 @@ builders :416/:448/:520).  Parameter names / shapes are identical, so reference 
 Differences that matter on MI355X (all numerically equivalent to fp32 rounding):
   * every point-voxel operator is a HIP kernel from ``lion_amd.functional``;
   * ``Voxelization.forward`` is two launches (fused normalise + index + mean-pool) instead of ~12;
+  * in inference everything that the coordinates alone decide -- voxel index plan, tile occupancy, r = 32 devoxelisation
+    plan -- lives on one ``VoxelGeometry`` per (cloud, resolution) of the forward in flight (``voxel_plans``);
   * the time embedding that the reference broadcasts to [B,64,N] and concatenates before every
     block is kept as given (shape contract of the callers), nothing is re-laid-out on the host.
 """
@@ -18,6 +20,7 @@ import torch.nn as nn
 from einops import rearrange
 
 from .. import functional as F
+from ..functional import backend   # (backend._backend is looked up at call time: tests replace it and spy on it)
 from ..conv_ops import conv3d_module
 from .. import fused_ops
 
@@ -30,11 +33,11 @@ OVERLAP_POINT_BRANCH = os.environ.get("LION_OVERLAP_POINT_BRANCH", "0") != "0"
 _POINT_STREAMS = {}
 
 
-# Index plans of the voxelisations of one forward pass (inference): every PVConv of a stage voxelises the SAME coordinates
-# at the SAME resolution (reference :235-243), and the feature-propagation stages come back to the set-abstraction stages'
-# clouds -- 4 distinct (cloud, r) pairs for 14 voxelisations in the released denoiser.  While a PVCNN2Unet forward is in
-# flight this holds {(data_ptr, shape, r, normalize, eps): (coords tensor, plan)}; the coordinates tensor is kept alive by
-# the entry, so its address cannot be handed to another tensor while the entry exists.
+# What the coordinates alone decide about the voxel branches of one forward pass (inference): every PVConv of a stage
+# voxelises the SAME coordinates at the SAME resolution (reference :235-243), and the feature-propagation stages come back to
+# the set-abstraction stages' clouds -- 4 distinct (cloud, r) pairs for 14 voxelisations in the released denoiser.  While a
+# PVCNN2Unet forward is in flight this holds {(data_ptr, shape, r, normalize, eps): VoxelGeometry}; the record keeps its
+# coordinates tensor alive, so its address cannot be handed to another tensor while the entry exists.
 _VOX_PLANS = None
 VOX_PLAN = os.environ.get("LION_VOX_PLAN", "1") != "0"   # A/B switch: 0 = every voxelisation recomputes its indices
 OCC_PLAN = os.environ.get("LION_OCC_PLAN", "1") != "0"       # A/B switch: 0 = every PVConv recomputes its tile occupancy
@@ -59,40 +62,53 @@ def voxel_plans():
         _VOX_PLANS = prev
 
 
-def _occupancy(counts, r, cout, b, level=None):
-    """tile occupancy + work lists (fused_ops.conv3d_occupancy) of the count grid of a (cloud, r) pair: the same for every
-    PVConv that voxelises this pair (the sparse tile plan depends on r only), so while a forward's plans are alive it is
-    computed once and every convolution of the pair works from the SAME buffers: a sparse convolution re-arms its work
-    queue when its last workgroup leaves (round 5; until then every use took a copy -- 7 copy launches per step).
-    level: the consumer-aware level of the buffers (0 every voxel written, 1 unread empty tiles skipped, 2 the delta
-    convolution is the split kernel: conv1 stores occupied tiles only); None = 1 if SKIP_UNREAD else 0."""
-    if level is None:
-        level = 1 if SKIP_UNREAD else 0
-    if _VOX_PLANS is None or not OCC_PLAN:
-        return fused_ops.conv3d_occupancy(counts, r, cout, b, consumer_aware=level)
-    key = ("occ", counts.data_ptr(), tuple(counts.shape), int(r), int(b), int(level))
-    hit = _VOX_PLANS.get(key)
-    if hit is None:
-        o1, o2 = fused_ops.conv3d_occupancy(counts, r, cout, b, consumer_aware=level)
-        hit = (counts, (o1, o2))   # counts stays alive with the entry
-        _VOX_PLANS[key] = hit
-    if OCC_CLONE:   # A/B against a library from before round 5, whose convolutions leave the queue counter consumed
-        return hit[1][0].clone(), hit[1][1].clone()
-    return hit[1]
+class VoxelGeometry:
+    """one (cloud, r) pair of a forward pass: the contiguous fp32 [B,3,N] coordinates, the voxel index plan (voxel_index's; None
+    outside a scope and for a shape it does not plan) and, on first use, the tile occupancy per consumer-aware level and the
+    devoxelisation plan.  scoped: made inside voxel_plans() -- only then does anything outlive one PVConv."""
 
+    def __init__(self, coords, r, normalize, eps, plan, scoped):
+        self.coords, self.r, self.normalize, self.eps, self.plan, self.scoped = coords, r, normalize, eps, plan, scoped
+        # voxel coordinates f32 [B,3,N] and point counts int32 [B, r^3]; without a plan the first scatter fills them in
+        self.norm, self.cnt = (plan["norm"], plan["cnt"]) if plan is not None else (None, None)
+        self._occ, self._devox = {}, False
 
-def _devox_plan(voxel_coords, r):
-    """the devoxelisation plan of (voxel coordinates, r) of the forward in flight (kept beside the voxel index plans: the
-    same four (cloud, r) pairs, the r = 32 pair devoxelised four times), or None."""
-    if _VOX_PLANS is None or not DEVOX_PLAN or r != 32 or voxel_coords.shape[2] > 2048 or not voxel_coords.is_contiguous():
-        return None
-    key = ("devox", voxel_coords.data_ptr(), tuple(voxel_coords.shape), int(r))
-    hit = _VOX_PLANS.get(key)
-    if hit is None:
-        plan = fused_ops.devoxelize_plan(voxel_coords, r)
-        hit = (voxel_coords, plan)      # the coordinates tensor stays alive with the entry
-        _VOX_PLANS[key] = hit
-    return hit[1]
+    def scatter(self, features, reader_level=0):
+        """features [B,C,N] -> mean-pooled grid [B,C,r,r,r].  reader_level non-zero (the level of PVConv's fused branch): only the
+        sparse convolution reads the grid -- the scatter leaves the z-rows outside every occupied tile's halo unwritten (round 5)."""
+        b, c = features.shape[:2]
+        if self.plan is None:
+            out, self.norm, _, self.cnt = backend._backend.voxelize_points_forward(
+                features.float().contiguous(), self.coords, self.r, self.normalize, self.eps)
+        else:   # phases B + C only: the voxel ids of this cloud at this resolution exist already; the occupancy comes first
+            aware = reader_level and SKIP_UNREAD and SPARSE_CONV1 and self.r in (16, 32)
+            occ_m1 = self.occupancy(reader_level, 64)[0] if aware else None
+            out = backend._backend.voxel_scatter(features.float().contiguous(), self.plan, occ_m1)
+        return out.view(b, c, self.r, self.r, self.r)
+
+    def occupancy(self, level, cout):
+        """(occ1, occ2): tile occupancy + work lists (fused_ops.conv3d_occupancy) of the pair's count grid: the same for every
+        PVConv that voxelises this pair (the sparse tile plan depends on r only, so `cout` is no part of the memo's key): inside a
+        scope it is computed once per level and every convolution of the pair works from the SAME buffers: a sparse convolution
+        re-arms its work queue when its last workgroup leaves (round 5; until then every use took a copy -- 7 copy launches per
+        step).  level: 0 every voxel written, 1 unread empty tiles skipped, 2 conv1 stores occupied tiles only (split delta conv)."""
+        keep = self.scoped and OCC_PLAN
+        occ = self._occ.get(level) if keep else None
+        if occ is None:
+            occ = fused_ops.conv3d_occupancy(self.cnt, self.r, cout, self.cnt.shape[0], consumer_aware=level)
+            if keep:
+                self._occ[level] = occ
+        if keep and OCC_CLONE:   # A/B against a library from before round 5, whose convolutions leave the queue counter consumed
+            return occ[0].clone(), occ[1].clone()
+        return occ
+
+    def devox_plan(self):
+        """the devoxelisation plan of the voxel coordinates (the r = 32 pair is devoxelised four times), or None."""
+        if not (self.scoped and DEVOX_PLAN) or self.r != 32 or self.norm.shape[2] > 2048 or not self.norm.is_contiguous():
+            return None
+        if self._devox is False:   # not asked yet (None: outside the planned kernel's range)
+            self._devox = fused_ops.devoxelize_plan(self.norm, self.r)
+        return self._devox
 
 
 def _point_stream(device):
@@ -306,8 +322,7 @@ class SharedMLP(nn.Module):
         self.layers = nn.ModuleList(layers)
 
     def _fusable(self, x):
-        return (FUSE_INFERENCE and not self.training and not torch.is_grad_enabled() and x.is_cuda
-                and x.dtype == torch.float32 and not torch.is_autocast_enabled())
+        return own_kernels(x) and not self.training
 
     def _run(self, x, style, reduce_max=False, add=None):
         """reduce_max: additionally take the max over the last dimension (the SA modules' pooling,
@@ -346,38 +361,24 @@ class Voxelization(nn.Module):
         self.normalize = normalize
         self.eps = eps
 
-    def forward(self, features, coords, return_counts=False, sparse_reader=False):
-        """return_counts (inference only): also the per-voxel point counts int32 [B, r^3], from which
-        the first convolution derives its empty tiles.  sparse_reader (PVConv's fused branch): the grid will be read by the
-        sparse convolution only -- the tile occupancy of the (cloud, r) pair is computed first and the scatter leaves the
-        z-rows outside every occupied tile's halo unwritten (round 5)."""
+    def geometry(self, coords):
+        """the VoxelGeometry of these coordinates at this resolution (inference): the record of the forward in flight, made on a
+        miss; outside voxel_plans(), and for a shape voxel_index does not plan, one that lives for this call and keeps nothing."""
+        co = coords.detach()[:, :3].float().contiguous()
+        if _VOX_PLANS is None:
+            return VoxelGeometry(co, self.r, self.normalize, self.eps, None, False)
+        key = (co.data_ptr(), tuple(co.shape), self.r, bool(self.normalize), float(self.eps))
+        geo = _VOX_PLANS.get(key)
+        if geo is None:
+            geo = VoxelGeometry(co, self.r, self.normalize, self.eps, backend._backend.voxel_index(co, self.r, self.normalize, self.eps), True)
+            if geo.plan is not None:
+                _VOX_PLANS[key] = geo
+        return geo
+
+    def forward(self, features, coords):
         coords = coords.detach()
-        if return_counts:
-            from ..functional.backend import _backend
-            b, c = features.shape[:2]
-            co = coords[:, :3].float().contiguous()
-            plan = None
-            if _VOX_PLANS is not None and hasattr(_backend, "voxel_index"):
-                key = (co.data_ptr(), tuple(co.shape), self.r, bool(self.normalize), float(self.eps))
-                hit = _VOX_PLANS.get(key)
-                if hit is None:
-                    plan = _backend.voxel_index(co, self.r, self.normalize, self.eps)
-                    if plan is not None:
-                        _VOX_PLANS[key] = (co, plan)
-                else:
-                    plan = hit[1]
-            if plan is not None:   # phases B + C only: the voxel ids of this cloud at this resolution exist already
-                occ_m1 = None
-                if sparse_reader and SKIP_UNREAD and SPARSE_CONV1 and self.r in (16, 32) and hasattr(_backend, "voxel_scatter"):
-                    occ_m1 = _occupancy(plan["cnt"], self.r, 64, b, int(sparse_reader))[0]
-                out = _backend.voxel_scatter(features.float().contiguous(), plan, occ_m1)
-                return out.view(b, c, self.r, self.r, self.r), plan["norm"], plan["cnt"]
-            out, norm_coords, _, counts = _backend.voxelize_points_forward(
-                features.float().contiguous(), co, self.r, self.normalize, self.eps)
-            return out.view(b, c, self.r, self.r, self.r), norm_coords, counts
         if features is None:
-            from ..functional.backend import _backend
-            _, norm_coords, _, _ = _backend.voxelize_points_forward(
+            _, norm_coords, _, _ = backend._backend.voxelize_points_forward(
                 None, coords[:, :3].float().contiguous(), self.r, self.normalize, self.eps)
             return features, norm_coords
         return F.voxelize_points(features, coords, self.r, self.normalize, self.eps)
@@ -425,17 +426,17 @@ class PVConv(nn.Module):
         conv2 = self.voxel_layers[4]
         return 2 if (SKIP_UNREAD_LEVEL2 and conv_ops.use_split(None, conv2.in_channels, conv2.out_channels, self.resolution)) else 1
 
-    def _fused_voxel_branch(self, grid, voxel_coords, style, counts=None):
+    def _fused_voxel_branch(self, grid, geo, style, level):
         """eval-mode voxel branch with every pointwise stage folded into the convolutions / the
         devoxelisation (lion_amd/fused_ops.py): conv1 (+GN sums) -> fold -> conv2 with the
         swish(AdaGN1(.)) prologue (+GN sums) -> fold, SE gate from the channel means ->
-        devoxelize(scale*grid + shift).  Dropout is the identity in eval mode."""
+        devoxelize(scale*grid + shift).  Dropout is the identity in eval mode.  geo scattered `grid`; level = _aware_level()."""
         conv1, gn1, conv2, gn2 = self.voxel_layers[0], self.voxel_layers[1], self.voxel_layers[4], self.voxel_layers[5]
         se = self.voxel_layers[6] if len(self.voxel_layers) > 6 else None
         r = self.resolution
         occ1 = occ2 = None
-        if SPARSE_CONV1 and counts is not None and r >= 16:
-            occ1, occ2 = _occupancy(counts, r, conv1.out_channels, grid.shape[0], self._aware_level())
+        if SPARSE_CONV1 and r >= 16:
+            occ1, occ2 = geo.occupancy(level, conv1.out_channels)
         f1, g1 = gn1.affine(style)
         y1, (a1, b1) = fused_ops.conv3d_fused(grid, conv1, None, True, occ1,   # skips all-zero tiles
                                               fold=fused_ops.FoldSpec(gn1.norm, f1, g1, r ** 3))
@@ -443,7 +444,7 @@ class PVConv(nn.Module):
         f2, g2 = gn2.affine(style)
         y2, (a2, b2) = fused_ops.conv3d_fused(y1, conv2, (a1, b1), True, occ2, prev_conv=conv1,
                                               fold=fused_ops.FoldSpec(gn2.norm, f2, g2, r ** 3, se))
-        return fused_ops.devoxelize_affine(y2, voxel_coords, r, a2, b2, plan=_devox_plan(voxel_coords, r))
+        return fused_ops.devoxelize_affine(y2, geo.norm, r, a2, b2, plan=geo.devox_plan())
 
     def forward(self, inputs):
         features, coords_input, time_emb, style = inputs
@@ -451,17 +452,16 @@ class PVConv(nn.Module):
         assert features.shape[0] == coords.shape[0] and features.shape[2] == coords.shape[2], \
             f'get feat: {features.shape} and {coords.shape}'
         assert coords.shape[1] == 3, f'expect coords: B,3,Npoint, get: {coords.shape}'
-        counts = None
-        if (FUSE_INFERENCE and not self.training and not torch.is_grad_enabled() and features.is_cuda
-                and not torch.is_autocast_enabled()):
-            # the fused voxel branch below is the grid's only reader, and its first convolution runs sparse
-            will_fuse = fused_ops.fusable(self.voxel_layers[0], self.voxel_layers[4], self.resolution, features.float())
-            grid, voxel_coords, counts = self.voxelization(features, coords, return_counts=True,
-                                                           sparse_reader=self._aware_level() if will_fuse else 0)
+        infer = (FUSE_INFERENCE and not self.training and not torch.is_grad_enabled() and features.is_cuda
+                 and not torch.is_autocast_enabled())
+        will_fuse = infer and fused_ops.fusable(self.voxel_layers[0], self.voxel_layers[4], self.resolution, features.float())
+        if infer:
+            level = self._aware_level() if will_fuse else 0   # the fused branch is the grid's only reader, its conv1 runs sparse
+            geo = self.voxelization.geometry(coords)
+            grid, voxel_coords = geo.scatter(features, level), geo.norm
         else:
             grid, voxel_coords = self.voxelization(features, coords)
-        if (FUSE_INFERENCE and not self.training and not torch.is_grad_enabled()
-                and fused_ops.fusable(self.voxel_layers[0], self.voxel_layers[4], self.resolution, grid)):
+        if will_fuse:
             pf = None
             if self.add_point_feat and OVERLAP_POINT_BRANCH:
                 # the point branch (1x1 conv + AdaGN + Swish: a handful of short, latency-bound launches) does not
@@ -471,7 +471,7 @@ class PVConv(nn.Module):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     pf = self.point_features(features, style)
-            fused = self._fused_voxel_branch(grid, voxel_coords, style, counts)
+            fused = self._fused_voxel_branch(grid, geo, style, level)
             if pf is not None:
                 main.wait_stream(side)
                 pf.record_stream(main)
