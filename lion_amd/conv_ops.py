@@ -1,4 +1,5 @@
 """Conv3d (3x3x3, pad 1) on the fp32 matrix cores: lion_conv3d_k3_forward over the C ABI."""
+import collections
 import contextlib
 import os
 
@@ -20,7 +21,7 @@ def supported(cin, cout, r):
 
 def split_supported(cin, cout, r):
     """what csrc/conv3d_split.hip can run"""
-    return r in (8, 16, 32) and cout % 32 == 0 and cin >= 16 and cin % 16 == 0
+    return supported(cin, cout, r) and cin % 16 == 0
 
 
 def split_preferred(cin, cout, r):
@@ -72,7 +73,7 @@ def requested_precision(value):
 
 def half_supported(cin, cout, r):
     """what csrc/conv3d_half.hip can run: the split kernel's shapes at r = 16 / 32 (r = 8 stays on the three-product kernel)"""
-    return r in (16, 32) and cout % 32 == 0 and cin >= 16 and cin % 16 == 0
+    return split_supported(cin, cout, r) and r >= 16
 
 
 def use_half(cin, cout, r, x=None):
@@ -118,37 +119,49 @@ def packed_weight(weight):
     return _PACK_CACHE.get(weight)
 
 
+ConvRoute = collections.namedtuple("ConvRoute", "kind forward stat_tiles packed")
+_CONV_ROUTES = {
+    "f32": ConvRoute("f32", "lion_conv3d_k3_fused_forward", "lion_conv3d_stat_tiles", packed_weight),
+    "split": ConvRoute("split", "lion_conv3d_k3_split_forward", "lion_conv3d_split_stat_tiles", split_packed_weight),
+    "half": ConvRoute("half", "lion_conv3d_k3_half_forward", "lion_conv3d_split_stat_tiles", split_packed_weight)}
+
+
+def conv_route(cin, cout, r, split=None, x=None, half=None):
+    """the kernel a voxel convolution of this shape runs on (split as use_split; half: None = use_half decides, False =
+    never; x: the input, for use_half's inference-only rule): its .kind ("f32", "split" or "half"), the entry point
+    .forward, the tile-count query .stat_tiles of its statistics and the getter .packed of its packed weights."""
+    if not use_split(split, cin, cout, r):
+        return _CONV_ROUTES["f32"]
+    return _CONV_ROUTES["half" if half is None and use_half(cin, cout, r, x) else "split"]
+
+
+def pad_cin4(x):
+    """x [B,Cin,r,r,r] with Cin zero-padded to a multiple of 4 (what the fp32 kernel stages), contiguous"""
+    pad = -x.shape[1] % 4
+    if pad:
+        x = torch.cat([x, x.new_zeros(x.shape[0], pad, *x.shape[2:])], dim=1)
+    return x.contiguous()
+
+
 def conv3d_k3(x, weight, bias=None, split=None, packed=None, occ=None, half=None):
     """x [B,Cin,r,r,r] fp32 -> [B,Cout,r,r,r]; Cin is zero-padded to a multiple of 4 if needed.
     split: None = the module default (SPLIT), False = the exact-fp32 MFMA kernel, True = split operands if supported.
     packed: callable(kind) -> the packed copy of `weight` for kind in ("split", "f32"), for callers whose `weight` is a
     derived temporary and who cache its packed forms under the ORIGINAL parameter (the data-gradient path).
-    occ: the tile occupancy of a freshly voxelised `x` (fused_ops.conv3d_occupancy(counts)[0]): tiles without a point within
+    occ: the tile occupancy of a freshly voxelised `x` (train_occupancy(counts, ...)): tiles without a point within
     one voxel skip their K loop (output = bias exactly); split kernel only, ignored otherwise.
     half: None = the precision policy (use_half) decides between the split kernel and the single-product one, False = never
     (the training ops)."""
     _lib.require_cuda(x)
     b, cin, r = x.shape[0], x.shape[1], x.shape[2]
     cout = weight.shape[0]
-    if use_split(split, cin, cout, r) and weight.shape[1] == cin:
-        x = x.contiguous()
-        y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
-        bias_c = bias.detach().contiguous() if bias is not None else None
-        wp = packed("split") if packed is not None else split_packed_weight(weight)
-        entry = "lion_conv3d_k3_half_forward" if (half is None and use_half(cin, cout, r, x)) else "lion_conv3d_k3_split_forward"
-        _lib.call(entry, x, wp, bias_c, b, cin, cout, r, None, None, None, None, y, None, occ if r >= 16 else None)
-        return y
-    if cin % 4:
-        pad = 4 - cin % 4
-        x = torch.cat([x, x.new_zeros(b, pad, r, r, r)], dim=1)
-        cin_p = cin + pad
-    else:
-        cin_p = cin
-    x = x.contiguous()
-    wp = packed("f32") if packed is not None else packed_weight(weight)
+    route = conv_route(cin, cout, r, split if weight.shape[1] == cin else False, x, half)
+    x = pad_cin4(x)   # (a split shape has Cin % 16 == 0: untouched)
+    wp = packed("f32" if route.kind == "f32" else "split") if packed is not None else route.packed(weight)
     y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
     bias_c = bias.detach().contiguous() if bias is not None else None
-    _lib.call("lion_conv3d_k3_forward", x, wp, bias_c, b, cin_p, cout, r, y)
+    occ = occ if route.kind != "f32" and r >= 16 else None
+    _lib.call(route.forward, x, wp, bias_c, b, x.shape[1], cout, r, None, None, None, None, y, None, occ)
     return y
 
 
@@ -178,18 +191,23 @@ _DGRAD_SPLIT_CACHE = WeightCache(lambda w: _split_pack(dgrad_weight(w)))
 _DGRAD_PACK_CACHE = WeightCache(lambda w: _pack(dgrad_weight(w)))
 
 
+def train_occupancy(counts, x, cout):
+    """counts (int32 [B, r^3] | None: the point counts of the voxelised grid that x is, or is the gradient of) -> the tile
+    occupancy a training convolution of x to cout channels skips its empty tiles by, or None where it runs dense"""
+    b, cin, r = x.shape[0], x.shape[1], x.shape[2]
+    if counts is None or not (TRAIN_SPARSE and r in (16, 32) and use_split(None, cin, cout, r)):
+        return None
+    from . import fused_ops
+    return fused_ops.conv3d_occupancy(counts, r, cout, b)[0]
+
+
 def conv3d_k3_dgrad(gy, weight, counts=None):
     """grad_x (with Cin padded to a multiple of 32, callers slice) = conv3d_k3(gy, mirror(weight)); every derived tensor
     is cached under `weight` (storage, version, generation) and replaced in place when the parameter changes.
     counts: the point counts of the voxelised grid x was (int32 [B, r^3]): its gradient is read by the voxelisation's backward
     at voxels that hold a point only, so tiles without a point within one voxel are not computed (they hold zeros)."""
     wt = dgrad_weight(weight)
-    occ = None
-    r = gy.shape[2]
-    if counts is not None and TRAIN_SPARSE and r in (16, 32) and use_split(None, gy.shape[1], wt.shape[0], r):
-        from . import fused_ops
-        occ = fused_ops.conv3d_occupancy(counts, r, wt.shape[0], gy.shape[0])[0]
-    return conv3d_k3(gy, wt, None, occ=occ, half=False,
+    return conv3d_k3(gy, wt, None, occ=train_occupancy(counts, gy, wt.shape[0]), half=False,
                      packed=lambda kind: (_DGRAD_SPLIT_CACHE if kind == "split" else _DGRAD_PACK_CACHE).get(weight))
 
 
@@ -234,12 +252,7 @@ class _Conv3dK3(torch.autograd.Function):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.counts = counts      # (not a differentiable input; kept for the data gradient's empty tiles)
-        occ = None
-        r, cout = x.shape[2], weight.shape[0]
-        if counts is not None and TRAIN_SPARSE and r in (16, 32) and use_split(None, x.shape[1], cout, r):
-            from . import fused_ops
-            occ = fused_ops.conv3d_occupancy(counts, r, cout, x.shape[0])[0]
-        return conv3d_k3(x, weight, bias, occ=occ, half=False)
+        return conv3d_k3(x, weight, bias, occ=train_occupancy(counts, x, weight.shape[0]), half=False)
 
     @staticmethod
     def backward(ctx, gy):

@@ -15,7 +15,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vec
 # An object is rebuilt when the hash of (compiler, flags, its source, the shared headers) differs from the one recorded
 # beside it (FILE.o.key) -- content, not mtime: a flag change, a checkout of an older file or a fresh clone with stale
 # objects all rebuild; LION_REBUILD=1 forces everything.
-HDRS="common.h split_ops.h conv3d_split_kernel.h ../../include/lion_hip.h"
+HDRS="common.h split_ops.h conv3d_tiles.h conv3d_split_kernel.h ../../include/lion_hip.h"
 VER="$($HIPCC --version 2>/dev/null | head -3)"
 OBJS=()
 PIDS=()

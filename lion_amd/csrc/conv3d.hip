@@ -19,7 +19,7 @@
 // and the weight slice [KC][27][COT] (pre-packed once per weight tensor into [Cin][27][Cout]) are
 // staged in 41 KiB of LDS; the next chunk's global loads are in flight while the current chunk's
 // 54 k-steps (216 MFMAs per wave) execute.  Each k-step is 4 conflict-free ds_read_b32 + 4 MFMAs.
-#include "common.h"
+#include "conv3d_tiles.h"
 
 namespace {
 
@@ -548,18 +548,15 @@ __global__ void conv3d_pack_kernel(const float *__restrict__ w, int Cout, int Ci
   wp[i] = ci < Cin ? w[((size_t)co * Cin + ci) * 27 + t] : 0.f;
 }
 
-template <int TD, int TH, int TW, int COT, int VB> struct ConvTile {}; // spatial tile, output channels, voxel blocks per wave
-template <int TD, int TH, int TW, int COT, int VB>
-static int launch_conv_t(ConvTile<TD, TH, TW, COT, VB>, const float *x, const float *wp, const float *bias, float *y, int B,
-                         int Cin, int Cout, int r, const float *pa, const float *pb, const float *pbias, const float *tconst,
-                         float *stats, int32_t *occ, hipStream_t st) {
-  const int tiles = (r / TD) * (r / TH) * (r / TW);
-  int n_cu = 0;
-  if (int e = lion_cu_count(&n_cu)) return e;
-  const long items = (long)B * tiles * (Cout / COT);
-  const dim3 grid = occ ? dim3((unsigned)(items < 2L * n_cu ? items : 2L * n_cu)) : dim3(B, tiles, Cout / COT);
-  constexpr int NT = 256;
-  constexpr int HALO = (TD + 2) * (TH + 2) * (TW + 2);
+template <int COT, int TD, int TH, int TW> // output channels per workgroup; the spatial tile as conv_tile_dispatch hands it over
+static int launch_conv(IntC<TD>, IntC<TH>, IntC<TW>, const float *x, const float *wp, const float *bias, float *y, int B,
+                       int Cin, int Cout, int r, const float *pa, const float *pb, const float *pbias, const float *tconst,
+                       float *stats, int32_t *occ, hipStream_t st) {
+  constexpr int VB = TD * TH * TW / 128; // voxel blocks per wave
+  const int tiles = conv_tile_count(r, VB);
+  dim3 grid;
+  if (int e = conv_grid(occ != nullptr, B, tiles, Cout / COT, 2, &grid)) return e;
+  constexpr int NT = 256, HALO = (TD + 2) * (TH + 2) * (TW + 2);
   constexpr int SWS = ((KC * 27 * COT + 255) / 256) * 256 + 256;
   static_assert(KC * HALO >= 27 * COT, "the response table must fit the input tile buffer");
   const size_t LDS = (size_t)(((KC * HALO + 3) & ~3) + 2 * SWS + COT + (pa ? 3 * ((Cin + 63) & ~63) : 0) +
@@ -570,7 +567,7 @@ static int launch_conv_t(ConvTile<TD, TH, TW, COT, VB>, const float *x, const fl
   });
 }
 
-// Tile choice per (r, Cout): spatial tile = 4 waves x VB x 32 voxels, COT output channels per workgroup.
+// Tile choice per (r, Cout): spatial tile = 4 waves x VB x 32 voxels (conv3d_tiles.h), COT output channels per workgroup.
 //   Cout % 64 == 0, >= 512 workgroups : VB 4 x COT 64  (4x2 MFMA tiles per wave: 6 LDS reads per 8 MFMAs, 2.4x halo
 //                                                        instead of 3.2x -> less staging / prologue per MFMA)
 //   Cout % 64 == 0 otherwise          : VB 2 x COT 64  (2x2 tiles, 4 LDS reads per 4 MFMAs)
@@ -580,56 +577,19 @@ static int launch_conv_t(ConvTile<TD, TH, TW, COT, VB>, const float *x, const fl
 struct ConvPlan { int vb, cot, tiles; };
 // sparse (work-queue) launches take the smaller 2x2 tiles: more of them are empty, the tail is finer grained, and the
 // occupied ones spread over all CUs even when they are fewer than the resident workgroups.
-static ConvPlan conv_plan(int r, int Cout, int B, bool sparse) {
-  const int r3 = r * r * r;
-  if (!sparse && Cout % 64 == 0 && r >= 16 && (long)(r3 / 512) * (Cout / 64) * B >= 512) return {4, 64, r3 / 512};
-  if (Cout % 64 == 0 && (long)(r3 / 256) * (Cout / 64) * B >= 512) return {2, 64, r3 / 256};
-  if (Cout % 32 == 0 && r >= 16 && !sparse) return {4, 32, r3 / 512};
-  if (Cout % 32 == 0 && r >= 16) return {2, 32, r3 / 256};
-  if (Cout % 32 == 0) return {1, 32, r3 / 128};
+constexpr ConvPlan conv_plan(int r, int Cout, int B, bool sparse) {
+  const int t4 = conv_tile_count(r, 4), t2 = conv_tile_count(r, 2);
+  if (!sparse && Cout % 64 == 0 && r >= 16 && (long)t4 * (Cout / 64) * B >= 512) return {4, 64, t4};
+  if (Cout % 64 == 0 && (long)t2 * (Cout / 64) * B >= 512) return {2, 64, t2};
+  if (Cout % 32 == 0 && r >= 16) return sparse ? ConvPlan{2, 32, t2} : ConvPlan{4, 32, t4};
+  if (Cout % 32 == 0) return {1, 32, conv_tile_count(r, 1)};
   return {0, 0, 0};
 }
-
-static void conv_tile_dims(int r, int vb, int *td, int *th, int *tw) {
-  *tw = r;
-  if (r == 32) { *td = vb == 2 ? 2 : 4; *th = 4; }
-  else if (r == 16) { *td = vb == 2 ? 4 : 8; *th = 4; }
-  else { *td = vb == 2 ? 4 : 2; *th = 8; }
-}
-
-static int launch_conv(const float *x, const float *wp, const float *bias, float *y, int B, int Cin, int Cout,
-                       int r, const float *pa, const float *pb, const float *pbias, const float *tconst, float *stats,
-                       int32_t *occ, hipStream_t st) {
-  const ConvPlan p = conv_plan(r, Cout, B, occ != nullptr);
-  auto go = [&](auto tile) {
-    return launch_conv_t(tile, x, wp, bias, y, B, Cin, Cout, r, pa, pb, pbias, tconst, stats, occ, st);
-  };
-  const int vb = p.vb, cot = p.cot; // -> ConvTile<TD, TH, TW, COT, VB>
-  if (r == 32 && vb == 2 && cot == 64) return go(ConvTile<2, 4, 32, 64, 2>{});
-  if (r == 32 && vb == 4 && cot == 64) return go(ConvTile<4, 4, 32, 64, 4>{});
-  if (r == 16 && vb == 4 && cot == 64) return go(ConvTile<8, 4, 16, 64, 4>{});
-  if (r == 32 && vb == 4 && cot == 32) return go(ConvTile<4, 4, 32, 32, 4>{});
-  if (r == 32 && vb == 2 && cot == 32) return go(ConvTile<2, 4, 32, 32, 2>{});
-  if (r == 16 && vb == 2 && cot == 32) return go(ConvTile<4, 4, 16, 32, 2>{});
-  if (r == 16 && vb == 2 && cot == 64) return go(ConvTile<4, 4, 16, 64, 2>{});
-  if (r == 16 && vb == 4 && cot == 32) return go(ConvTile<8, 4, 16, 32, 4>{});
-  if (r == 8 && vb == 2 && cot == 64) return go(ConvTile<4, 8, 8, 64, 2>{});
-  if (r == 8 && vb == 1 && cot == 32) return go(ConvTile<2, 8, 8, 32, 1>{});
-  return LION_EUNSUPPORTED;
-}
+// Every sparse plan is the 256-voxel tile (vb = 2): the geometry the occupancy flags and their other readers are laid out in.
+constexpr bool sparse256(int r, int B) { return conv_plan(r, 32, B, true).vb == 2 && conv_plan(r, 64, B, true).vb == 2; }
+static_assert(sparse256(16, 1) && sparse256(16, 32) && sparse256(32, 1) && sparse256(32, 32), "a sparse plan left conv_tile256");
 
 } // namespace
-
-// see common.h: the sparse plans of every channel class share one spatial tile per resolution (vb = 2); a plan change that
-// breaks that must be met here, not by silently stale flags in another file
-int lion_internal_sparse_tile_dims(int r, int *td, int *th) {
-  if (r != 16 && r != 32) return LION_EUNSUPPORTED;
-  const ConvPlan a = conv_plan(r, 64, 32, true), b = conv_plan(r, 32, 32, true), c = conv_plan(r, 64, 1, true);
-  if (!a.vb || a.vb != b.vb || a.vb != c.vb) return LION_EUNSUPPORTED;
-  int tw;
-  conv_tile_dims(r, a.vb, td, th, &tw);
-  return 0;
-}
 
 extern "C" {
 
@@ -655,14 +615,20 @@ int lion_conv3d_pack_weights(const float *w, int Cout, int Cin, float *wp, lionS
 int lion_conv3d_k3_fused_forward(const float *x, const float *wp, const float *bias, int B, int Cin,
                                  int Cout, int r, const float *pro_a, const float *pro_b, const float *pro_bias,
                                  const float *tconst, float *y, float *stats, int32_t *occ, lionStream_t stream) {
-  if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0) return LION_EINVAL;
-  if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
-  if (tconst && !pro_a) return LION_EINVAL;
-  if (occ && pro_a && !tconst) return LION_EINVAL; // an activated input is sparse only as constant + delta
-  if (Cin % KC != 0 || (pro_a && Cin > 256)) return LION_EUNSUPPORTED;
+  if (int e = conv_forward_args(x, wp, y, B, Cin, Cout, pro_a, pro_b, tconst, occ)) return e;
+  if (Cin % KC != 0 || (pro_a && Cin > 256) || (r != 8 && r != 16 && r != 32)) return LION_EUNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (r != 8 && r != 16 && r != 32) return LION_EUNSUPPORTED;
-  return launch_conv(x, wp, bias, y, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, stats, occ, st);
+  const ConvPlan p = conv_plan(r, Cout, B, occ != nullptr);
+  return conv_tile_dispatch(r, p.vb, [&](auto TD, auto TH, auto TW) {
+    auto go = [&](auto COT) {
+      return launch_conv<decltype(COT)::value>(TD, TH, TW, x, wp, bias, y, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst,
+                                               stats, occ, st);
+    };
+    // r = 8 has one channel tile per vb (2 x 64, 1 x 32): the other two kernels are not built
+    constexpr int vb = decltype(TD)::value * decltype(TH)::value * decltype(TW)::value / 128;
+    if constexpr (decltype(TW)::value == 8) return p.cot == 32 * vb ? go(IntC<32 * vb>{}) : (int)LION_EUNSUPPORTED;
+    else return p.cot == 64 ? go(IntC<64>{}) : go(IntC<32>{});
+  });
 }
 
 int lion_conv3d_k3_forward(const float *x, const float *wp, const float *bias, int B, int Cin,
@@ -710,10 +676,9 @@ int lion_conv3d_tile_occupancy_aware(const int32_t *cnt, int B, int r, int Cout,
   if (r != 16 && r != 32) return LION_EUNSUPPORTED;
   const ConvPlan p = conv_plan(r, Cout, B, true);
   if (!p.vb || p.tiles > 256 || (((uintptr_t)cnt) & 15) != 0) return LION_EUNSUPPORTED;
-  int td, th, tw;
-  conv_tile_dims(r, p.vb, &td, &th, &tw);
+  const ConvTileDims t = conv_tile_dims(r, p.vb);
   // the reader map of the first buffer is derived from the second margin's flags: both are computed in any case
-  return lion_launch<conv_tile_occ_kernel>(B, 1024, 0, static_cast<hipStream_t>(stream), cnt, r, td, th, occ_m1, occ_m2,
+  return lion_launch<conv_tile_occ_kernel>(B, 1024, 0, static_cast<hipStream_t>(stream), cnt, r, t.td, t.th, occ_m1, occ_m2,
                                            consumer_aware == 2 ? 2 : consumer_aware ? 1 : 0);
 }
 

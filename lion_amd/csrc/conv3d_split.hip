@@ -348,7 +348,7 @@ int lion_conv3d_split_stat_tiles(int r, int Cout) {
   // r = 8: the pipelined half-sample kernel (conv3d_split_pipe_kernel): 2 tiles of 256 voxels, 32 channels per workgroup
   // (history: 128-voxel tiles 144 us, whole-sample tiles x 32 channels on B * Cout/32 = 128 workgroups 104-108 us at
   // 128->128, B=32, against 114 us of the fp32 kernel); r = 16 / 32: the 256-voxel tiles of split_tile_forward
-  return r == 8 ? 2 : r * r * r / 256;
+  return r == 8 ? 2 : conv_tile256_count(r);
 }
 
 // Arguments exactly as lion_conv3d_k3_fused_forward (include/lion_hip.h), wp from lion_conv3d_split_pack_weights;

@@ -7,6 +7,7 @@
 // epilogue term.  Each translation unit instantiates its own P only.  tests/test_isa_cpu.py and
 // tests/test_conv_half_isa_cpu.py pin the compiled code of either.
 #pragma once
+#include "conv3d_tiles.h"
 #include "split_ops.h"
 
 namespace {
@@ -534,19 +535,15 @@ __global__ __launch_bounds__(256, OCC) void conv3d_split_kernel(const float *__r
   // @phase-flush
 }
 
-template <int TD, int TH, int TW, int CB, int VB, int OCC, int P>
-static int launch_split_t(const float *x, const u4 *wp, const float *wtail, const float *bias, float *y, int B, int Cin,
-                          int Cout, int r,
-                          const float *pa, const float *pb, const float *pbias, const float *tconst, float *stats,
-                          int32_t *occ, hipStream_t st) {
-  constexpr int COT = 32 * CB;
+template <int CB, int OCC, int P, int TD, int TH, int TW> // the spatial tile as conv_tile256_dispatch hands it over
+static int launch_split_t(IntC<TD>, IntC<TH>, IntC<TW>, const float *x, const u4 *wp, const float *wtail, const float *bias,
+                          float *y, int B, int Cin, int Cout, int r, const float *pa, const float *pb, const float *pbias,
+                          const float *tconst, float *stats, int32_t *occ, hipStream_t st) {
+  constexpr int COT = 32 * CB, VB = TD * TH * TW / 128;
   constexpr int HALO = (TD + 2) * (TH + 2) * (TW + 2), HP = (HALO + 63) / 64 * 64;
-  const int tiles = (r / TD) * (r / TH) * (r / TW);
-  int n_cu = 0;
-  if (int e = lion_cu_count(&n_cu)) return e;
-  const long items = (long)B * tiles * (Cout / COT);
-  const long resident = (long)OCC * n_cu;
-  const dim3 grid = occ ? dim3((unsigned)(items < resident ? items : resident)) : dim3(B, tiles, Cout / COT);
+  const int tiles = conv_tile_count(r, VB);
+  dim3 grid;
+  if (int e = conv_grid(occ != nullptr, B, tiles, Cout / COT, OCC, &grid)) return e;
   // (PRO = false, STATS = true) of the 64-channel tile gets 556-568 bytes of scratch from the register allocator where
   // (true, true) gets 304-360: launches with statistics and without a prologue run on the PRO instantiation with the
   // prologue switched off at run time (pro_a == nullptr).  P = 2 only: that is the kernel it was measured on.
@@ -570,22 +567,20 @@ template <int P>
 static int split_tile_forward(const float *x, const uint16_t *wp, const float *bias, int B, int Cin, int Cout, int r,
                               const float *pro_a, const float *pro_b, const float *pro_bias, const float *tconst, float *y,
                               float *stats, int32_t *occ, hipStream_t st) {
-  if (!x || !wp || !y || B <= 0 || Cin <= 0 || Cout <= 0) return LION_EINVAL;
-  if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
-  if (tconst && !pro_a) return LION_EINVAL;
-  if (occ && pro_a && !tconst) return LION_EINVAL;
+  if (int e = conv_forward_args(x, wp, y, B, Cin, Cout, pro_a, pro_b, tconst, occ)) return e;
   if ((r != 16 && r != 32) || Cin % KS != 0 || Cout % 32 != 0) return LION_SPLIT_NO_TILE;
   if (pro_a && Cin > 256) return LION_EUNSUPPORTED;
   const u4 *w4 = reinterpret_cast<const u4 *>(wp);
   const float *wtail = reinterpret_cast<const float *>(wp + split_piece_halfs(Cout, Cin));
-  // always the 4 waves x 2 column blocks (VB = 2) geometry of the fp32 kernel's sparse plan, so that the occupancy lists of
-  // lion_conv3d_tile_occupancy apply unchanged: tile (TD, 4, r), 32 * CB channels, two workgroups per CU
-  auto go = [&](auto TD, auto TW, auto CB) {
-    return launch_split_t<decltype(TD)::value, 4, decltype(TW)::value, decltype(CB)::value, 2, 2, P>(
-        x, w4, wtail, bias, y, B, Cin, Cout, r, pro_a, pro_b, pro_bias, tconst, stats, occ, st);
-  };
-  if (r == 32) return Cout % 64 == 0 ? go(IntC<2>{}, IntC<32>{}, IntC<2>{}) : go(IntC<2>{}, IntC<32>{}, IntC<1>{});
-  return Cout % 64 == 0 ? go(IntC<4>{}, IntC<16>{}, IntC<2>{}) : go(IntC<4>{}, IntC<16>{}, IntC<1>{});
+  // always the 256-voxel tile of the fp32 kernel's sparse plan, so that the occupancy lists of lion_conv3d_tile_occupancy
+  // apply unchanged; 32 * CB channels, two workgroups per CU
+  return conv_tile256_dispatch(r, [&](auto TD, auto TH, auto TW) {
+    if constexpr (decltype(TW)::value == 8) return (int)LION_SPLIT_NO_TILE; // (refused above: no tile kernel at r = 8)
+    else return lion_with_flags(Cout % 64 == 0, [&](auto WIDE) {
+      return launch_split_t<decltype(WIDE)::value ? 2 : 1, 2, P>(TD, TH, TW, x, w4, wtail, bias, y, B, Cin, Cout, r, pro_a,
+                                                                 pro_b, pro_bias, tconst, stats, occ, st);
+    });
+  });
 }
 
 } // namespace

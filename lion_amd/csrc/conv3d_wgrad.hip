@@ -12,6 +12,7 @@
 // waves split each 256-voxel tile (combined through LDS in fixed order at the end), so there are B * splits partial
 // results per (co, ci) tile, summed in a fixed order by a second kernel (deterministic, no atomics).  The next tile's
 // loads travel through registers under the current tile's MFMAs.  Exact fp32 products, like the forward.
+#include "conv3d_tiles.h"
 #include "split_ops.h"
 
 namespace {
@@ -459,18 +460,18 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_reduce_kernel(const float *_
   gw[i] = (float)s;
 }
 
-template <int TD, int TH, int TW, int CIT>
-static int launch_wgrad(const float *x, const float *gy, int B, int Cin, int Cout, int r, int TS, float *partial,
-                        hipStream_t st) {
+template <int CIT, int TD, int TH, int TW> // the tile as conv_tile256_dispatch hands it over
+static int launch_wgrad(IntC<TD>, IntC<TH>, IntC<TW>, const float *x, const float *gy, int B, int Cin, int Cout, int r,
+                        int TS, float *partial, hipStream_t st) {
   constexpr int HALO = (TD + 2) * (TH + 2) * (TW + 2);
   const size_t lds = (size_t)(32 * 257 + CIT * HALO) * 4;
   return lion_launch<conv3d_wgrad_kernel<TD, TH, TW, CIT>>(dim3(B * TS, Cin / CIT, Cout / 32), 256, lds, st, x, gy, Cin,
                                                            Cout, r, TS, partial);
 }
 
-template <int TD, int TH, int TW, int CIT>
-static int launch_wgrad_split(const float *x, const float *gy, int B, int Cin, int Cout, int r, int TS,
-                              const unsigned char *skip, float *partial, hipStream_t st) {
+template <int CIT, int TD, int TH, int TW>
+static int launch_wgrad_split(IntC<TD>, IntC<TH>, IntC<TW>, const float *x, const float *gy, int B, int Cin, int Cout, int r,
+                              int TS, const unsigned char *skip, float *partial, hipStream_t st) {
   constexpr int HALO = (TD + 2) * (TH + 2) * (TW + 2);
   size_t lds = (size_t)(32 * WG_GS + CIT * HALO) * 4;
   if (lds < (size_t)4 * 16 * 64 * 4) lds = (size_t)4 * 16 * 64 * 4; // the epilogue's [4][16][64] reduction buffer
@@ -488,9 +489,8 @@ extern "C" {
 static int wgrad_splits(int B, int Cin, int Cout, int r) {
   const int cit = Cin % 8 == 0 ? 8 : 4;
   const long wg = (long)B * (Cin / cit) * (Cout / 32);
-  const int ntiles = r * r * r / 256;
   int ts = 1;
-  while (ts < ntiles && ts < 8 && wg * ts < 512) ts *= 2;
+  while (ts < conv_tile256_count(r) && ts < 8 && wg * ts < 512) ts *= 2;
   return ts;
 }
 
@@ -508,11 +508,10 @@ int lion_conv3d_k3_wgrad(const float *x, const float *gy, int B, int Cin, int Co
   if (!ws || ws_floats < lion_conv3d_wgrad_workspace_floats(B, Cin, Cout, r)) return LION_EWORKSPACE;
   const int TS = wgrad_splits(B, Cin, Cout, r);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool c8 = Cin % 8 == 0;
-  int rc;
-  if (r == 32) rc = c8 ? launch_wgrad<2, 4, 32, 8>(x, gy, B, Cin, Cout, r, TS, ws, st) : launch_wgrad<2, 4, 32, 4>(x, gy, B, Cin, Cout, r, TS, ws, st);
-  else if (r == 16) rc = c8 ? launch_wgrad<4, 4, 16, 8>(x, gy, B, Cin, Cout, r, TS, ws, st) : launch_wgrad<4, 4, 16, 4>(x, gy, B, Cin, Cout, r, TS, ws, st);
-  else rc = c8 ? launch_wgrad<4, 8, 8, 8>(x, gy, B, Cin, Cout, r, TS, ws, st) : launch_wgrad<4, 8, 8, 4>(x, gy, B, Cin, Cout, r, TS, ws, st);
+  const int rc = conv_tile256_dispatch(r, [&](auto... tile) {
+    return Cin % 8 == 0 ? launch_wgrad<8>(tile..., x, gy, B, Cin, Cout, r, TS, ws, st)
+                        : launch_wgrad<4>(tile..., x, gy, B, Cin, Cout, r, TS, ws, st);
+  });
   if (rc) return rc;
   const size_t n = (size_t)Cout * Cin * 27;
   return lion_launch<conv3d_wgrad_reduce_kernel>((unsigned)((n + 255) / 256), 256, 0, st, ws, B * TS, n, gw);
@@ -532,16 +531,14 @@ static int wgrad_split_impl(const float *x, const float *gy, const int32_t *cnt,
   const size_t n = (size_t)Cout * Cin * 27;
   unsigned char *skip = nullptr;
   if (cnt) {   // the tile map lives behind the partials (the workspace's 64 spare floats are not enough: B * ntiles bytes)
-    const int td = r == 32 ? 2 : 4, th = r == 8 ? 8 : 4, ntiles = (r / td) * (r / th);
+    const ConvTileDims t = conv_tile256(r);
     const size_t used = (size_t)B * TS * n;
-    if (ws_floats < used + ((size_t)B * ntiles + 3) / 4) return LION_EWORKSPACE;
+    if (ws_floats < used + ((size_t)B * conv_tile256_count(r) + 3) / 4) return LION_EWORKSPACE;
     skip = reinterpret_cast<unsigned char *>(ws + used);
-    if (int e = lion_launch<wgrad_tile_skip_kernel>(B, 256, 0, st, cnt, r, td, th, skip)) return e;
+    if (int e = lion_launch<wgrad_tile_skip_kernel>(B, 256, 0, st, cnt, r, t.td, t.th, skip)) return e;
   }
-  int rc;
-  if (r == 32) rc = launch_wgrad_split<2, 4, 32, 8>(x, gy, B, Cin, Cout, r, TS, skip, ws, st);
-  else if (r == 16) rc = launch_wgrad_split<4, 4, 16, 8>(x, gy, B, Cin, Cout, r, TS, skip, ws, st);
-  else rc = launch_wgrad_split<4, 8, 8, 8>(x, gy, B, Cin, Cout, r, TS, skip, ws, st);
+  const int rc = conv_tile256_dispatch(
+      r, [&](auto... tile) { return launch_wgrad_split<8>(tile..., x, gy, B, Cin, Cout, r, TS, skip, ws, st); });
   if (rc) return rc;
   return lion_launch<conv3d_wgrad_reduce_kernel>((unsigned)((n + 255) / 256), 256, 0, st, ws, B * TS, n, gw);
 }

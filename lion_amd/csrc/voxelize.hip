@@ -21,7 +21,7 @@
 // No memset, no global atomics, no workspace.
 //   fallback (r^3 or N too large for LDS, misaligned output): memset + integer/float atomics, like
 //            the reference but with a (points x batch) grid.  Within 1e-6 of the oracle, not bit-exact.
-#include "common.h"
+#include "conv3d_tiles.h"
 
 namespace {
 
@@ -882,23 +882,6 @@ int lion_voxel_index(const float *coords, int B, int N, int r, int normalize, fl
 }
 
 static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r, float *out,
-                              const int32_t *occ_flags, lionStream_t stream);
-
-int lion_voxel_scatter(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r, float *out,
-                       lionStream_t stream) {
-  return voxel_scatter_impl(feat, plan, plan_bytes, B, C, N, r, out, nullptr, stream);
-}
-
-// The same scatter for a grid whose ONLY reader is the sparse convolution popping occ_m1 (lion_conv3d_tile_occupancy[_aware],
-// margin 1; r in {16, 32}): z-rows outside the halo of every occupied tile are not written (left as allocated).
-int lion_voxel_scatter_read(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r,
-                            const int32_t *occ_m1, float *out, lionStream_t stream) {
-  if (!occ_m1) return LION_EINVAL;
-  if (r != 16 && r != 32) return LION_EUNSUPPORTED;
-  return voxel_scatter_impl(feat, plan, plan_bytes, B, C, N, r, out, occ_m1, stream);
-}
-
-static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r, float *out,
                               const int32_t *occ_flags, lionStream_t stream) {
   if (!feat || !plan || !out || B <= 0 || C <= 0 || N <= 0 || r <= 0) return LION_EINVAL;
   const size_t need = lion_voxel_plan_bytes(B, N, r);
@@ -936,16 +919,29 @@ static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_b
   const int grid = ((B + 7) / 8) * 8 * p.S * p.CS;
   const int r3 = r * r * r;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int occ_td = 0, occ_th = 0;   // the tile geometry of the flags: the sparse convolution's own choice (csrc/conv3d.hip)
-  if (occ_flags)
-    if (int e = lion_internal_sparse_tile_dims(r, &occ_td, &occ_th)) return e;
-  return lion_with_flags(occ_flags != nullptr, [&](auto READ) { // without flags occ_td = occ_th = 0
+  // the tile geometry of the flags: the sparse convolution's own (conv3d_tiles.h); without flags occ_td = occ_th = 0
+  const ConvTileDims occ_t = occ_flags ? conv_tile256(r) : ConvTileDims{0, 0, 0};
+  return lion_with_flags(occ_flags != nullptr, [&](auto READ) {
     return vox_np_dispatch(p.NP, [&](auto NPV) {
       return lion_launch<vox_scatter_kernel<decltype(NPV)::value, decltype(READ)::value>>(
           grid, VT, lds, st, feat, plan, B, C, N, r3, p.S, p.CS, p.SV, p.n_words, (int)(arena / 4), 64, out, occ_flags, r,
-          occ_td, occ_th);
+          occ_t.td, occ_t.th);
     });
   });
+}
+
+int lion_voxel_scatter(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r, float *out,
+                       lionStream_t stream) {
+  return voxel_scatter_impl(feat, plan, plan_bytes, B, C, N, r, out, nullptr, stream);
+}
+
+// The same scatter for a grid whose ONLY reader is the sparse convolution popping occ_m1 (lion_conv3d_tile_occupancy[_aware],
+// margin 1; r in {16, 32}): z-rows outside the halo of every occupied tile are not written (left as allocated).
+int lion_voxel_scatter_read(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r,
+                            const int32_t *occ_m1, float *out, lionStream_t stream) {
+  if (!occ_m1) return LION_EINVAL;
+  if (r != 16 && r != 32) return LION_EUNSUPPORTED;
+  return voxel_scatter_impl(feat, plan, plan_bytes, B, C, N, r, out, occ_m1, stream);
 }
 
 int lion_avg_voxelize_backward(const float *gy, const int32_t *ind, const int32_t *cnt, int B,

@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from ._wcache import WeightCache
 from . import conv_ops
-from .conv_ops import packed_weight, supported
+from .conv_ops import supported
 
 
 def _border_sums(weight):
@@ -98,13 +98,11 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
     lib = _lib.load()
     b, cin, r = x.shape[0], x.shape[1], x.shape[2]
     cout = conv.out_channels
-    use_split = conv_ops.use_split(split, cin, cout, r)
-    if cin % 4:
-        assert pro is None
-        x = torch.cat([x, x.new_zeros(b, 4 - cin % 4, r, r, r)], dim=1)
-        cin = x.shape[1]
-    x = x.contiguous()
-    wp = conv_ops.split_packed_weight(conv.weight) if use_split else packed_weight(conv.weight)
+    route = conv_ops.conv_route(cin, cout, r, split, x)
+    assert pro is None or cin % 4 == 0
+    x = conv_ops.pad_cin4(x)
+    cin = x.shape[1]
+    wp = route.packed(conv.weight)
     y = torch.empty((b, cout, r, r, r), device=x.device, dtype=torch.float32)
     pbias = tconst = None
     pa, pb = _pro_pair(pro)
@@ -120,14 +118,12 @@ def conv3d_fused(x, conv, pro=None, want_stats=True, occ=None, prev_conv=None, s
             _lib.call("lion_conv3d_const_response", ws, bias, pbias, pa, pb, b, cin, cout, tconst)
     stats = None
     if want_stats:
-        tiles = lib.lion_conv3d_split_stat_tiles(r, cout) if use_split else lib.lion_conv3d_stat_tiles(r, cout, b, int(sparse))
+        query = getattr(lib, route.stat_tiles)
+        tiles = query(r, cout, b, int(sparse)) if route.kind == "f32" else query(r, cout)
         stats = torch.empty((b, cout, tiles, 2), device=x.device, dtype=torch.float32)
     if not sparse:
         occ = None
-    entry = "lion_conv3d_k3_fused_forward"
-    if use_split:
-        entry = "lion_conv3d_k3_half_forward" if conv_ops.use_half(cin, cout, r, x) else "lion_conv3d_k3_split_forward"
-    _lib.call(entry, x, wp, bias, b, cin, cout, r, pa, pb, pbias, tconst, y, stats, occ)
+    _lib.call(route.forward, x, wp, bias, b, cin, cout, r, pa, pb, pbias, tconst, y, stats, occ)
     if fold is not None:
         return y, fold.apply(stats)
     return y, stats

@@ -45,7 +45,7 @@ def k_products(cin):
     return 27 * ceil4(cin)
 
 
-# ---- the plan of the library, restated (conv_plan / conv_tile_dims / launch_conv of csrc/conv3d.hip) -------------------
+# ---- the plan of the library, restated (conv_plan / launch_conv of csrc/conv3d.hip, csrc/conv3d_tiles.h) --------------
 
 def conv_plan(r, cout, B, sparse):
     """(vb, cot, tiles): voxel blocks per wave, output channels per workgroup, spatial tiles; (0, 0, 0): unsupported"""
@@ -72,7 +72,7 @@ def tile_dims(r, vb):
     return (4 if vb == 2 else 2), 8, r
 
 
-# the ten ConvTile<TD, TH, TW, COT, VB> of launch_conv as (r, vb, cot)
+# the ten launch_conv<COT>(TD, TH, TW) that the fp32 entry instantiates, as (r, vb, cot)
 LAUNCH_TILES = {(32, 2, 64), (32, 4, 64), (16, 4, 64), (32, 4, 32), (32, 2, 32), (16, 2, 32), (16, 2, 64), (16, 4, 32),
                 (8, 2, 64), (8, 1, 32)}
 

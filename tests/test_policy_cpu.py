@@ -13,6 +13,32 @@ def test_conv_split_policy():
     assert conv_ops.use_split(None, 128, 128, 8) == (conv_ops.SPLIT and conv_ops.SPLIT_MIN_R <= 8)
 
 
+def test_conv_route_follows_the_policy():
+    """conv_route names the split / half entry points exactly where use_split / use_half say so, and only entry points the
+    library has; an input that requires grad never goes to the half kernel"""
+    import torch
+    from lion_amd import _lib
+    shapes = [(64, 64, 32), (128, 128, 8), (4, 32, 32), (64, 48, 32), (64, 64, 12), (64, 64, 16), (35, 64, 16),
+              (128, 128, 16), (16, 32, 16)]                # those of test_conv_split_policy and of the half policy's table
+    grad_x = torch.zeros(1, 64, 2, 2, 2, requires_grad=True)
+    for precision in conv_ops.PRECISIONS:
+        with conv_ops.conv_precision(precision):
+            for shape in shapes:
+                for split in (None, True, False):
+                    route = conv_ops.conv_route(*shape, split=split)
+                    want = "f32" if not conv_ops.use_split(split, *shape) else "half" if conv_ops.use_half(*shape) else "split"
+                    assert route.kind == want, (precision, shape, split)
+                    names = [v for v in route if isinstance(v, str) and v != route.kind]
+                    assert len(names) == 2 and all(n in _lib.SIGNATURES for n in names), (precision, shape, split, names)
+                    assert ("_half_" in route.forward) == (route.kind == "half"), (precision, shape, split)
+                    assert route.kind != "half" or conv_ops.half_supported(*shape), (precision, shape, split)
+                    assert conv_ops.conv_route(*shape, split=split, half=False).kind in ("f32", "split")
+                    with torch.enable_grad():
+                        assert conv_ops.conv_route(*shape, split=split, x=grad_x).kind != "half", (precision, shape, split)
+    with conv_ops.conv_precision("half"):
+        assert conv_ops.conv_route(64, 64, 32, split=True).kind == "half"   # (so the loop above did see the half route)
+
+
 def test_pointwise_split_policy():
     pol = fused_ops.pw_use_split
     if fused_ops.PW_SPLIT:
