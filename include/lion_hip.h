@@ -302,6 +302,38 @@ int lion_chain_update_encode_cm(const float *base, const float *eps_cm, int B, i
 int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m, float s,
                        const uint32_t *seed /* device u32[2]: lo, hi; may be NULL with z_in */, uint32_t stream_id,
                        float *out, float *z_out, lionStream_t stream);
+/* Per-sample keys: noise addressed by sample, not by batch position.  keys is device u32[2*B], the lo and hi word of sample b's
+ * 64-bit Philox key at keys[2b], keys[2b+1]; n is the element count of ONE sample and must be a multiple of 4, so that no quad
+ * straddles two samples.  The draw for elements 4j .. 4j+3 of sample b is the chain generator's (Philox4x32-10, Box-Muller: the
+ * device function of lion_chain_update_noise) under keys[b] at counter = (j, step word, stream_id), j counted WITHIN the sample:
+ * bit for bit what the single-seed entry points above draw for a one-sample tensor of n elements under seed = keys[b].  It
+ * depends on neither B, nor b, nor the other keys.  (Grid: y = sample, x over the sample's quads; no division.)
+ *   lion_philox_normal_keyed                   out f32[B][n] = z alone, at the given step word: a chain's start latent
+ *                                              (LION_START_STEP_WORD), the per-step noise of an eager loop (the row's index)
+ *   lion_chain_update_noise_keyed / _cm_keyed  lion_chain_update_noise / _cm (mode, `cur` contract, aliasing, z_out as there)
+ *   lion_chain_update_multistep_noise_keyed / _cm_keyed   lion_chain_update_multistep_noise / _cm: the noise scale is
+ *                                              table[8*i + 7]; where it is 0 nothing is drawn, no key is read, z_out gets zeros
+ *   lion_chain_diffuse_keyed                   lion_chain_diffuse without z_in, at LION_DIFFUSE_STEP_WORD; any alignment
+ * The _cm forms take x / out / z_out f32[B][N][4] and eps_cm f32[B][4][N]: n = 4*N there.
+ * LION_START_STEP_WORD is the second reserved step word, beside LION_DIFFUSE_STEP_WORD: a chain step's word is its row index,
+ * which is below the table's capacity (an int), so neither reserved word can collide with a step's, nor with each other.
+ * LION_EINVAL before any launch: a NULL required pointer (z_out may be NULL), B <= 0 or B > 65535, n <= 0 / N <= 0, n % 4 != 0,
+ * a mode outside {0, 1}, or (all but lion_chain_diffuse_keyed) a pointer other than eps_cm and keys not 16-byte aligned. */
+#define LION_START_STEP_WORD 0xFFFFFFFEu
+int lion_philox_normal_keyed(const uint32_t *keys /* device u32[2*B] */, int B, int n, uint32_t step_word, uint32_t stream_id,
+                             float *out, lionStream_t stream);
+int lion_chain_update_noise_keyed(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                  const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, lionStream_t stream);
+int lion_chain_update_noise_cm_keyed(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
+                                     const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, lionStream_t stream);
+int lion_chain_update_multistep_noise_keyed(const float *x, const float *eps, const float *hist, int B, int n, const float *cur,
+                                            const float *table, const uint32_t *keys, uint32_t stream_id, float *out,
+                                            float *hist_out, float *z_out, lionStream_t stream);
+int lion_chain_update_multistep_noise_cm_keyed(const float *x, const float *eps_cm, const float *hist, int B, int N,
+                                               const float *cur, const float *table, const uint32_t *keys, uint32_t stream_id,
+                                               float *out, float *hist_out, float *z_out, lionStream_t stream);
+int lion_chain_diffuse_keyed(const float *x0, int B, int n, float m, float s, const uint32_t *keys, uint32_t stream_id,
+                             float *out, float *z_out, lionStream_t stream);
 /* x f32[B][N][D] (point-major latent; 3 <= D <= 8) -> channel-major all f32[B][D][N], coords f32[B][3][N] (rows 0-2),
  * rest f32[B][D-3][N]; each output may be NULL: the view / permute / slice / contiguous head of
  * models/latent_points_ada_localprior.py:72-84 + models/latent_points_ada.py:118-121 in one launch. */

@@ -154,6 +154,12 @@ SIGNATURES = {
     "lion_ddim_encode_update": (_i, [_vp, _vp, _sz, _f, _f, _f, _vp, _vp, _vp]),
     "lion_chain_update_encode": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "lion_chain_update_encode_cm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lion_philox_normal_keyed": (_i, [_vp, _i, _i, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "lion_chain_update_noise_keyed": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "lion_chain_update_noise_cm_keyed": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "lion_chain_update_multistep_noise_keyed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "lion_chain_update_multistep_noise_cm_keyed": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "lion_chain_diffuse_keyed": (_i, [_vp, _i, _i, _f, _f, _vp, C.c_uint32, _vp, _vp, _vp]),
     "lion_latent_unpack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_concat_broadcast": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lion_three_nn_interpolate_cat_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -43,6 +43,50 @@ UPDATE = {
     SDE_DPMPP: ("lion_chain_update_multistep_noise", ("x", "eps", "hist", "size", "cur", "table", "seed", 0, "x", "hist", "z")),
     ENCODE: ("lion_chain_update_encode", ("base", "eps", "size", "cur", "x", "base")),
 }
+# Per-sample keys (GraphedChain(keyed=True)): the modes that draw end their step with the "_keyed" entry point
+# of the same name, which takes the chain's `keys` (int32[B, 2]: a 64-bit Philox key per sample) where the spec says "seed" and
+# (num_samples, elements per sample) where it says "size".  DPMPP and ENCODE draw nothing and have no keyed form.
+KEYED_MODES = (DDIM, DDPM, SDE_DPMPP)
+# the step words no chain step can have (a step's word is its row index < the table's capacity): include/lion_hip.h
+START_STEP_WORD, DIFFUSE_STEP_WORD = 0xFFFFFFFE, 0xFFFFFFFF
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def split_seed(seed: int, n: int):
+    """n 64-bit keys from one (SplitMix64, Steele et al. 2014): one seed -> a key per purpose, or per shape"""
+    out, state = [], seed & _MASK64
+    for _ in range(n):
+        state = (state + 0x9E3779B97F4A7C15) & _MASK64
+        z = state
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+        out.append(z ^ (z >> 31))
+    return out
+
+
+def sample_keys(seeds, num_samples, who="seeds") -> list:
+    """`seeds` -- a sequence or an integer tensor of num_samples ints -- as a list of Python ints mod 2^64; ValueError where the
+    count is not num_samples.  Host work only."""
+    if isinstance(seeds, torch.Tensor):
+        seeds = seeds.detach().cpu().reshape(-1).tolist()
+    elif isinstance(seeds, np.ndarray):
+        seeds = seeds.reshape(-1).tolist()
+    try:
+        keys = [int(s) & _MASK64 for s in seeds]
+    except TypeError as e:
+        raise ValueError(f"{who}: a sequence or tensor of {num_samples} ints, got {seeds!r}") from e
+    if len(keys) != int(num_samples):
+        raise ValueError(f"{who}: {len(keys)} seeds for {num_samples} samples")
+    return keys
+
+
+def key_words(keys, device=None):
+    """a list of 64-bit keys as int32[B, 2], the (lo, hi) words the keyed kernels read from device memory (device None: host)"""
+    k = np.array([[s & 0xFFFFFFFF, (s >> 32) & 0xFFFFFFFF] for s in keys], dtype=np.uint32).view(np.int32)
+    t = torch.from_numpy(k)
+    return t if device is None else t.to(device)
+
+
 # tests: a list here makes every chain run append (start latent, [the noise each step drew]) -- what an eager loop needs
 # to repeat a graphed chain draw for draw (run_ddim(given_noise=...)); chains are then captured with the noise output on
 RECORD = None
@@ -220,17 +264,25 @@ class CapturedStep:
 
 class GraphedChain:
     def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
-                 record_noise=False):
-        self.model, self.mode, self.capacity = model, mode, int(capacity)
+                 record_noise=False, keyed=False):
+        """keyed: sample b draws its noise under its own key, seed[b], at counters that count within the sample (the "_keyed"
+        update kernels) -- `seed` is then int32[num_samples, 2] and prepare() / run() take num_samples keys."""
+        self.model, self.mode, self.capacity, self.keyed = model, mode, int(capacity), bool(keyed)
         dev = torch.device(device)
         size = [num_samples] + list(shape)
+        per_sample = int(np.prod(shape))
+        if keyed and mode not in KEYED_MODES:
+            raise ValueError(f"GraphedChain: mode {mode} draws nothing and has no keyed form")
+        if keyed and per_sample % 4 != 0:
+            raise ValueError(f"GraphedChain: keyed noise needs a multiple of 4 elements per sample, got {per_sample}")
         self.x = torch.zeros(size, device=dev)
         self.t = torch.zeros(num_samples, device=dev)
         self.cond = None if condition_input is None else condition_input.detach().clone().contiguous()
         self.clip = None if clip_feat is None else clip_feat.detach().clone().contiguous()
         self.table = torch.zeros(self.capacity, 8, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.seed = torch.zeros(2, dtype=torch.int32, device=dev)   # two 32-bit words of the Philox key
+        # two 32-bit words of the Philox key -- of the chain, or (keyed) of every sample
+        self.seed = torch.zeros((num_samples, 2) if keyed else 2, dtype=torch.int32, device=dev)
         self.cur = torch.zeros(8, device=dev)
         self.z = torch.zeros(size, device=dev) if record_noise and mode != ENCODE else None   # tests: the noise each step used
         self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
@@ -270,20 +322,25 @@ class GraphedChain:
             assert not self.cm_out or tuple(eps.shape) == (num_samples, n_cls, n_pts)
             entry, spec = UPDATE[mode]
             given = {"eps": [eps], "size": [num_samples, n_pts] if self.cm_out else [self.x.numel()]}
+            if self.keyed:
+                spec = tuple("keys" if a == "seed" else a for a in spec)
+                given["keys"] = [self.seed]
+                if not self.cm_out:
+                    given["size"] = [num_samples, per_sample]
             args = []
             for a in spec:
                 args += given[a] if a in given else [getattr(self, a) if isinstance(a, str) else a]
-            _lib.call(entry + ("_cm" if self.cm_out else ""), *args)
+            _lib.call(entry + ("_cm" if self.cm_out else "") + ("_keyed" if self.keyed else ""), *args)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
 
     def matches(self, condition_input, clip_feat):
         return same_conditioning(self, condition_input, clip_feat) and self.step.valid()
 
     @torch.no_grad()
-    def run(self, x_init, table: np.ndarray, seed: int, condition_input=None, clip_feat=None, trajectory=None,
+    def run(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None, trajectory=None,
             trajectory_before_last=False, noise_trajectory=None, state_hook=None, trajectory_rows=None):
         """x_init: the chain's start; table [S, 8] float32 rows {t_model, a0..a5, a6} (a6: SDE_DPMPP's noise scale, 0 in
-        every other mode).  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after
+        every other mode); seed: the chain's 64-bit key -- of a keyed chain, a sequence or tensor of one key per sample.  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after
         every step (before the last step's update if `trajectory_before_last`, as run_denoising_diffusion reports it); with
         `trajectory_rows(i)`, a predicate on the step's index, only after the steps it holds for (the encoder: a leg's last
         row).
@@ -308,9 +365,10 @@ class GraphedChain:
         return self.x.clone()
 
     @torch.no_grad()
-    def prepare(self, x_init, table: np.ndarray, seed: int, condition_input=None, clip_feat=None) -> int:
+    def prepare(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None) -> int:
         """everything a chain needs in device memory before its first replay (on the current stream): the start latent, the
-        conditioning, the schedule table, the time-embedding rows, the step counter and the Philox key.  Returns S."""
+        conditioning, the schedule table, the time-embedding rows, the step counter and the Philox key (keyed: the keys, a
+        sequence or tensor of one per sample).  Returns S."""
         S = int(table.shape[0])
         assert 1 <= S <= self.capacity and table.shape[1] == 8
         self.x.copy_(x_init)
@@ -329,8 +387,11 @@ class GraphedChain:
             self.hist.zero_()
         if self.base is not None:
             self.base.copy_(self.x)
-        words = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
-        self.seed.copy_(torch.from_numpy(words))
+        if self.keyed:
+            self.seed.copy_(key_words(sample_keys(seed, self.x.shape[0], "GraphedChain")))
+        else:
+            words = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
+            self.seed.copy_(torch.from_numpy(words))
         return S
 
 
@@ -339,15 +400,18 @@ for _name in ("replay", "graph", "graphs", "graph_b", "geo_graphs", "pinned", "p
 
 
 class ChainCache(LRU):
-    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape) -> GraphedChain"""
+    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed) -> GraphedChain.  A keyed and an
+    unkeyed capture of one (model, mode, shape) coexist, each in a slot of its own; the modes that draw nothing have the
+    unkeyed capture only and serve a keyed call with it."""
 
-    def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity):
+    def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity, keyed=False):
         rec = RECORD is not None
+        keyed = bool(keyed) and mode in KEYED_MODES
         return self.lookup(
-            (id(model), mode, int(num_samples), tuple(shape), str(device), rec),
+            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed),
             lambda hit: hit.model is model and hit.capacity >= table_capacity and hit.matches(condition_input, clip_feat),
             lambda: GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity,
-                                 record_noise=rec))
+                                 record_noise=rec, keyed=keyed))
 
 
 def draw_seed() -> int:

@@ -84,12 +84,38 @@ __device__ __forceinline__ void load_quad(const float *p, size_t i, size_t numel
   }
 }
 
+// ---- which quad a lane owns, and which Philox (counter, key) draws its noise ------------------------------------------------
+// Unkeyed (one 64-bit key per chain): a 1-D grid over the flat tensor; lane q owns quad q, and q is also the counter's quad word.
+// KEYED (one key per sample, keys = u32[2*B]): grid.y is the sample b, grid.x walks that sample's own `sample_quads` = n/4 quads
+// (n % 4 == 0: no quad straddles two samples, every quad is full); the counter's quad word is j, the quad's index WITHIN the
+// sample, under keys[b] -- what the unkeyed kernel draws for a one-sample tensor of n elements under that key, whatever B, b
+// and the other keys are.  No division.  False: the lane owns nothing.  `key` is only pointed at, not read.
+template <bool KEYED>
+__device__ __forceinline__ bool own_quad(size_t numel, uint32_t sample_quads, const uint32_t *words, size_t &q, uint64_t &ctr,
+                                         const uint32_t *&key) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (KEYED) {
+    if (t >= sample_quads) return false;
+    q = (size_t)blockIdx.y * sample_quads + t;
+    key = words + 2 * (size_t)blockIdx.y;
+  } else {
+    if (t * 4 >= numel) return false;
+    q = t;
+    key = words;
+  }
+  ctr = t;
+  return true;
+}
+
 // eps is flat like x, or (cm_points = N != 0) the denoiser's channel-major output [B][4][N] beside the point-major latent
 // x [B][N][4]: quad q = (b, n) takes its four channels from four rows -- the permute(0, 2, 1).contiguous() copy of the model's
-// output folded into this read.  numel = B*N*4 there: every quad is full.
-__device__ __forceinline__ void load_eps_quad(const float *eps, size_t q, size_t numel, bool full, int cm_points, float v[4]) {
+// output folded into this read.  numel = B*N*4 there: every quad is full.  KEYED: (b, n) = (grid.y, ctr), as own_quad left them.
+template <bool KEYED>
+__device__ __forceinline__ void load_eps_quad(const float *eps, size_t q, size_t ctr, size_t numel, bool full, int cm_points,
+                                              float v[4]) {
   if (cm_points) {
-    const size_t b = q / (size_t)cm_points, n = q - b * (size_t)cm_points;
+    const size_t b = KEYED ? (size_t)blockIdx.y : q / (size_t)cm_points;
+    const size_t n = KEYED ? ctr : q - b * (size_t)cm_points;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = eps[(b * 4 + j) * (size_t)cm_points + n];
   } else {
@@ -127,22 +153,25 @@ __global__ void begin_step_kernel(const float *__restrict__ table, int n_steps, 
 
 // MODE 0: DDIM  out = x*a0 + (a1*eps + a2*z)                     (a = {s, c, sigma})
 // MODE 1: DDPM  a5 != 0 (t == 0): out = a0*(x - a1*eps);  else out = a0*(x - a1*eps/a2) + (a3*z)*a4
-template <int MODE>
-__global__ void update_noise_kernel(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
-                                    const float *__restrict__ cur, const uint32_t *__restrict__ seed_words,
-                                    uint32_t stream_id, float *__restrict__ out, float *__restrict__ z_out, int cm_points) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+template <int MODE, bool KEYED>
+__device__ __forceinline__ void update_noise_body(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
+                                                  uint32_t sample_quads, const float *__restrict__ cur,
+                                                  const uint32_t *__restrict__ seed_words, uint32_t stream_id,
+                                                  float *__restrict__ out, float *__restrict__ z_out, int cm_points) {
+  size_t q;
+  uint64_t ctr;
+  const uint32_t *key;
+  if (!own_quad<KEYED>(numel, sample_quads, seed_words, q, ctr, key)) return;
   const size_t i = q * 4;
-  if (i >= numel) return;
   const float a0 = cur[1], a1 = cur[2], a2 = cur[3], a3 = cur[4], a4 = cur[5], a5 = cur[6];
   const uint32_t step = (uint32_t)__float_as_int(cur[7]);
-  const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
+  const uint64_t seed = (uint64_t)key[0] | ((uint64_t)key[1] << 32);
   float z[4];
-  normal4(q, step, stream_id, seed, z);
+  normal4(ctr, step, stream_id, seed, z);
   float xv[4], ev[4], o[4];
   const bool full = i + 3 < numel;
   load_quad(x, i, numel, full, xv);
-  load_eps_quad(eps, q, numel, full, cm_points, ev);
+  load_eps_quad<KEYED>(eps, q, ctr, numel, full, cm_points, ev);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (MODE == 0) {
@@ -155,6 +184,35 @@ __global__ void update_noise_kernel(const float *__restrict__ x, const float *__
   }
   store_quad(out, i, numel, full, o);
   if (z_out) store_quad(z_out, i, numel, full, z);
+}
+
+template <int MODE>
+__global__ void update_noise_kernel(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
+                                    const float *__restrict__ cur, const uint32_t *__restrict__ seed_words,
+                                    uint32_t stream_id, float *__restrict__ out, float *__restrict__ z_out, int cm_points) {
+  update_noise_body<MODE, false>(x, eps, numel, 0, cur, seed_words, stream_id, out, z_out, cm_points);
+}
+
+// the keyed form: grid (ceil(sample_quads / 256), B), keys u32[2*B]
+template <int MODE>
+__global__ void update_noise_keyed_kernel(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
+                                          uint32_t sample_quads, const float *__restrict__ cur,
+                                          const uint32_t *__restrict__ keys, uint32_t stream_id, float *__restrict__ out,
+                                          float *__restrict__ z_out, int cm_points) {
+  update_noise_body<MODE, true>(x, eps, numel, sample_quads, cur, keys, stream_id, out, z_out, cm_points);
+}
+
+// out[b][.] = z alone: sample b's draw at counter (j, step, stream_id) under keys[b] -- the start latent of a keyed chain
+// (LION_START_STEP_WORD), the reparameterisation draws, the per-step noise of the eager loops
+__global__ void normal_keyed_kernel(const uint32_t *__restrict__ keys, size_t numel, uint32_t sample_quads, uint32_t step,
+                                    uint32_t stream_id, float *__restrict__ out) {
+  size_t q;
+  uint64_t ctr;
+  const uint32_t *key;
+  if (!own_quad<true>(numel, sample_quads, keys, q, ctr, key)) return;
+  float z[4];
+  normal4(ctr, step, stream_id, (uint64_t)key[0] | ((uint64_t)key[1] << 32), z);
+  store_quad(out, q * 4, numel, true, z);
 }
 
 // ---- host side of the quad kernels ---------------------------------------------------------------------------------------
@@ -172,6 +230,27 @@ static int quad_blocks(size_t numel, unsigned *blocks) {
   if (numel == 0 || n > 0x7fffffffu) return LION_EINVAL;
   *blocks = (unsigned)n;
   return LION_OK;
+}
+
+// B samples of n elements, one key each: LION_OK, the grid (x over a sample's quads, y = sample) and n/4, or LION_EINVAL
+// (B <= 0, n <= 0, n % 4 != 0 -- a quad would straddle two samples --, or more samples than a grid's y dimension holds)
+static int keyed_grid(int B, int n, dim3 *grid, uint32_t *sample_quads) {
+  if (B <= 0 || n <= 0 || n % 4 != 0 || B > 65535) return LION_EINVAL;
+  *sample_quads = (uint32_t)(n / 4);
+  *grid = dim3((*sample_quads + 255) / 256, (unsigned)B);
+  return LION_OK;
+}
+
+static int update_noise_keyed_launch(int mode, hipStream_t st, const float *x, const float *eps, int B, int n, const float *cur,
+                                     const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, int cm_points) {
+  dim3 grid;
+  uint32_t sq;
+  if (keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
+  const size_t numel = (size_t)B * n;
+  return mode == 0 ? lion_launch<update_noise_keyed_kernel<0>>(grid, 256, 0, st, x, eps, numel, sq, cur, keys, stream_id, out,
+                                                               z_out, cm_points)
+                   : lion_launch<update_noise_keyed_kernel<1>>(grid, 256, 0, st, x, eps, numel, sq, cur, keys, stream_id, out,
+                                                               z_out, cm_points);
 }
 
 static int update_noise_launch(int mode, hipStream_t st, const float *x, const float *eps, size_t numel,
@@ -192,26 +271,30 @@ static int update_noise_launch(int mode, hipStream_t st, const float *x, const f
 // hist_out may alias hist (a lane reads every quad it needs before its first store, no lane reads another's).
 // NOISE (the stochastic form below): out gains + a6*z where a6 != 0; without it z_in, a6, the seed, step, stream_id and z_out
 // are not looked at and nothing of that path is compiled in.
-template <bool NOISE>
+// KEYED: own_quad's per-sample counters and keys (seed_words = keys u32[2*B]; sample_quads = n/4, else unused).
+template <bool NOISE, bool KEYED = false>
 __device__ __forceinline__ void multistep_body(const float *x, const float *eps, const float *hist, const float *z_in,
                                                size_t numel, float a0, float a1, float a2, float a3, float a4, float a5,
                                                float a6, const uint32_t *__restrict__ seed_words, uint32_t step,
-                                               uint32_t stream_id, float *out, float *hist_out, float *z_out, int cm_points) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                               uint32_t stream_id, float *out, float *hist_out, float *z_out, int cm_points,
+                                               uint32_t sample_quads = 0) {
+  size_t q;
+  uint64_t ctr;
+  const uint32_t *key;
+  if (!own_quad<KEYED>(numel, sample_quads, seed_words, q, ctr, key)) return;
   const size_t i = q * 4;
-  if (i >= numel) return;
   const bool second = a5 != 0.f, noisy = NOISE && a6 != 0.f;
   float xv[4], ev[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, o[4], p[4];
   const bool full = i + 3 < numel;
   load_quad(x, i, numel, full, xv);
   if (second) load_quad(hist, i, numel, full, hv);
-  load_eps_quad(eps, q, numel, full, cm_points, ev);
+  load_eps_quad<KEYED>(eps, q, ctr, numel, full, cm_points, ev);
   if (noisy) {
     if (z_in) {
       load_quad(z_in, i, numel, full, z);
     } else {
-      const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
-      normal4(q, step, stream_id, seed, z);
+      const uint64_t seed = (uint64_t)key[0] | ((uint64_t)key[1] << 32);
+      normal4(ctr, step, stream_id, seed, z);
     }
   }
 #pragma unroll
@@ -278,6 +361,27 @@ static int multistep_noise_launch(hipStream_t st, const float *x, const float *e
                                              cm_points);
 }
 
+// the captured step's form of it under per-sample keys (grid and keys: update_noise_keyed_kernel): coefficients, step word and
+// a6 from `cur` and `table`, no z_in; where a6 == 0 no key is read
+__global__ void multistep_noise_keyed_kernel(const float *x, const float *eps, const float *hist, size_t numel,
+                                             uint32_t sample_quads, const float *__restrict__ cur,
+                                             const float *__restrict__ table, const uint32_t *__restrict__ keys,
+                                             uint32_t stream_id, float *out, float *hist_out, float *z_out, int cm_points) {
+  const uint32_t step = (uint32_t)__float_as_int(cur[7]);
+  multistep_body<true, true>(x, eps, hist, nullptr, numel, cur[1], cur[2], cur[3], cur[4], cur[5], cur[6],
+                             table[(size_t)step * 8 + 7], keys, step, stream_id, out, hist_out, z_out, cm_points, sample_quads);
+}
+
+static int multistep_noise_keyed_launch(hipStream_t st, const float *x, const float *eps, const float *hist, int B, int n,
+                                        const float *cur, const float *table, const uint32_t *keys, uint32_t stream_id,
+                                        float *out, float *hist_out, float *z_out, int cm_points) {
+  dim3 grid;
+  uint32_t sq;
+  if (keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
+  return lion_launch<multistep_noise_keyed_kernel>(grid, 256, 0, st, x, eps, hist, (size_t)B * n, sq, cur, table, keys,
+                                                   stream_id, out, hist_out, z_out, cm_points);
+}
+
 // Deterministic encoder (refined DDIM inversion, DiffusionDiscretized.run_ddim_forward): one row of a leg n -> t from low
 // noise to high noise, one rounding per written operation:
 //   out = a0*base + a1*eps;   if (a2 != 0) base_out = out
@@ -297,7 +401,7 @@ __global__ void encode_kernel(const float *base, const float *eps, size_t numel,
   float bv[4], ev[4], o[4];
   const bool full = i + 3 < numel;
   load_quad(base, i, numel, full, bv);
-  load_eps_quad(eps, q, numel, full, cm_points, ev);
+  load_eps_quad<false>(eps, q, q, numel, full, cm_points, ev);
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(a0, bv[j]), mul_rn(a1, ev[j]));
   store_quad(out, i, numel, full, o);
@@ -315,25 +419,41 @@ static int encode_launch(hipStream_t st, const float *base, const float *eps, si
 // flat tensor takes Philox counter (q, LION_DIFFUSE_STEP_WORD, stream_id), whatever the pointers' alignment.  VEC: every pointer
 // is 16-byte aligned, so that a quad below numel is `full`; without it every quad goes element by element.
 // The tensors are not __restrict__: out may alias x0 (a lane reads its quad before it writes it, no lane reads another's).
-template <bool VEC>
-__global__ void diffuse_kernel(const float *x0, const float *z_in, size_t numel, float m, float s,
-                               const uint32_t *__restrict__ seed_words, uint32_t stream_id, float *out, float *z_out) {
-  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+// KEYED: own_quad's per-sample counters and keys.
+template <bool VEC, bool KEYED>
+__device__ __forceinline__ void diffuse_body(const float *x0, const float *z_in, size_t numel, uint32_t sample_quads, float m,
+                                             float s, const uint32_t *__restrict__ seed_words, uint32_t stream_id, float *out,
+                                             float *z_out) {
+  size_t q;
+  uint64_t ctr;
+  const uint32_t *key;
+  if (!own_quad<KEYED>(numel, sample_quads, seed_words, q, ctr, key)) return;
   const size_t i = q * 4;
-  if (i >= numel) return;
   const bool full = VEC && i + 3 < numel;
   float xv[4], z[4], o[4];
   if (z_in) {
     load_quad(z_in, i, numel, full, z);
   } else {
-    const uint64_t seed = (uint64_t)seed_words[0] | ((uint64_t)seed_words[1] << 32);
-    normal4(q, LION_DIFFUSE_STEP_WORD, stream_id, seed, z);
+    const uint64_t seed = (uint64_t)key[0] | ((uint64_t)key[1] << 32);
+    normal4(ctr, LION_DIFFUSE_STEP_WORD, stream_id, seed, z);
   }
   load_quad(x0, i, numel, full, xv);
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(m, xv[j]), mul_rn(s, z[j]));
   store_quad(out, i, numel, full, o);
   if (z_out) store_quad(z_out, i, numel, full, z);
+}
+
+template <bool VEC>
+__global__ void diffuse_kernel(const float *x0, const float *z_in, size_t numel, float m, float s,
+                               const uint32_t *__restrict__ seed_words, uint32_t stream_id, float *out, float *z_out) {
+  diffuse_body<VEC, false>(x0, z_in, numel, 0, m, s, seed_words, stream_id, out, z_out);
+}
+
+template <bool VEC>
+__global__ void diffuse_keyed_kernel(const float *x0, size_t numel, uint32_t sample_quads, float m, float s,
+                                     const uint32_t *__restrict__ keys, uint32_t stream_id, float *out, float *z_out) {
+  diffuse_body<VEC, true>(x0, nullptr, numel, sample_quads, m, s, keys, stream_id, out, z_out);
 }
 
 } // namespace
@@ -477,6 +597,62 @@ int lion_chain_diffuse(const float *x0, const float *z_in, size_t numel, float m
   return aligned16({x0, z_in, out, z_out})
              ? lion_launch<diffuse_kernel<true>>(blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out, z_out)
              : lion_launch<diffuse_kernel<false>>(blocks, 256, 0, st, x0, z_in, numel, m, s, seed, stream_id, out, z_out);
+}
+
+// ---- per-sample keys: keys u32[2*B] (lo, hi per sample), n elements per sample, n % 4 == 0 ---------------------------------
+int lion_philox_normal_keyed(const uint32_t *keys, int B, int n, uint32_t step_word, uint32_t stream_id, float *out,
+                             lionStream_t stream) {
+  dim3 grid;
+  uint32_t sq;
+  if (!keys || !out || keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
+  if (!aligned16({out})) return LION_EINVAL;
+  return lion_launch<normal_keyed_kernel>(grid, 256, 0, static_cast<hipStream_t>(stream), keys, (size_t)B * n, sq, step_word,
+                                          stream_id, out);
+}
+
+int lion_chain_update_noise_keyed(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                  const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
+  if (!x || !eps || !cur || !keys || !out || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!aligned16({x, eps, out, z_out})) return LION_EINVAL;
+  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, keys, stream_id, out, z_out, 0);
+}
+
+int lion_chain_update_noise_cm_keyed(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
+                                     const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
+  if (!x || !eps_cm || !cur || !keys || !out || N <= 0 || N > 0x1fffffff || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!aligned16({x, out, z_out})) return LION_EINVAL;
+  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, keys, stream_id, out,
+                                   z_out, N);
+}
+
+int lion_chain_update_multistep_noise_keyed(const float *x, const float *eps, const float *hist, int B, int n, const float *cur,
+                                            const float *table, const uint32_t *keys, uint32_t stream_id, float *out,
+                                            float *hist_out, float *z_out, lionStream_t stream) {
+  if (!x || !eps || !hist || !cur || !table || !keys || !out || !hist_out) return LION_EINVAL;
+  if (!aligned16({x, eps, hist, out, hist_out, z_out})) return LION_EINVAL;
+  return multistep_noise_keyed_launch(static_cast<hipStream_t>(stream), x, eps, hist, B, n, cur, table, keys, stream_id, out,
+                                      hist_out, z_out, 0);
+}
+
+int lion_chain_update_multistep_noise_cm_keyed(const float *x, const float *eps_cm, const float *hist, int B, int N,
+                                               const float *cur, const float *table, const uint32_t *keys, uint32_t stream_id,
+                                               float *out, float *hist_out, float *z_out, lionStream_t stream) {
+  if (!x || !eps_cm || !hist || !cur || !table || !keys || !out || !hist_out || N <= 0 || N > 0x1fffffff) return LION_EINVAL;
+  if (!aligned16({x, hist, out, hist_out, z_out})) return LION_EINVAL;
+  return multistep_noise_keyed_launch(static_cast<hipStream_t>(stream), x, eps_cm, hist, B, N * 4, cur, table, keys, stream_id,
+                                      out, hist_out, z_out, N);
+}
+
+int lion_chain_diffuse_keyed(const float *x0, int B, int n, float m, float s, const uint32_t *keys, uint32_t stream_id,
+                             float *out, float *z_out, lionStream_t stream) {
+  dim3 grid;
+  uint32_t sq;
+  if (!x0 || !keys || !out || keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t numel = (size_t)B * n;
+  return aligned16({x0, out, z_out})
+             ? lion_launch<diffuse_keyed_kernel<true>>(grid, 256, 0, st, x0, numel, sq, m, s, keys, stream_id, out, z_out)
+             : lion_launch<diffuse_keyed_kernel<false>>(grid, 256, 0, st, x0, numel, sq, m, s, keys, stream_id, out, z_out);
 }
 
 } // extern "C"

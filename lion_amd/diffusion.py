@@ -359,26 +359,68 @@ class DiffusionDiscretized(object):
             pred = model(x=x, t=timestep.float(), condition_input=condition_input, clip_feat=clip_feat, **kwargs)
             return _mixed(model, pred, mixing).float().contiguous()
 
-    def _replay(self, model, num_samples, shape, mode, x, table, seed, condition_input, clip_feat, capacity=None, **run):
+    def _replay(self, model, num_samples, shape, mode, x, table, seed, condition_input, clip_feat, capacity=None, keys=None,
+                **run):
         """the graphed branch of every sampler: the captured chain of (model, mode, batch shape) from this object's cache, run
         from x over `table`; seed None: one is drawn with chain.draw_seed() once the chain is there; `run`: GraphedChain.run's
-        keywords.  Returns the final latent."""
+        keywords.  keys (a list of num_samples 64-bit keys) in place of seed: the keyed capture of a mode that draws.
+        Returns the final latent."""
+        keyed = keys is not None and mode in _chain.KEYED_MODES
         ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, self.device, mode,
-                              self._diffusion_steps if capacity is None else capacity)
+                              self._diffusion_steps if capacity is None else capacity, keyed=keyed)
+        if keyed:
+            return ch.run(x, table, keys, condition_input, clip_feat, **run)
         return ch.run(x, table, _chain.draw_seed() if seed is None else seed, condition_input, clip_feat, **run)
+
+    # ---- per-shape seeds (DESIGN.md 4.6.6) ---------------------------------------------------------------------------------
+    @staticmethod
+    def _sample_keys(who, seeds, num_samples, **excluded):
+        """`seeds` of a sampler call as a list of num_samples 64-bit keys (None: None).  ValueError -- before any launch -- on a
+        wrong count, or where one of `excluded` (name=value: the arguments seeds cannot be combined with) is set."""
+        if seeds is None:
+            return None
+        keys = _chain.sample_keys(seeds, num_samples, who)
+        for name, value in excluded.items():
+            if value is not None:
+                raise ValueError(f"{who}: seeds cannot be combined with {name}")
+        return keys
+
+    def _keyed_start(self, keys, num_samples, shape):
+        """the start latent of a keyed chain: sample b under keys[b] at LION_START_STEP_WORD, stream 0"""
+        return diffusion_ops.philox_normal_keyed(keys, num_samples, shape, _chain.START_STEP_WORD, device=self.device)
+
+    def _keyed_step_noise(self, words, num_samples, shape, row):
+        """the z a keyed captured chain draws at table row `row` (stream 0), for the eager loops"""
+        return diffusion_ops.philox_normal_keyed(words, num_samples, shape, int(row), device=self.device)
 
     @torch.no_grad()
     def run_denoising_diffusion(self, model, num_samples, shape, temp=1.0, enable_autocast=False,
                                 is_image=False, prior_var=1.0, condition_input=None, given_noise=None,
                                 clip_feat=None, cls_emb=None, grid_emb=None, graph=True, keep_trajectory=True,
-                                noise_scale=None, conv_precision="fp32"):
+                                noise_scale=None, conv_precision="fp32", *, seeds=None, x_noisy=None):
         """Ancestral DDPM sampling, T model evaluations (reference :224-303).  ``noise_scale(t)`` overrides the
         per-step noise standard deviation sqrt(beta_t) (LION.sample's scheduler variance).
-        conv_precision="half": the denoiser's voxel convolutions run at reduced precision (conv_ops.PRECISION)."""
+        conv_precision="half": the denoiser's voxel convolutions run at reduced precision (conv_ops.PRECISION).
+        seeds: num_samples ints (a sequence or an int64 tensor, each taken mod 2^64), the Philox key of each sample's chain: the
+        step at table row i adds to sample b the noise of counter word i, stream 0, under seeds[b], and the start latent is the
+        draw under the same key at LION_START_STEP_WORD (unless x_noisy, the start in place of a draw, is given).  No draw of
+        the call touches torch's global generators; graph=True (the keyed capture, a cache entry beside the unkeyed one) and
+        graph=False (lion_philox_normal_keyed + lion_ddpm_update) give the same bits.  A sample's NOISE then depends on its
+        seed alone -- not on num_samples, its position, or its batchmates.  Its result is promised bit-equal only at equal
+        num_samples: other batch sizes select other kernel plans in the denoiser (the split 1x1 convolution from 8192 columns,
+        the conv tile plans).  ValueError before any launch: len(seeds) != num_samples, or seeds with given_noise."""
+        keys = self._sample_keys("run_denoising_diffusion", seeds, num_samples, given_noise=given_noise)
+        if x_noisy is not None and given_noise is not None:
+            raise ValueError("run_denoising_diffusion: x_noisy and given_noise both name the start")
         with _sampling(model, conv_precision):
             dev = self.device
             size = [num_samples] + list(shape)
-            x_noisy = torch.randn(size=size, device=dev) if given_noise is None else given_noise[0].to(dev)
+            if x_noisy is not None:
+                x_noisy = x_noisy.to(dev)
+            elif keys is not None:
+                x_noisy = self._keyed_start(keys, num_samples, shape)
+            else:
+                x_noisy = torch.randn(size=size, device=dev) if given_noise is None else given_noise[0].to(dev)
             x_noisy = x_noisy.contiguous()
             output_list = {'pred_x': []}
             kwargs = {'grid_emb': grid_emb} if grid_emb is not None else {}
@@ -387,49 +429,61 @@ class DiffusionDiscretized(object):
             T = self._diffusion_steps
             if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
                 x_image = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, self.ddpm_table(T, temp, noise_scale),
-                                       None, condition_input, clip_feat,
+                                       None, condition_input, clip_feat, keys=keys,
                                        trajectory=output_list['pred_x'] if keep_trajectory else None,
                                        trajectory_before_last=True)
             else:
                 x_image = self._ancestral_steps(model, x_noisy, T, temp, enable_autocast, condition_input, given_noise,
-                                                clip_feat, kwargs, output_list['pred_x'])
+                                                clip_feat, kwargs, output_list['pred_x'], keys=keys)
             if is_image:
                 x_image = (x_image.clamp(min=-1., max=1.) + 1.0) / 2.0
             return x_image, output_list
 
     def _ancestral_steps(self, model, x_noisy, t_from, temp, enable_autocast, condition_input, given_noise, clip_feat, kwargs,
-                         states, generator=None):
+                         states, generator=None, keys=None):
         """the eager ancestral steps t = t_from-1 ... 0 from x_noisy; returns the posterior mean of the step at t = 0.  The noise
         of step t is given_noise[1][t] where given, else a device draw (from `generator` if one is passed).  `states` (a list,
-        or None) receives the state after every step -- for t = 0 the state BEFORE it once more, as the reference reports it."""
+        or None) receives the state after every step -- for t = 0 the state BEFORE it once more, as the reference reports it.
+        keys (one 64-bit key per sample): the step at t draws what the keyed captured chain draws at its table row
+        t_from - 1 - t."""
         dev, size = self.device, list(x_noisy.shape)
         x_image = None
+        words = None if keys is None else _chain.key_words(keys, dev)
         for t in reversed(range(0, t_from)):
             eps_hat = self._eps_hat(model, x_noisy, t + 1, condition_input, clip_feat, enable_autocast, kwargs)
             is0, k_outer, k_a, k_b, scale = self.ddpm_coefficients(t)
             if is0:
                 x_image = diffusion_ops.ddpm_update(x_noisy, eps_hat, None, True, k_outer, k_a, k_b, scale, temp)
             else:
-                z = (torch.randn(size=size, device=dev, generator=generator) if given_noise is None
-                     else given_noise[1][t].to(dev)).contiguous()
+                if words is not None:
+                    z = self._keyed_step_noise(words, size[0], size[1:], t_from - 1 - t)
+                else:
+                    z = (torch.randn(size=size, device=dev, generator=generator) if given_noise is None
+                         else given_noise[1][t].to(dev)).contiguous()
                 x_noisy = diffusion_ops.ddpm_update(x_noisy, eps_hat, z, False, k_outer, k_a, k_b, scale, temp)
             if states is not None:
                 states.append(x_noisy)
         return x_image
 
     # ---- diffuse-denoise: the forward draw at an index, and the reverse chain from there -----------------------------------
-    def diffuse(self, x0, t, noise=None, seed=None, return_noise=False):
+    def diffuse(self, x0, t, noise=None, seed=None, return_noise=False, *, seeds=None):
         """x_t = sqrt(alpha_bar_t) * x0 + sqrt(1 - alpha_bar_t) * z at the schedule INDEX t, 0 <= t <= T-1: what
         ``sample_q`` gives on the quantities of ``iw_quantities_t(B, full(t))`` (reference :44-113; the model's timestep there
         is t + 1).  The two scalars are those expressions on the host copy of the float32 schedule, each operation rounded
         once -- no device synchronisation; a device library's sqrt may differ from them in the last bit -- and the
         draw is one kernel (lion_chain_diffuse): z = ``noise`` if given, else N(0, 1) from the chain's Philox generator under
         ``seed`` (None: one is drawn with chain.draw_seed(), so torch.manual_seed governs it), on a stream of its own, so that
-        a chain run under the same seed repeats none of it.  return_noise: (x_t, z)."""
+        a chain run under the same seed repeats none of it.  return_noise: (x_t, z).
+        seeds: x0.shape[0] ints, one key per sample, in place of noise / seed (ValueError with either, or on a wrong count):
+        sample b's z is drawn under seeds[b] at counters within the sample (lion_chain_diffuse_keyed), so it depends on
+        neither the batch size nor the sample's position; torch's generators are not touched."""
         if not isinstance(t, (int, np.integer)) or isinstance(t, bool) or not 0 <= t <= self._diffusion_steps - 1:
             raise ValueError(f"diffuse: t = {t!r} is not an index in [0, {self._diffusion_steps - 1}]")
+        keys = self._sample_keys("diffuse", seeds, x0.shape[0], noise=noise, seed=seed)
         ab = self._h_alpha_bars[int(t)]
         m, s = float(torch.sqrt(ab)), float(torch.sqrt(1.0 - ab))
+        if keys is not None:
+            return diffusion_ops.diffuse(x0.contiguous(), m, s, seeds=keys, return_noise=return_noise)
         if noise is None and seed is None:
             seed = _chain.draw_seed()
         return diffusion_ops.diffuse(x0.contiguous(), m, s, noise=None if noise is None else noise.contiguous(), seed=seed,
@@ -438,7 +492,7 @@ class DiffusionDiscretized(object):
     @torch.no_grad()
     def run_denoising_diffusion_from_t(self, model, num_samples, shape, time_start, x_noisy, temp=1.0, enable_autocast=False,
                                        is_image=False, prior_var=1.0, condition_input=None, given_noise=None, clip_feat=None,
-                                       graph=True, keep_trajectory=True, conv_precision="fp32", *, seed=None):
+                                       graph=True, keep_trajectory=True, conv_precision="fp32", *, seed=None, seeds=None):
         """The tail of the ancestral chain from ``x_noisy`` (reference :504-563): the steps t = time_start-1 ... 0, the last of
         which returns the posterior mean; 1 <= time_start <= T, and time_start = T is the whole chain from a given start.
         Returns (x, output_list): output_list is the reference's plain list of the state after every step, whose last entry
@@ -450,7 +504,11 @@ class DiffusionDiscretized(object):
         the same cache entry, so a model that has sampled is not captured again -- with the schedule table's last
         time_start rows; the per-step noise is then the chain's Philox stream.
         seed (editing.diffuse_denoise): the 64-bit key of the tail's noise -- the chain's Philox key, or the seed of the eager
-        loop's device generator -- in place of a draw from torch's global generators (graphed: chain.draw_seed())."""
+        loop's device generator -- in place of a draw from torch's global generators (graphed: chain.draw_seed()).
+        seeds: one key per sample, as in run_denoising_diffusion: the tail's row i (t = time_start - 1 - i) adds to sample b the
+        noise of counter word i under seeds[b]; graphed and eager tails give the same bits.  ValueError before any launch:
+        len(seeds) != num_samples, or seeds with seed or given_noise."""
+        keys = self._sample_keys("run_denoising_diffusion_from_t", seeds, num_samples, seed=seed, given_noise=given_noise)
         if isinstance(time_start, bool) or not isinstance(time_start, (int, np.integer)) \
                 or not 0 <= time_start <= self._diffusion_steps:
             raise ValueError(f"run_denoising_diffusion_from_t: time_start = {time_start!r} outside [0, {self._diffusion_steps}]")
@@ -467,18 +525,18 @@ class DiffusionDiscretized(object):
             states = output_list if keep_trajectory else None
             if graph and given_noise is None and _chain.graphable(model, x_noisy, enable_autocast, {}):
                 x = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, self.ddpm_table(int(time_start), temp), seed,
-                                 condition_input, clip_feat, trajectory=states, trajectory_before_last=True)
+                                 condition_input, clip_feat, keys=keys, trajectory=states, trajectory_before_last=True)
             else:
                 gen = None if seed is None else torch.Generator(device=dev).manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
                 x = self._ancestral_steps(model, x_noisy, int(time_start), temp, enable_autocast, condition_input, given_noise,
-                                          clip_feat, {}, states, generator=gen)
+                                          clip_feat, {}, states, generator=gen, keys=keys)
             return x, output_list
 
     @torch.no_grad()
     def run_ddim(self, model, num_samples, shape, temp=1.0, enable_autocast=False, is_image=True,
                  prior_var=1.0, condition_input=None, ddim_step=100, skip_type='uniform', kappa=1.0,
                  clip_feat=None, grid_emb=None, x_noisy=None, dae_index=-1, noise='device',
-                 keep_trajectory=True, graph=True, given_noise=None, state_hook=None, conv_precision="fp32"):
+                 keep_trajectory=True, graph=True, given_noise=None, state_hook=None, conv_precision="fp32", *, seeds=None):
         """DDIM sampling with ``ddim_step`` model evaluations; kappa is DDIM's eta (reference :390-473).
         noise='cpu': EVERY draw of the chain -- the start and the per-step noise -- comes from torch's CPU generator, so
         that one seed gives one chain on any device (the reference draws the per-step noise there, :465-466, and the
@@ -488,12 +546,22 @@ class DiffusionDiscretized(object):
         (device-side launches only; known-region replacement, bench.py's forced clouds).
         conv_precision="half": the supported reduced-precision mode -- the denoiser's voxel convolutions at r = 16 / 32 run
         one fp16 product per operand pair on the project's own kernel, inside the captured chain (conv_ops.PRECISION;
-        DESIGN.md 4.3).  enable_autocast is unrelated to it and keeps its behaviour."""
+        DESIGN.md 4.3).  enable_autocast is unrelated to it and keeps its behaviour.
+        seeds: one key per sample, as in run_denoising_diffusion: the i-th step adds to sample b the noise of counter word i,
+        stream 0, under seeds[b]; the start latent, unless x_noisy is given, is the draw under the same key at
+        LION_START_STEP_WORD.  Graphed (the keyed capture) and eager (lion_philox_normal_keyed + lion_ddim_update) runs give the
+        same bits, and torch's generators are not touched.  A sample's noise depends on its seed alone; its result is promised
+        bit-equal only at equal num_samples (other batch sizes select other kernel plans).  ValueError before any launch:
+        len(seeds) != num_samples, or seeds with given_noise or noise='cpu'."""
+        keys = self._sample_keys("run_ddim", seeds, num_samples, given_noise=given_noise,
+                                 **{"noise='cpu'": True if noise == 'cpu' else None})
         with _sampling(model, conv_precision):
             dev = self.device
             size = [num_samples] + list(shape)
             if given_noise is not None:
                 x_noisy, noise = given_noise[0], 'given'
+            if x_noisy is None and keys is not None:
+                x_noisy = self._keyed_start(keys, num_samples, shape)
             if x_noisy is None:
                 x_noisy = torch.randn(size=size).to(dev) if noise == 'cpu' else torch.randn(size=size, device=dev)
             x_noisy = x_noisy.to(dev).contiguous()
@@ -502,9 +570,10 @@ class DiffusionDiscretized(object):
             output_list = []
             if graph and noise == 'device' and _chain.graphable(model, x_noisy, enable_autocast, kwargs):
                 x_noisy = self._replay(model, num_samples, shape, _chain.DDIM, x_noisy, self.ddim_table(steps, kappa), None,
-                                       condition_input, clip_feat, trajectory=output_list if keep_trajectory else None,
+                                       condition_input, clip_feat, keys=keys, trajectory=output_list if keep_trajectory else None,
                                        state_hook=state_hook)
                 return x_noisy, output_list
+            words = None if keys is None else _chain.key_words(keys, dev)
             for i, t in enumerate(steps):
                 last = i == len(steps) - 1
                 if last:
@@ -516,6 +585,8 @@ class DiffusionDiscretized(object):
                 # the reference draws (and adds, scaled by sigma == 0) noise on the last step as well
                 if noise == 'given':
                     z = given_noise[1][i].to(dev).contiguous() if sigma != 0.0 else None
+                elif words is not None:
+                    z = self._keyed_step_noise(words, num_samples, shape, i) if sigma != 0.0 else None
                 else:
                     z = self._noise(size, noise, dev).contiguous() if (sigma != 0.0 or noise == 'cpu') else None
                 x_noisy = diffusion_ops.ddim_update(x_noisy, eps_hat, z if sigma != 0.0 else None, s, c, sigma)
@@ -526,7 +597,7 @@ class DiffusionDiscretized(object):
     @torch.no_grad()
     def run_dpm_solver(self, model, num_samples, shape, steps=20, order=2, skip_type='logsnr', x_noisy=None,
                        condition_input=None, clip_feat=None, enable_autocast=False, keep_trajectory=True, graph=True,
-                       state_hook=None, conv_precision="fp32", stochastic=False, t_start=None, seed=None):
+                       state_hook=None, conv_precision="fp32", stochastic=False, t_start=None, seed=None, *, seeds=None):
         """Deterministic few-step sampling with DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2): the second-order multistep
         solver of the probability-flow ODE that run_ddim(kappa=0) integrates to first order.  At most ``steps`` model
         evaluations (solver_schedule removes duplicate indices), one per visited index of
@@ -549,15 +620,25 @@ class DiffusionDiscretized(object):
         words and stream: from the same start and seed the two give the same bits.
         t_start (an index in 1 ... T-1; needs x_noisy, else ValueError): the tail of the chain from x_noisy, taken as a draw
         of the marginal at index t_start (DiffusionDiscretized.diffuse(x0, t_start)), over
-        solver_schedule(steps, skip_type, t_start).  Either solver runs it."""
+        solver_schedule(steps, skip_type, t_start).  Either solver runs it.
+        seeds: one key per sample in place of seed, as in run_denoising_diffusion: the start latent, unless x_noisy is given, is
+        sample b's draw under seeds[b] at LION_START_STEP_WORD, and with stochastic=True row i adds the noise of counter word i,
+        stream 0, under seeds[b] (the keyed chain.SDE_DPMPP capture, or eagerly lion_philox_normal_keyed +
+        lion_sde_dpmpp_update(noise=z): the same bits).  The deterministic solver draws nothing after the start and replays its
+        existing capture.  torch's generators are not touched.  A sample's noise depends on its seed alone; its result is
+        promised bit-equal only at equal num_samples (other batch sizes select other kernel plans).  ValueError before any
+        launch: len(seeds) != num_samples, or seeds with seed."""
+        keys = self._sample_keys("run_dpm_solver", seeds, num_samples, seed=seed)
         if t_start is not None and x_noisy is None:
             raise ValueError("run_dpm_solver: t_start needs x_noisy, the state at that index")
         taus = self.solver_schedule(steps, skip_type, t_start)
         table = self.dpm_solver_table(taus, order, stochastic=bool(stochastic))
-        if stochastic:
+        if stochastic and keys is None:
             seed = _chain.draw_seed() if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
         with _sampling(model, conv_precision):
             dev = self.device
+            if x_noisy is None and keys is not None:
+                x_noisy = self._keyed_start(keys, num_samples, shape)
             if x_noisy is None:
                 x_noisy = torch.randn(size=[num_samples] + list(shape), device=dev)
             x_noisy = x_noisy.to(dev).contiguous()
@@ -565,15 +646,20 @@ class DiffusionDiscretized(object):
             if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
                 x = self._replay(model, num_samples, shape, _chain.SDE_DPMPP if stochastic else _chain.DPMPP, x_noisy, table,
                                  seed if stochastic else 0, condition_input, clip_feat,   # 0: the deterministic step draws nothing
+                                 keys=keys if stochastic else None,
                                  trajectory=output_list if keep_trajectory else None, state_hook=state_hook)
                 return x, output_list
             x, hist = x_noisy.clone(), None     # the hook may overwrite the latent in place: never the caller's tensor
-            words = diffusion_ops.seed_words(seed, dev) if stochastic else None
+            keyed = stochastic and keys is not None
+            words = (_chain.key_words(keys, dev) if keyed else diffusion_ops.seed_words(seed, dev)) if stochastic else None
             for i, t in enumerate(taus):
                 if state_hook is not None:
                     state_hook(i, x)
                 eps_hat = self._eps_hat(model, x, t + 1, condition_input, clip_feat, enable_autocast, {})
-                if stochastic:   # step i of the captured chain: counter word i, stream 0
+                if keyed:        # row i of the keyed chain: counter word i, stream 0, under each sample's key; a6 == 0 draws nothing
+                    z = self._keyed_step_noise(words, num_samples, shape, i) if table[i, 7] != 0 else None
+                    x, hist = diffusion_ops.sde_dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:8]], noise=z)
+                elif stochastic:   # step i of the captured chain: counter word i, stream 0
                     x, hist = diffusion_ops.sde_dpmpp_update(x, eps_hat, hist, *[float(v) for v in table[i, 1:8]], seed=words,
                                                              step=i)
                 else:

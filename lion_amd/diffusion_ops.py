@@ -1,12 +1,14 @@
 """Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, the multistep solver
 step lion_dpmpp_update and its stochastic form lion_sde_dpmpp_update, the deterministic encoder's row lion_ddim_encode_update,
-and the forward-process draw lion_chain_diffuse."""
+the forward-process draw lion_chain_diffuse, and the per-sample-key draws lion_philox_normal_keyed / lion_chain_diffuse_keyed."""
 import numpy as np
 import torch
 
 from . import _lib
+from .chain import key_words, sample_keys
 
-__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "sde_dpmpp_update", "ddim_encode_update", "diffuse"]
+__all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "sde_dpmpp_update", "ddim_encode_update", "diffuse",
+           "philox_normal_keyed"]
 
 
 def ddim_update(x, eps, z, s, c, sigma, out=None):
@@ -23,10 +25,52 @@ def seed_words(seed, device):
     return torch.from_numpy(words).to(device)
 
 
-def diffuse(x0, m, s, noise=None, seed=None, stream_id=1, out=None, return_noise=False):
+def _device_keys(keys, num_samples, device, who):
+    """per-sample keys as the device words the keyed kernels read: an int32[B, 2] device tensor passes (a loop uploads its keys
+    once), anything else goes through chain.sample_keys (ValueError on a wrong count)"""
+    if isinstance(keys, torch.Tensor) and keys.dtype == torch.int32 and keys.dim() == 2:
+        if tuple(keys.shape) != (num_samples, 2):
+            raise ValueError(f"{who}: key words {tuple(keys.shape)} for {num_samples} samples")
+        return keys
+    return key_words(sample_keys(keys, num_samples, who), device)
+
+
+def philox_normal_keyed(keys, num_samples, shape, step, stream_id=0, device="cuda", out=None):
+    """z [num_samples] + shape with z[b] ~ N(0, 1) drawn by the chain's Philox generator under the 64-bit key keys[b] at counter
+    (quad within the sample, `step`, stream_id) (lion_philox_normal_keyed): what a keyed chain draws for sample b at that step
+    word, and what the single-seed kernels draw for ONE sample of this shape under seed keys[b] -- whatever num_samples, b and
+    the other keys are.  keys: num_samples ints (a sequence or tensor), or their device words (chain.key_words).  The
+    elements of one sample must be a multiple of 4.  step = chain.START_STEP_WORD is the start latent of a keyed chain."""
+    size = [int(num_samples)] + list(shape)
+    n = int(np.prod(shape))
+    if n <= 0 or n % 4 != 0:
+        raise ValueError(f"philox_normal_keyed: {n} elements per sample, must be a positive multiple of 4")
+    out = torch.empty(size, device=device) if out is None else out
+    _lib.require_cuda(out)
+    words = _device_keys(keys, num_samples, out.device, "philox_normal_keyed")
+    _lib.call("lion_philox_normal_keyed", words, int(num_samples), n, int(step), int(stream_id), out)
+    return out
+
+
+def diffuse(x0, m, s, noise=None, seed=None, stream_id=1, out=None, return_noise=False, seeds=None):
     """out = m*x0 + s*z, the forward-process draw (utils/diffusion_pvd.py:105-113).  z = `noise` if given, else N(0, 1) drawn
     in the kernel by the chain's Philox generator under the 64-bit `seed` (lion_chain_diffuse; stream_id 1 keeps the draw apart
-    from every step's noise of a chain run under the same seed, which uses stream 0).  out may be x0."""
+    from every step's noise of a chain run under the same seed, which uses stream 0).  out may be x0.
+    seeds (instead of noise / seed): one key per sample x0[b]; sample b's z is drawn under seeds[b] at counters within the sample
+    (lion_chain_diffuse_keyed), so it does not depend on the batch it sits in."""
+    if seeds is not None:
+        if noise is not None or seed is not None:
+            raise ValueError("diffuse: seeds excludes noise and seed")
+        B = x0.shape[0]
+        words = _device_keys(seeds, B, x0.device, "diffuse")
+        _lib.require_cuda(x0, out)
+        n = x0.numel() // max(B, 1)
+        if n <= 0 or n % 4 != 0:
+            raise ValueError(f"diffuse: {n} elements per sample, keyed noise needs a positive multiple of 4")
+        out = torch.empty_like(x0) if out is None else out
+        z_out = torch.empty_like(x0) if return_noise else None
+        _lib.call("lion_chain_diffuse_keyed", x0, B, n, float(m), float(s), words, int(stream_id), out, z_out)
+        return (out, z_out) if return_noise else out
     _lib.require_cuda(x0, noise, out)
     if noise is None and seed is None:
         raise ValueError("diffuse: either noise or seed")

@@ -15,25 +15,16 @@ import numbers
 import torch
 
 from . import chain as _chain
+from . import diffusion_ops
+from .chain import split_seed as _split_seed   # SplitMix64: one seed -> a key per draw (shared with sampling.py)
 
 _MASK64 = 0xFFFFFFFFFFFFFFFF
-
-
-def _split_seed(seed: int, n: int):
-    """n 64-bit keys from one (SplitMix64, Steele et al. 2014): one call's seed -> a key per draw"""
-    out, state = [], seed & _MASK64
-    for _ in range(n):
-        state = (state + 0x9E3779B97F4A7C15) & _MASK64
-        z = state
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
-        out.append(z ^ (z >> 31))
-    return out
+SUBKEYS = ("vae", "diffuse_global", "chain_global", "diffuse_local", "chain_local")   # the order a seed is split in
 
 
 @torch.no_grad()
 def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=None, keep_first=False, graph=True,
-                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True):
+                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True, seeds=None):
     """x [B, N, 3] -> (points [B, N, 3], info).  vae: models.vae_adain.Model (in the mode the caller wants: eval() for
     inference); dae: [global prior, local prior]; diffusion: DiffusionDiscretized.
 
@@ -63,7 +54,14 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     which stays with the ancestral tail.  stochastic=True (default) is SDE-DPM-Solver++(2M), whose steps draw fresh noise
     as the ancestral steps do; False is the deterministic solver, which only transports the perturbation of the forward draw.
     keep_first, conv_precision, graph and time_start = 0 behave as in the ancestral tail; temp scales the ancestral steps'
-    noise only, the solver has no such knob."""
+    noise only, the solver has no such knob.
+    seeds: B ints (a sequence or an int64 tensor, each mod 2^64) in place of `seed`, one per sample: "variation #5 again".
+    Sample b's seed is split (SplitMix64) into the five keys of SUBKEYS, and every draw of sample b -- the two
+    reparameterisation draws (streams 0 and 1 of lion_philox_normal_keyed under 'vae'), the two forward draws, the two tails'
+    per-step noise -- comes from its own keys at counters within the sample: it depends on neither B, nor b, nor the other
+    samples' seeds, and torch's generators are not touched.  The output for a seed is promised bit-equal at equal B only
+    (other batch sizes select other kernel plans).  info['seeds'] then holds 'seeds' (the list) and a list per sub-key.
+    ValueError before any launch: len(seeds) != B, or seeds with seed."""
     T = diffusion._diffusion_steps
     pair = tuple(time_start) if isinstance(time_start, (tuple, list)) else (time_start, time_start)
     if len(pair) != 2 or any(isinstance(t, bool) or not isinstance(t, numbers.Integral) or not 0 <= t <= T - 1 for t in pair):
@@ -73,34 +71,54 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
                                      or solver_steps < 2):
         raise ValueError(f"diffuse_denoise: solver_steps = {solver_steps!r}: None or an int >= 2")
     visited = [[], []]
+    names = SUBKEYS
+    keyed = seeds is not None
+    if keyed:
+        if seed is not None:
+            raise ValueError("diffuse_denoise: seeds cannot be combined with seed")
+        per_sample = _chain.sample_keys(seeds, x.shape[0], "diffuse_denoise")
     if not x.is_cuda:
         raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
-    base = _chain.draw_seed() if seed is None else int(seed) & _MASK64
-    names = ("vae", "diffuse_global", "chain_global", "diffuse_local", "chain_local")
-    seeds = dict(zip(names, _split_seed(base, len(names))), seed=base)
-    gen = torch.Generator(device=x.device).manual_seed(seeds["vae"] & 0x7FFFFFFFFFFFFFFF)
     B, shapes = x.shape[0], vae.latent_shape()
+    if keyed:
+        split = [_split_seed(k, len(names)) for k in per_sample]
+        seeds = {name: [sp[j] for sp in split] for j, name in enumerate(names)}
+        seeds["seeds"] = per_sample
+        vae_words = _chain.key_words(seeds["vae"], x.device)
+        draws = iter((0, 1))
 
-    def sample(dist):   # Normal.sample() on a generator of this call
-        return dist.sample_given_rho(torch.randn(dist.mu.shape, device=dist.mu.device, dtype=dist.mu.dtype, generator=gen))
+        def sample(dist):   # Normal.sample() on each sample's own key: stream 0 for the global latent, 1 for the local
+            rho = diffusion_ops.philox_normal_keyed(vae_words, B, list(dist.mu.shape[1:]), _chain.START_STEP_WORD,
+                                                    stream_id=next(draws), device=dist.mu.device)
+            return dist.sample_given_rho(rho.to(dist.mu.dtype))
+    else:
+        base = _chain.draw_seed() if seed is None else int(seed) & _MASK64
+        seeds = dict(zip(names, _split_seed(base, len(names))), seed=base)
+        gen = torch.Generator(device=x.device).manual_seed(seeds["vae"] & 0x7FFFFFFFFFFFFFFF)
+
+        def sample(dist):   # Normal.sample() on a generator of this call
+            return dist.sample_given_rho(torch.randn(dist.mu.shape, device=dist.mu.device, dtype=dist.mu.dtype, generator=gen))
+
+    def key(name):   # the call's key of that draw, or (seeds) every sample's
+        return {"seeds" if keyed else "seed": seeds[name]}
 
     def edit(i, eps_ori, condition_input):
         if pair[i] == 0:
             return eps_ori
         which = ("global", "local")[i]
-        eps_t = diffusion.diffuse(eps_ori, pair[i], seed=seeds["diffuse_" + which])
+        eps_t = diffusion.diffuse(eps_ori, pair[i], **key("diffuse_" + which))
         if solver_steps is not None:
             visited[i] = diffusion.solver_schedule(int(solver_steps), 'logsnr', pair[i])
             eps, _ = diffusion.run_dpm_solver(dae[i], B, shapes[i], steps=int(solver_steps), x_noisy=eps_t,
                                               condition_input=condition_input, clip_feat=clip_feat, keep_trajectory=False,
                                               graph=graph, conv_precision=conv_precision, stochastic=stochastic,
-                                              t_start=pair[i], seed=seeds["chain_" + which])
+                                              t_start=pair[i], **key("chain_" + which))
         else:
             visited[i] = list(range(pair[i] - 1, -1, -1))
             eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp=temp,
                                                               condition_input=condition_input, clip_feat=clip_feat, graph=graph,
                                                               keep_trajectory=False, conv_precision=conv_precision,
-                                                              seed=seeds["chain_" + which])
+                                                              **key("chain_" + which))
         if keep_first:
             eps[0:1] = eps_ori[0:1]
         return eps.contiguous()

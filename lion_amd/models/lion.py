@@ -74,13 +74,21 @@ class LION(object):
         print(f'INFO finish loading from {model_path}')
 
     @torch.no_grad()
-    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32", dpm_step=0, dpm_stochastic=False):
+    def sample(self, num_samples=10, clip_feat=None, save_img=False, conv_precision="fp32", dpm_step=0, dpm_stochastic=False,
+               seeds=None):
         """1000 ancestral steps of the global prior, 1000 of the local prior, one decode
         (reference :38-80).  conv_precision="half": the priors' voxel convolutions run at reduced precision
         (conv_ops.PRECISION); the decode stays fp32-accurate.
         dpm_step > 0: both priors run DPM-Solver++(2M) with at most dpm_step evaluations instead of the ancestral steps
         (DiffusionDiscretized.run_dpm_solver), dpm_stochastic=True its stochastic form; the default is the reference's
-        chain."""
+        chain.
+        seeds: num_samples ints, one per shape, split and used as in sampling.generate_samples_vada_2prior(seeds=...): shape b's
+        start latents and per-step noise depend on seeds[b] alone and torch's generators are not touched; the points are
+        promised bit-equal only at equal num_samples (other batch sizes select other kernel plans).  output_dict['seeds']
+        reports the seeds and their sub-keys.  ValueError on a wrong count."""
+        from ..sampling import split_sample_seeds
+        from .. import chain as _chain
+        sub = None if seeds is None else split_sample_seeds(seeds, num_samples, who="LION.sample")
         self.priors.eval()
         self.vae.eval()
         self.scheduler.set_timesteps(self.diffusion._diffusion_steps, device=self.device)
@@ -91,20 +99,26 @@ class LION(object):
         condition_input = None
         for prior, shp, key in ((global_prior, latent_shape[0], 'z_global'),
                                 (local_prior, latent_shape[1], 'z_local')):
+            keyed = {} if sub is None else dict(
+                seeds=sub["chain_" + key[2:]],
+                x_noisy=diffusion_ops.philox_normal_keyed(sub["start_" + key[2:]], num_samples, shp, _chain.START_STEP_WORD,
+                                                          device=self.device))
             # the reference's loop (:55-70: prior forward + scheduler.step per timestep) as one graphed chain:
             # the scheduler's mean / variance rule feeds the chain's coefficient table (lion_amd/chain.py)
             if dpm_step > 0:
                 x, _ = self.diffusion.run_dpm_solver(prior, num_samples, shp, steps=dpm_step, condition_input=condition_input,
                                                      clip_feat=clip_feat, keep_trajectory=False, conv_precision=conv_precision,
-                                                     stochastic=dpm_stochastic)
+                                                     stochastic=dpm_stochastic, **keyed)
             else:
                 x, _ = self.diffusion.run_denoising_diffusion(
                     prior, num_samples, shp, condition_input=condition_input, clip_feat=clip_feat,
-                    keep_trajectory=False, noise_scale=self.scheduler._noise_scale, conv_precision=conv_precision)
+                    keep_trajectory=False, noise_scale=self.scheduler._noise_scale, conv_precision=conv_precision, **keyed)
             prior.eval()
             sampled.append(x)
             output_dict[key] = x
             if condition_input is None:
                 condition_input = self.vae.global2style(x)
+        if sub is not None:
+            output_dict['seeds'] = sub
         output_dict['points'] = self.vae.sample(num_samples=num_samples, decomposed_eps=sampled)
         return output_dict
