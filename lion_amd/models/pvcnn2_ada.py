@@ -269,41 +269,78 @@ def route_1x1_convs(module):
     return module
 
 
-def run_layers(layers, x, style, conv, reduce_max=False):
-    """the generic (training / non-fused) walk over [conv, AdaGN, Swish, ...] layer lists.  With gradients enabled on the
-    GPU an AdaGN (and the Swish behind it, when there is one) is ONE differentiable op on the library's kernels
-    (lion_amd/train_ops.py: two passes forward, three backward, instead of ATen's five and ten).
+def _group_norm(layer, adaptive):
+    """the nn.GroupNorm of a norm layer the training ops (lion_amd/train_ops.py) can stand in for, else None: an AdaGN's in the
+    adaptive blocks, an affine nn.GroupNorm itself in the plain ones (models/pvcnn2.py) -- neither takes the other's"""
+    if adaptive:
+        return layer.norm if isinstance(layer, AdaGN) and layer.n_channel <= 1024 else None
+    return layer if isinstance(layer, nn.GroupNorm) and layer.affine and layer.num_channels <= 1024 else None
+
+
+def walk(layers, x, style, conv, reduce_max, adaptive):
+    """the generic (training / non-fused) walk over [conv, norm, Swish, Dropout, ..., SE3d] layer lists.  On the GPU in fp32 a
+    norm layer (and the Swish and the Dropout behind it, when there are) is ONE differentiable op on the library's kernels
+    (train_ops.adagn_act: two passes forward, three backward, instead of ATen's five and ten), norm -> SE3d is one
+    (train_ops.adagn_se), an SE3d alone is train_ops.se3d.
     reduce_max: additionally the max over the last axis of the result (the SA modules' pooling); when the list ends in
-    AdaGN + Swish on a [B, C, M, U] activation that pooling is part of the same op (train_ops.adagn_act_max, round 6)."""
+    norm (+ Swish) on a [B, C, M, U] activation that pooling is part of the same op (train_ops.adagn_act_max, round 6).
+    adaptive (run_layers below): the norm layers are AdaGN, whose affine(style) is asked exactly once per layer and before the
+    branch is chosen (adagn.StylePlan records who asks); the ops need autograd (without it the modules run: inference has fused
+    paths of its own); every Conv1d / Conv2d / Conv3d goes to `conv`.  Not adaptive (models/pvcnn2.py run_layers): affine
+    nn.GroupNorm with factor = bias = None; the ops also run forward-only (these blocks have no fused inference path: the frozen
+    VAE's encode inside a prior training step); only Conv3d goes to `conv`, Conv1d / Conv2d are called as modules."""
     from .. import train_ops
+    need_grad = adaptive
+    convs = (nn.Conv1d, nn.Conv2d, nn.Conv3d) if adaptive else nn.Conv3d
     i, n = 0, len(layers)
     while i < n:
         layer = layers[i]
-        if isinstance(layer, AdaGN):
-            if train_ops.usable(x) and layer.n_channel <= 1024:
-                fused_act = i + 1 < n and isinstance(layers[i + 1], Swish)
-                factor, bias = layer.affine(style)
-                if (not fused_act and i + 1 < n and isinstance(layers[i + 1], SE3d) and x.dim() == 5
-                        and train_ops.se3d_trainable(layers[i + 1], x)):
-                    x = train_ops.adagn_se(x, layer.norm, factor, bias, layers[i + 1])   # AdaGN -> SE3d, nothing between: one op
-                    i += 2
-                    continue
-                if reduce_max and i + (2 if fused_act else 1) == n and train_ops.adagn_act_max_usable(x):
-                    return train_ops.adagn_act_max(x, layer.norm, factor, bias, act=fused_act)   # pooled: [B, C, M]
-                i += 2 if fused_act else 1
-                drop_p, used = train_ops.fusable_dropout(layers, i) if fused_act else (0.0, 0)   # Swish -> Dropout (PVConv :211-222)
-                x = train_ops.adagn_act(x, layer.norm, factor, bias, act=fused_act, dropout_p=drop_p)
-                i += used
+        norm = _group_norm(layer, adaptive)
+        if norm is not None and train_ops.usable(x, need_grad):
+            fused_act = i + 1 < n and isinstance(layers[i + 1], Swish)
+            factor, bias = layer.affine(style) if adaptive else (None, None)
+            if (not fused_act and i + 1 < n and isinstance(layers[i + 1], SE3d) and x.dim() == 5
+                    and train_ops.se3d_trainable(layers[i + 1], x, need_grad)):
+                x = train_ops.adagn_se(x, norm, factor, bias, layers[i + 1])   # norm -> SE3d, nothing between: one op
+                i += 2
                 continue
+            if reduce_max and i + (2 if fused_act else 1) == n and train_ops.adagn_act_max_usable(x, need_grad):
+                return train_ops.adagn_act_max(x, norm, factor, bias, act=fused_act)   # pooled: [B, C, M]
+            i += 2 if fused_act else 1
+            drop_p, used = train_ops.fusable_dropout(layers, i) if fused_act else (0.0, 0)   # Swish -> Dropout (PVConv :211-222)
+            x = train_ops.adagn_act(x, norm, factor, bias, act=fused_act, dropout_p=drop_p)
+            i += used
+            continue
+        if adaptive and isinstance(layer, AdaGN):
             x = layer(x, style)
-        elif isinstance(layer, (nn.Conv1d, nn.Conv2d, nn.Conv3d)):
+        elif isinstance(layer, convs):
             x = conv(layer, x)
-        elif isinstance(layer, SE3d) and train_ops.se3d_trainable(layer, x):
+        elif isinstance(layer, SE3d) and train_ops.se3d_trainable(layer, x, need_grad):
             x = train_ops.se3d(layer, x)     # one differentiable op on the library's kernels (round 6)
         else:
             x = layer(x)
         i += 1
     return x.max(dim=-1).values if reduce_max else x
+
+
+def run_layers(layers, x, style, conv, reduce_max=False):
+    """the walk of the adaptive blocks"""
+    return walk(layers, x, style, conv, reduce_max, adaptive=True)
+
+
+def voxel_tail(layers, grid, style, voxel_coords, resolution, training, adaptive):
+    """the voxel branch of a PVConv behind its voxelisation, layer by layer: `layers` over the grid, then the devoxelisation ->
+    (point features [B, C, N], the grid that was devoxelised).  In training a list that ends in norm -> SE3d hands those two and
+    the devoxelisation to ONE op (train_ops.adagn_se_devox: no gated grid, no dense gradient of the devoxelisation) -- the grid
+    returned is then None: it does not exist."""
+    from .. import train_ops
+    norm = _group_norm(layers[-2], adaptive) if training and len(layers) >= 2 and isinstance(layers[-1], SE3d) else None
+    if norm is not None and train_ops.usable(grid) and train_ops.adagn_se_devox_usable(grid, layers[-1]):
+        grid = walk(layers[:-2], grid, style, conv3d_module, False, adaptive)
+        factor, bias = layers[-2].affine(style) if adaptive else (None, None)
+        return train_ops.adagn_se_devox(grid, norm, factor, bias, layers[-1], voxel_coords, resolution), None
+    grid = walk(layers, grid, style, conv3d_module, False, adaptive)  # convs: fp32-MFMA implicit GEMM (csrc/conv3d.hip)
+    return F.trilinear_devoxelize(grid, voxel_coords, resolution, training), grid
 
 
 class SharedMLP(nn.Module):
@@ -481,17 +518,7 @@ class PVConv(nn.Module):
             if self.attn is not None:
                 fused = self.attn(fused)
             return fused, coords_input, time_emb, style
-        layers = list(self.voxel_layers)
-        from .. import train_ops
-        if (self.training and len(layers) >= 2 and isinstance(layers[-1], SE3d) and isinstance(layers[-2], AdaGN)
-                and train_ops.usable(grid) and layers[-2].n_channel <= 1024 and train_ops.adagn_se_devox_usable(grid, layers[-1])):
-            # ... AdaGN -> SE3d -> devoxelize: one op, no gated grid, no dense gradient of the devoxelisation (train_ops._AdaGNSEDevox)
-            grid = run_layers(layers[:-2], grid, style, conv3d_module)
-            factor, bias = layers[-2].affine(style)
-            fused = train_ops.adagn_se_devox(grid, layers[-2].norm, factor, bias, layers[-1], voxel_coords, self.resolution)
-        else:
-            grid = run_layers(layers, grid, style, conv3d_module)  # convs: fp32-MFMA implicit GEMM (csrc/conv3d.hip)
-            fused = F.trilinear_devoxelize(grid, voxel_coords, self.resolution, self.training)
+        fused, grid = voxel_tail(list(self.voxel_layers), grid, style, voxel_coords, self.resolution, self.training, adaptive=True)
         if self.add_point_feat:
             fused = fused + self.point_features(features, style)
         if self.attn is not None:

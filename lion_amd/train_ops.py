@@ -5,6 +5,11 @@
 x, norm.weight, norm.bias, factor, bias.  ATen evaluates that expression in five passes over the activation forward and
 about ten backward; here the forward is two passes (row sums; one fused apply) and the backward three (row sums of the
 activation gradient; one fused apply) plus one small kernel per direction for the [B, C] scalar algebra (double inside).
+
+``adagn_act``, ``adagn_act_max``, ``adagn_se`` and ``adagn_se_devox`` are ONE autograd.Function (``_AdaGNOp``): the shell -- fold
+head, optional SE gate, what is saved, the backward's [B, C] algebra, gradient slots -- exists once, and each op is a record of
+its three passes over the activation (output, row sums S, dx) and of the tensors it alone keeps (``_Act`` ... ``_SEDevox``).
+The walk over a layer list that picks among them, and the PVConv tail, are models/pvcnn2_ada.py ``walk`` / ``voxel_tail``.
 """
 import os
 
@@ -146,7 +151,7 @@ def _fold_head(x, gw, gb, factor, bias, groups, eps):
 
 def _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A=None, stats=None, g=None, Qse=None):
     """the GroupNorm backward's [B, C] algebra from the row sums S -> (Q, R, d factor, d bias, pw for _param_grads, Aout);
-    g / Qse (the SE gate and its gradient term, _AdaGNSE / _AdaGNSEDevox) fold the gate in and give Aout = A g, else None"""
+    g / Qse (the SE gate and its gradient term, _SE / _SEDevox) fold the gate in and give Aout = A g, else None"""
     B, C = mean.shape
     dev = mean.device
     Q, R = torch.empty(B, C, device=dev, dtype=torch.float32), torch.empty(B, C, device=dev, dtype=torch.float32)
@@ -192,95 +197,70 @@ def _unbroadcast(g, shape):
     return g.sum_to_size(core if core else (1,)).reshape(shape)
 
 
-class _AdaGNAct(torch.autograd.Function):
+_AFFINE_ACT = {"out": ("lion_affine_act", "lion_affine_act_dropout"),
+               "sums": ("lion_affine_act_bwd_stats", "lion_affine_act_dropout_bwd_stats"),
+               "dx": ("lion_affine_act_bwd_apply", "lion_affine_act_dropout_bwd_apply")}
+
+
+def _affine_act(stage, seed, drop_p, *args):
+    """one pass of y = dropout(act(A x + Bs)) over the rows of x -- args: the tensors, rows, L, act, and last the output.  With a
+    seed, nn.Dropout rides on the pass: the mask comes from a seed torch's generator draws on the device (a replayed graph draws
+    a new one) and is regenerated by both backward passes -- it is never stored"""
+    if seed.numel():
+        _lib.call(_AFFINE_ACT[stage][1], *args[:-1], seed, 1.0 - drop_p, args[-1])
+    else:
+        _lib.call(_AFFINE_ACT[stage][0], *args)
+
+
+# What is an op's own, for the shell _AdaGNOp below -- out(x, A, Bs, p, aux) -> (y, the tensors it alone keeps), with A, Bs the
+# affine per (sample, channel) in front of the activation (gate folded in); sums(x, gy, A, Bs, p, kept, S): S = the two row sums the
+# [B, C] algebra of the backward starts from; dx(x, gy, A, Bs, Q, R, p, kept, dx).  p: the op's Python scalars; aux: a tensor input
+# that gets no gradient.  gate: an SE gate behind the norm; keeps_stats: the double row sums of x are saved (gate ops always do).
+
+class _Act:
+    """adagn_act.  p = (act, dropout p); keeps the dropout seed (empty without dropout) and, for the sum of dx per channel that a
+    voxel grid's backward hands to the Conv3d in front, the row sums of x"""
+    gate, keeps_stats = False, True
+
     @staticmethod
-    def forward(ctx, x, gw, gb, factor, bias, groups, eps, act, drop_p=0.0):
-        x = x.contiguous()
-        B, C = x.shape[:2]
-        L = x[0, 0].numel()
-        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
+    def out(x, A, Bs, p, aux):
         y = torch.empty_like(x)
-        keep = 1.0 - float(drop_p)
-        if drop_p > 0.0:
-            # nn.Dropout behind the activation, in the same pass: the mask comes from a seed torch's generator draws on the device
-            # (a replayed graph draws a new one) and is regenerated by the backward passes -- it is never stored
-            seed = torch.empty(1, device=x.device, dtype=torch.int64).random_()
-            _lib.call("lion_affine_act_dropout", x, A, Bs, B * C, L, int(act), seed, keep, y)
-        else:
-            seed = x.new_empty(0)
-            _lib.call("lion_affine_act", x, A, Bs, B * C, L, int(act), y)
-        ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0), seed, stats)
-        ctx.meta = (groups, int(act), factor is not None, bias is not None, fs,
-                    None if factor is None else factor.shape, None if bias is None else bias.shape, keep)
-        return y
+        seed = torch.empty(1, device=x.device, dtype=torch.int64).random_() if p[1] > 0.0 else x.new_empty(0)
+        _affine_act("out", seed, p[1], x, A, Bs, x.shape[0] * x.shape[1], x[0, 0].numel(), p[0], y)
+        return y, (seed,)
 
     @staticmethod
-    @once_differentiable   # raw kernels: a double backward must raise, not silently treat these gradients as constants
-    def backward(ctx, gy):
-        x, A, Bs, mean, rstd, gwc, gbc, f, seed, stats = ctx.saved_tensors
-        groups, act, has_f, has_b, fs, f_shape, b_shape, keep = ctx.meta
-        drop = seed.numel() > 0
-        gy = gy.contiguous()
-        B, C = x.shape[:2]
-        L = x[0, 0].numel()
-        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
-        if drop:
-            _lib.call("lion_affine_act_dropout_bwd_stats", x, gy, A, Bs, B * C, L, act, seed, keep, S)
-        else:
-            _lib.call("lion_affine_act_bwd_stats", x, gy, A, Bs, B * C, L, act, S)
-        Q, R, dfac, dbias, pw, _ = _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A, stats)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            if drop:
-                _lib.call("lion_affine_act_dropout_bwd_apply", x, gy, A, Bs, Q, R, B * C, L, act, seed, keep, dx)
-            else:
-                _lib.call("lion_affine_act_bwd_apply", x, gy, A, Bs, Q, R, B * C, L, act, dx)
-        # d norm.weight, d norm.bias; for a voxel grid also the sum of dx per channel = the bias gradient of the Conv3d in front
-        dgw, dgb, dxs = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], dx is not None and x.dim() == 5)
-        if dxs is not None:
-            tag_channel_sum(dx, dxs)
-        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
-        return dx, dgw, dgb, dfac, dbias, None, None, None, None
+    def sums(x, gy, A, Bs, p, kept, S):
+        _affine_act("sums", kept[0], p[1], x, gy, A, Bs, x.shape[0] * x.shape[1], x[0, 0].numel(), p[0], S)
+
+    @staticmethod
+    def dx(x, gy, A, Bs, Q, R, p, kept, dx):
+        _affine_act("dx", kept[0], p[1], x, gy, A, Bs, Q, R, x.shape[0] * x.shape[1], x[0, 0].numel(), p[0], dx)
 
 
-class _AdaGNActMax(torch.autograd.Function):
-    """max over the last (neighbour) axis of act(GroupNorm(x) * factor + bias) for x [B, C, M, U] -> [B, C, M]: _AdaGNAct with
-    the set-abstraction pooling (reference pvcnn2_ada.py:375-377) folded in.  Forward: row sums + one pass that writes [B, C, M]
+class _ActMax:
+    """adagn_act_max: max over the last (neighbour) axis of act(GroupNorm(x) * factor + bias) for x [B, C, M, U] -> [B, C, M]: _Act
+    with the set-abstraction pooling (reference pvcnn2_ada.py:375-377) folded in.  Forward: row sums + one pass that writes [B, C, M]
     only; backward: one reduction + one pass writing dx -- the activated [B, C, M, U] tensor and its (one-hot per group) gradient
-    are never materialised (csrc/norm_train.hip, round 6)."""
+    are never materialised (csrc/norm_train.hip, round 6).  p = (act,); keeps nothing of its own."""
+    gate, keeps_stats = False, False
 
     @staticmethod
-    def forward(ctx, x, gw, gb, factor, bias, groups, eps, act):
-        x = x.contiguous()
+    def out(x, A, Bs, p, aux):
         B, C, M, U = x.shape
-        _, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
         y = torch.empty(B, C, M, device=x.device, dtype=torch.float32)
-        _lib.call("lion_affine_act_max", x, A, Bs, B * C, M, U, int(act), y)
-        ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0))
-        ctx.meta = (groups, int(act), factor is not None, bias is not None, fs,
-                    None if factor is None else factor.shape, None if bias is None else bias.shape)
-        return y
+        _lib.call("lion_affine_act_max", x, A, Bs, B * C, M, U, p[0], y)
+        return y, ()
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, A, Bs, mean, rstd, gwc, gbc, f = ctx.saved_tensors
-        groups, act, has_f, has_b, fs, f_shape, b_shape = ctx.meta
-        gy = gy.contiguous()
+    def sums(x, gy, A, Bs, p, kept, S):
         B, C, M, U = x.shape
-        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
-        _lib.call("lion_affine_act_max_bwd_stats", x, gy, A, Bs, B * C, M, U, act, S)
-        Q, R, dfac, dbias, pw, _ = _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, M * U)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            _lib.call("lion_affine_act_max_bwd_apply", x, gy, A, Bs, Q, R, B * C, M, U, act, dx)
-        dgw, dgb, _ = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2])   # d norm.weight, d norm.bias
-        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
-        return dx, dgw, dgb, dfac, dbias, None, None, None
+        _lib.call("lion_affine_act_max_bwd_stats", x, gy, A, Bs, B * C, M, U, p[0], S)
+
+    @staticmethod
+    def dx(x, gy, A, Bs, Q, R, p, kept, dx):
+        B, C, M, U = x.shape
+        _lib.call("lion_affine_act_max_bwd_apply", x, gy, A, Bs, Q, R, B * C, M, U, p[0], dx)
 
 
 def adagn_act_max_usable(x, need_grad=True) -> bool:
@@ -288,14 +268,13 @@ def adagn_act_max_usable(x, need_grad=True) -> bool:
 
 
 def adagn_act_max(x, norm, factor=None, bias=None, act=True):
-    """max_u act(GroupNorm(x) * factor + bias) over the last axis of x [B, C, M, U] (see _AdaGNActMax)."""
-    return _AdaGNActMax.apply(x, norm.weight, norm.bias, factor, bias, int(norm.num_groups), float(norm.eps), bool(act))
+    """max_u act(GroupNorm(x) * factor + bias) over the last axis of x [B, C, M, U] (see _ActMax)."""
+    return _adagn_op(_ActMax, (int(bool(act)),), x, norm, factor, bias)
 
 
 def adagn_act(x, norm, factor=None, bias=None, act=True, dropout_p=0.0):
     """dropout(act(GroupNorm(x) * factor + bias), dropout_p); factor / bias [B, C] (or broadcastable views of it) or None."""
-    return _AdaGNAct.apply(x, norm.weight, norm.bias, factor, bias, int(norm.num_groups), float(norm.eps), bool(act),
-                           float(dropout_p))
+    return _adagn_op(_Act, (int(bool(act)), float(dropout_p)), x, norm, factor, bias)
 
 
 def fusable_dropout(layers, i):
@@ -310,101 +289,115 @@ def fusable_dropout(layers, i):
     return 0.0, 0
 
 
-class _AdaGNSE(torch.autograd.Function):
-    """SE3d(AdaGN(x)) with no activation between the two -- the tail of every PVConv's voxel branch (reference pvcnn2_ada.py:211-226:
+class _SE:
+    """adagn_se: SE3d(AdaGN(x)) with no activation between the two -- the tail of every PVConv's voxel branch (reference pvcnn2_ada.py:211-226:
     Conv3d -> AdaGN -> SE3d) -- as ONE differentiable op.  u = A x + Bs (the AdaGN) and y = g u (the gate, g from the channel means
     of u) are both affine per (sample, channel): forward = row sums of x, the [B, C] algebra (GroupNorm fold, mean(u) = A mean(x) + Bs,
     the gate), ONE pass y = (g A) x + g Bs; backward = ONE reduction {sum gy, sum gy x}, the [B, C] algebra (the gate's gradient is
     A S2 + Bs S1; du = g gy + Qse and its row sums follow in closed form; GroupNorm backward), ONE pass dx = (A g) gy + Q + R x.
-    The two separate ops (adagn_act(act=False) -> se3d) make 6 passes over the grid forward and 10 backward."""
+    The two separate ops (adagn_act(act=False) -> se3d) make 6 passes over the grid forward and 10 backward.
+    No scalars, keeps nothing beyond the gate's tensors."""
+    gate, keeps_stats = True, True
 
     @staticmethod
-    def forward(ctx, x, gw, gb, factor, bias, w1, w2, groups, eps):
-        x = x.contiguous()
-        B, C = x.shape[:2]
-        L = x[0, 0].numel()
-        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
-        w1c, w2c, um, h, g, A2, B2 = _se_gate_fwd(stats, A, Bs, w1, w2, L)
+    def out(x, A, Bs, p, aux):
         y = torch.empty_like(x)
-        _lib.call("lion_affine_act", x, A2, B2, B * C, L, 0, y)
-        ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0), stats, um, h, g, w1c, w2c)
-        ctx.meta = (groups, factor is not None, bias is not None, fs,
-                    None if factor is None else factor.shape, None if bias is None else bias.shape)
-        return y
+        _lib.call("lion_affine_act", x, A, Bs, x.shape[0] * x.shape[1], x[0, 0].numel(), 0, y)
+        return y, ()
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, A, Bs, mean, rstd, gwc, gbc, f, stats, um, h, g, w1, w2 = ctx.saved_tensors
-        groups, has_f, has_b, fs, f_shape, b_shape = ctx.meta
-        gy = gy.contiguous()
-        B, C = x.shape[:2]
-        L = x[0, 0].numel()
-        S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
-        _lib.call("lion_affine_act_bwd_stats", x, gy, A, Bs, B * C, L, 0, S)   # act 0: S = {sum gy, sum gy x}
-        Sp, Qse, dw1, dw2 = _se_gate_bwd(S, stats, A, Bs, g, h, um, w1, w2, L)
-        Q, R, dfac, dbias, pw, Aout = _bwd_fold(Sp, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A, stats, g, Qse)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            _lib.call("lion_affine_act_bwd_apply", x, gy, Aout, Bs, Q, R, B * C, L, 0, dx)   # (act 0: Bs does not enter)
-        dgw, dgb, dxs = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], dx is not None and x.dim() == 5)
-        if dxs is not None:
-            tag_channel_sum(dx, dxs)
-        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
-        return (dx, dgw, dgb, dfac, dbias, (dw1 if ctx.needs_input_grad[5] else None), (dw2 if ctx.needs_input_grad[6] else None),
-                None, None)
+    def sums(x, gy, A, Bs, p, kept, S):   # act 0: S = {sum gy, sum gy x}
+        _lib.call("lion_affine_act_bwd_stats", x, gy, A, Bs, x.shape[0] * x.shape[1], x[0, 0].numel(), 0, S)
+
+    @staticmethod
+    def dx(x, gy, A, Bs, Q, R, p, kept, dx):   # (act 0: Bs does not enter)
+        _lib.call("lion_affine_act_bwd_apply", x, gy, A, Bs, Q, R, x.shape[0] * x.shape[1], x[0, 0].numel(), 0, dx)
 
 
-class _AdaGNSEDevox(torch.autograd.Function):
-    """trilinear_devoxelize(SE3d(AdaGN(x)), coords) -- the whole tail of a PVConv's voxel branch behind its second convolution
+class _SEDevox:
+    """adagn_se_devox: trilinear_devoxelize(SE3d(AdaGN(x)), coords) -- the whole tail of a PVConv's voxel branch behind its second convolution
     (reference pvcnn2_ada.py:211-233) -- as ONE differentiable op.  All three are linear in x given the [B, C] scalars, and the
     devoxelisation's weights sum to one per point, so devox(g (A x + Bs)) = (g A) devox(x) + g Bs: the forward devoxelises x itself
     and never writes a gated grid; the backward gets its two row sums from the POINTS (sum_p gpt ws, sum_p gpt devox(x): no pass over
     the grid) and writes dx = A' scatter(gpt) + Q + R x inside the scatter's own pass.  Dense passes over [B, C, r^3]: 1 forward
-    (the GroupNorm row sums), 2 backward (read x, write dx); _AdaGNSE followed by the devoxelisation makes 3 and 6."""
+    (the GroupNorm row sums), 2 backward (read x, write dx); _SE followed by the devoxelisation makes 3 and 6.
+    p = (r,), aux = the voxel coordinates; keeps devox(x) [B, C, N], the corner indices and weights [B, 8, N] and the weights' sums [B, N]."""
+    gate, keeps_stats = True, True
 
     @staticmethod
-    def forward(ctx, x, gw, gb, factor, bias, w1, w2, coords, groups, eps, r):
+    def out(x, A, Bs, p, aux):
         from .functional import backend as _bk
-        x = x.contiguous()
-        L = x[0, 0].numel()
-        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
-        w1c, w2c, um, h, g, A2, B2 = _se_gate_fwd(stats, A, Bs, w1, w2, L)
-        dv, inds, wgts = _bk._backend.trilinear_devoxelize_forward(int(r), True, coords[:, :3].contiguous(), x.flatten(2))
-        out = torch.addcmul(B2.unsqueeze(-1), dv, A2.unsqueeze(-1))          # [B, C, N]: (g A) devox(x) + g Bs
-        wsum = wgts.sum(1)                                                     # [B, N]: the 8 corner weights of a point
-        ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0), stats, um, h, g, w1c, w2c,
-                              dv, inds, wgts, wsum)
-        ctx.meta = (groups, factor is not None, bias is not None, fs,
-                    None if factor is None else factor.shape, None if bias is None else bias.shape)
-        return out
+        dv, inds, wgts = _bk._backend.trilinear_devoxelize_forward(p[0], True, aux[:, :3].contiguous(), x.flatten(2))
+        y = torch.addcmul(Bs.unsqueeze(-1), dv, A.unsqueeze(-1))            # [B, C, N]: (g A) devox(x) + g Bs
+        return y, (dv, inds, wgts, wgts.sum(1))                             # [B, N]: the 8 corner weights of a point
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, gpt):
-        x, A, Bs, mean, rstd, gwc, gbc, f, stats, um, h, g, w1, w2, dv, inds, wgts, wsum = ctx.saved_tensors
-        groups, has_f, has_b, fs, f_shape, b_shape = ctx.meta
-        gpt = gpt.contiguous()
+    def sums(x, gpt, A, Bs, p, kept, S):
+        _lib.call("lion_rows_dot2", gpt, kept[0], kept[3], x.shape[0], x.shape[1], gpt.shape[2], S)
+
+    @staticmethod
+    def dx(x, gpt, A, Bs, Q, R, p, kept, dx):
+        _lib.call("lion_trilinear_devoxelize_backward_affine", gpt, kept[1], kept[2], x, A, Q, R, x.shape[0], x.shape[1], gpt.shape[2],
+                  x[0, 0].numel(), dx)
+
+
+class _AdaGNOp(torch.autograd.Function):
+    """the shell of the four ops above.  Forward: GroupNorm fold, the SE gate where the op has one, the op's output pass.  Backward:
+    the op's row sums S, the gate's backward, the GroupNorm backward's [B, C] algebra, the op's dx pass when x wants a gradient,
+    the parameter gradients that are wanted (one launch, none when nothing is), the gradients of factor / bias in their own shapes.
+    Saved: x, A, Bs, mean, rstd, norm weight, norm bias, factor view (8), the row sums of x where the op keeps them (1), the gate's
+    um, h, g, w1, w2 (5), then what out() returned -- an op keeps no more than it reads."""
+
+    @staticmethod
+    def forward(ctx, op, p, x, gw, gb, factor, bias, w1, w2, aux, groups, eps):
+        x = x.contiguous()
+        stats, A, Bs, mean, rstd, gwc, gbc, f, fs = _fold_head(x, gw, gb, factor, bias, groups, eps)
+        Ay, By, gate = A, Bs, ()
+        if op.gate:
+            w1c, w2c, um, h, g, Ay, By = _se_gate_fwd(stats, A, Bs, w1, w2, x[0, 0].numel())
+            gate = (um, h, g, w1c, w2c)
+        y, kept = op.out(x, Ay, By, p, aux)
+        ctx.save_for_backward(x, A, Bs, mean, rstd, gwc, gbc, f if f is not None else x.new_empty(0),
+                              *((stats,) if op.keeps_stats else ()), *gate, *kept)
+        ctx.meta = (op, p, groups, factor is not None, bias is not None, fs,
+                    None if factor is None else factor.shape, None if bias is None else bias.shape)
+        return y
+
+    @staticmethod
+    @once_differentiable   # raw kernels: a double backward must raise, not silently treat these gradients as constants
+    def backward(ctx, gy):
+        op, p, groups, has_f, has_b, fs, f_shape, b_shape = ctx.meta
+        x, A, Bs, mean, rstd, gwc, gbc, f, *kept = ctx.saved_tensors
+        need = ctx.needs_input_grad   # by position in forward's arguments: x 2, norm weight 3, norm bias 4, factor 5, bias 6, w1 7, w2 8
+        stats = kept.pop(0) if op.keeps_stats else None
+        gy = gy.contiguous()
         B, C = x.shape[:2]
         L = x[0, 0].numel()
-        N = gpt.shape[2]
         S = torch.empty(B * C, 2, device=x.device, dtype=torch.float32)
-        _lib.call("lion_rows_dot2", gpt, dv, wsum, B, C, N, S)
-        Sp, Qse, dw1, dw2 = _se_gate_bwd(S, stats, A, Bs, g, h, um, w1, w2, L)
-        Q, R, dfac, dbias, pw, Aout = _bwd_fold(Sp, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L, A, stats, g, Qse)
+        g = Qse = dw1 = dw2 = None
+        if op.gate:
+            um, h, g, w1, w2, *kept = kept
+        op.sums(x, gy, A, Bs, p, kept, S)
+        if op.gate:   # S becomes the row sums of du = g gy + Qse
+            S, Qse, dw1, dw2 = _se_gate_bwd(S, stats, A, Bs, g, h, um, w1, w2, L)
+        Q, R, dfac, dbias, pw, Ag = _bwd_fold(S, mean, rstd, gwc, gbc, f, fs, has_f, has_b, groups, L,
+                                              A if stats is not None else None, stats, g, Qse)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if need[2]:
             dx = torch.empty_like(x)
-            _lib.call("lion_trilinear_devoxelize_backward_affine", gpt, inds, wgts, x, Aout, Q, R, B, C, N, L, dx)
-        dgw, dgb, dxs = _param_grads(pw, ctx.needs_input_grad[1], ctx.needs_input_grad[2], dx is not None and x.dim() == 5)
+            op.dx(x, gy, Ag if op.gate else A, Bs, Q, R, p, kept, dx)
+        # d norm.weight, d norm.bias; for a voxel grid also the sum of dx per channel = the bias gradient of the Conv3d in front
+        dgw, dgb, dxs = _param_grads(pw, need[3], need[4], dx is not None and x.dim() == 5)
         if dxs is not None:
             tag_channel_sum(dx, dxs)
-        dfac = _unbroadcast(dfac, f_shape) if has_f and ctx.needs_input_grad[3] else None
-        dbias = _unbroadcast(dbias, b_shape) if has_b and ctx.needs_input_grad[4] else None
-        return (dx, dgw, dgb, dfac, dbias, (dw1 if ctx.needs_input_grad[5] else None), (dw2 if ctx.needs_input_grad[6] else None),
-                None, None, None, None)
+        dfac = _unbroadcast(dfac, f_shape) if has_f and need[5] else None
+        dbias = _unbroadcast(dbias, b_shape) if has_b and need[6] else None
+        return (None, None, dx, dgw, dgb, dfac, dbias, (dw1 if need[7] else None), (dw2 if need[8] else None), None, None, None)
+
+
+def _adagn_op(op, p, x, norm, factor, bias, se=None, aux=None):
+    w1, w2 = (se.fc[0].weight, se.fc[2].weight) if se is not None else (None, None)
+    return _AdaGNOp.apply(op, p, x, norm.weight, norm.bias, factor, bias, w1, w2, aux, int(norm.num_groups), float(norm.eps))
 
 
 def adagn_se_devox_usable(x, se) -> bool:
@@ -414,15 +407,13 @@ def adagn_se_devox_usable(x, se) -> bool:
 
 
 def adagn_se_devox(x, norm, factor, bias, se, coords, r):
-    """trilinear_devoxelize(SE3d(GroupNorm(x) * factor + bias), coords, r) as one op (see _AdaGNSEDevox)"""
-    return _AdaGNSEDevox.apply(x, norm.weight, norm.bias, factor, bias, se.fc[0].weight, se.fc[2].weight, coords.detach(),
-                               int(norm.num_groups), float(norm.eps), int(r))
+    """trilinear_devoxelize(SE3d(GroupNorm(x) * factor + bias), coords, r) as one op (see _SEDevox)"""
+    return _adagn_op(_SEDevox, (int(r),), x, norm, factor, bias, se, coords.detach())
 
 
 def adagn_se(x, norm, factor, bias, se):
-    """SE3d(GroupNorm(x) * factor + bias) as one op (see _AdaGNSE); `se` passes se3d_trainable."""
-    return _AdaGNSE.apply(x, norm.weight, norm.bias, factor, bias, se.fc[0].weight, se.fc[2].weight, int(norm.num_groups),
-                          float(norm.eps))
+    """SE3d(GroupNorm(x) * factor + bias) as one op (see _SE); `se` passes se3d_trainable."""
+    return _adagn_op(_SE, (), x, norm, factor, bias, se)
 
 
 class _SE3d(torch.autograd.Function):

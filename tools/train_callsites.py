@@ -27,7 +27,7 @@ else:
     model = lion.priors.train(); params = list(model.parameters())
     opt = torch.optim.Adam(params, lr=1e-4, betas=(0.9, 0.99), fused=True); av = BucketedGradAverager(params)
     def step():
-        training.prior_forward_backward(lion.vae, model, lion.diffusion, opt, x, averager=av); opt.step()
+        training.prior_forward_backward(lion.vae, model, lion.diffusion, opt, x, averager=av); av.finish(); opt.step()
 for _ in range(3): step()
 torch.cuda.synchronize()
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], with_stack=True) as prof:
