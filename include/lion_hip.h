@@ -334,6 +334,40 @@ int lion_chain_update_multistep_noise_cm_keyed(const float *x, const float *eps_
                                                float *out, float *hist_out, float *z_out, lionStream_t stream);
 int lion_chain_diffuse_keyed(const float *x0, int B, int n, float m, float s, const uint32_t *keys, uint32_t stream_id,
                              float *out, float *z_out, lionStream_t stream);
+/* Inputs of guided synthesis (csrc/perturb.hip): perturbed copies of clouds x f32[B][N][3], every cloud on its
+ * own and under its own key (keys as above).  One Philox4x32-10 call per output point at counter = (point index WITHIN the
+ * sample, a reserved step word, stream_id), words w0..w3; a fraction is u(w) = (w >> 8) * 2^-24, exact.  LION_VOXEL_STEP_WORD
+ * and LION_PERTURB_STEP_WORD are the third and fourth reserved step words: no chain step, start latent or forward draw
+ * shares a counter with them.  Every written operation on a coordinate is rounded once (no fma); what selects a face or a
+ * point is integer arithmetic; no atomics: the output is bit-reproducible and depends on neither B, nor b, nor the other keys.
+ *
+ * lion_voxel_surface_points_keyed: out f32[B][K][3] = K points on the surface of the cloud's voxelisation at resolution r.
+ *   Box: mn, mx = the per-axis min and max of the points; c = (mn + mx)*0.5 per axis; h = the largest (mx - mn)*0.5 over the
+ *   axes, 1 where that is 0; lo = c - h per axis; s = (2h)/r; inv = r/(2h).
+ *   Occupancy: point p sets voxel i_axis = clamp((int)floorf((p - lo)*inv), 0, r-1), flat id x*r*r + y*r + z.
+ *   Faces: face f = 0..5 = -x, +x, -y, +y, -z, +z of an occupied voxel is exposed when the neighbour across it is empty or
+ *   outside the grid; the exposed faces are numbered in ascending (flat id, f), F of them (F >= 6); faces_out[b] = F.
+ *   Point k: face (uint64(w0)*F) >> 32 of voxel (ix, iy, iz); the grid coordinate t is i on a - face and i + 1 on a + face
+ *   along the face's axis, i + u(w1) and i + u(w2) along the other two in ascending axis order; out = lo + t*s per axis.
+ *   One workgroup per cloud, every table in LDS: lion_voxel_surface_workspace_bytes is 0 for every shape and ws may be NULL
+ *   (the parameters keep the call's shape should a finer grid ever spill).
+ *   LION_EINVAL before any launch: x, keys or out NULL (faces_out may be NULL), B <= 0 or B > 65535, N <= 0, K <= 0, r < 1 or
+ *   r > 32, ws_bytes below lion_voxel_surface_workspace_bytes or ws NULL where that is not 0.
+ * lion_perturb_points_keyed: out f32[B][N][3]; out must not overlap x.
+ *   mode 0 (uniform noise):  out = x + (p0*(2*u(w_axis) - 1)) per coordinate, axis = 0, 1, 2.
+ *   mode 1 (outliers):       where w3 < floor(p0 * 2^32) (in double from the float p0, saturated at 2^32 - 1) the point becomes
+ *                            mn + u(w_axis)*(mx - mn) per axis, mn / mx the cloud's own bounding box as above; else it is copied.
+ *   LION_EINVAL before any launch: x, keys or out NULL, B <= 0 or B > 65535, N <= 0, a mode outside {0, 1}, p0 negative or
+ *   NaN, p0 > 1 in mode 1.
+ * Normal noise out = x + sigma*z is lion_chain_diffuse_keyed with m = 1, s = sigma, bit for bit. */
+#define LION_VOXEL_STEP_WORD 0xFFFFFFFDu
+#define LION_PERTURB_STEP_WORD 0xFFFFFFFCu
+size_t lion_voxel_surface_workspace_bytes(int B, int N, int r, int K);
+int lion_voxel_surface_points_keyed(const float *x, int B, int N, int r, const uint32_t *keys /* device u32[2*B] */,
+                                    uint32_t stream_id, int K, float *out, int32_t *faces_out /* device i32[B], may be NULL */,
+                                    void *ws, size_t ws_bytes, lionStream_t stream);
+int lion_perturb_points_keyed(int mode, const float *x, int B, int N, float p0, const uint32_t *keys, uint32_t stream_id,
+                              float *out, lionStream_t stream);
 /* x f32[B][N][D] (point-major latent; 3 <= D <= 8) -> channel-major all f32[B][D][N], coords f32[B][3][N] (rows 0-2),
  * rest f32[B][D-3][N]; each output may be NULL: the view / permute / slice / contiguous head of
  * models/latent_points_ada_localprior.py:72-84 + models/latent_points_ada.py:118-121 in one launch. */

@@ -6,7 +6,8 @@ Sub-packages:
   chamfer3d, emd   the reference's chamfer_3D / emd_ext operator modules
   models/      host-side mirror of models.pvcnn2_ada / latent_points_ada / score_sde / vae_adain / lion
   diffusion    DiffusionDiscretized (utils/diffusion_pvd.py) with a fused per-step update
-  editing      diffuse-denoise of an encoded shape (trainers/denoise_pts.py) on the captured chain
+  editing      diffuse-denoise of an encoded shape (trainers/denoise_pts.py) on the captured chain; voxel-guided synthesis
+  perturb      the inputs of guided synthesis: voxel-surface points, normal / uniform / outlier corruption, keyed per sample
   dist         data-parallel gradient step (utils/utils.py:717-770) over RCCL
 
 Nothing here falls back to a CPU implementation: without the built HIP library every

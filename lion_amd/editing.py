@@ -7,6 +7,8 @@ Per latent the device work is one forward draw (``DiffusionDiscretized.diffuse``
 call of the same batch shape captured is the one replayed here.  One ``time_start`` per latent for the whole batch, as in the
 reference.  With ``solver_steps=S`` the tail is instead at most S replays of the few-step solver's captured step
 (``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
+
+``voxel_guided`` is the recipe on the surface of the input's voxelisation (``perturb.voxel_surface_points``).
 """
 from __future__ import annotations
 
@@ -138,4 +140,20 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     info = {"global_original": global_ori, "global_edited": global_new, "local_original": local_ori,
             "local_edited": local_new, "condition_input": condition_input, "time_start": pair, "seeds": seeds,
             "tail_steps": (visited[0], visited[1])}
+    return points, info
+
+
+@torch.no_grad()
+def voxel_guided(vae, dae, diffusion, x, resolution, time_start, **diffuse_denoise_kwargs):
+    """Voxel-guided synthesis: x [B, N, 3] -> (points [B, N, 3], info).  The input is replaced by N points on the surface of
+    its voxelisation at `resolution` (perturb.voxel_surface_points) and that cloud goes through diffuse_denoise(vae, dae,
+    diffusion, ., time_start, **diffuse_denoise_kwargs), which is not changed.  `seeds` (or `seed`) of the keyword arguments
+    address both: sample b's voxel points are drawn under seeds[b] at LION_VOXEL_STEP_WORD, a step word no draw of
+    diffuse_denoise uses, so the two never share a counter.  info is diffuse_denoise's with 'input' (the voxel-surface cloud
+    that was denoised) and 'faces' (int32[B], the exposed faces per cloud)."""
+    from . import perturb
+    pts, made = perturb.voxel_surface_points(x, resolution, x.shape[1], seeds=diffuse_denoise_kwargs.get("seeds"),
+                                             seed=diffuse_denoise_kwargs.get("seed"))
+    points, info = diffuse_denoise(vae, dae, diffusion, pts, time_start, **diffuse_denoise_kwargs)
+    info["input"], info["faces"] = pts, made["faces"]
     return points, info
