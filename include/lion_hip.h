@@ -520,6 +520,12 @@ int lion_from_channel_major(const float *x, int B, int C, float *y, lionStream_t
 int lion_groupnorm_fold_se(const float *stats, int B, int C, int T, int G, int voxels, const float *gamma,
                            const float *beta, const float *fac, const float *gbias, int ld_fg, float eps, const float *w1,
                            const float *w2, int H, float *A, float *Bs, lionStream_t stream);
+/* For tests only: the same through the plain kernel, which requests the operands of each of its four phases behind the
+ * barrier of the phase before; lion_groupnorm_fold_se requests them all in front of the first wait (for H in {4, 8, 16, 32}
+ * and a 16-byte aligned w2; otherwise it runs this kernel) and equals it bit for bit (tests/test_small_launches_gpu.py). */
+int lion_internal_groupnorm_fold_se_plain(const float *stats, int B, int C, int T, int G, int voxels, const float *gamma,
+                                          const float *beta, const float *fac, const float *gbias, int ld_fg, float eps,
+                                          const float *w1, const float *w2, int H, float *A, float *Bs, lionStream_t stream);
 int lion_se_gate(const float *chmean, const float *w1, const float *w2, int B, int C, int H, float *A,
                  float *Bs, lionStream_t stream);
 int lion_trilinear_devoxelize_affine_forward(const float *coords, const float *feat, const float *scale,
@@ -600,6 +606,15 @@ int lion_internal_pwconv_walk(const float *x, const float *wp, const float *bias
                               const float *pro_a, const float *pro_b, const float *out_a, const float *out_b,
                               const float *coords, const float *centers, const float *feat, const int32_t *idx, int N, int U,
                               float *y, float *stats, int max_wg, int lds_weights, lionStream_t stream);
+/* For tests only: the short-activation kernel (L <= 4096) in its plain form -- prologue scalars waited for before the first
+ * operand is requested, each round of 32 k-steps requested after the previous round's MFMAs.  The public entries at such an
+ * L request the operands in front of the first wait and one round ahead, and equal this one bit for bit
+ * (tests/test_small_launches_gpu.py).  Arguments of lion_pwconv_forward; idx != NULL: the gathered operand (x unused,
+ * Cin = 3 + C, feat NULL when Cin = 3, L = M * U, no prologue). */
+int lion_internal_pwconv_small_plain(const float *x, const float *wp, const float *bias, int B, int Cin, int Cout, int L,
+                                     const float *pro_a, const float *pro_b, const float *coords, const float *centers,
+                                     const float *feat, const int32_t *idx, int N, int U, float *y, float *stats,
+                                     lionStream_t stream);
 /* ---- P5: LinearAttention (models/pvcnn2_ada.py:43-71) between its two 1x1 convolutions ---------------------
  * qkv f32[B, 3*H*D, N] (to_qkv's output, channel order (qkv, head, d)) -> out f32[B, H*D, N] (to_out's input):
  * softmax over the N points of every k row, ctx = softmax(k) v^T (D x D), out = ctx^T q.  D = 32 (every

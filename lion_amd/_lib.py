@@ -68,6 +68,7 @@ SIGNATURES = {
     "lion_conv3d_k3_half_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lion_groupnorm_fold": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     "lion_groupnorm_fold_se": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
+    "lion_internal_groupnorm_fold_se_plain": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
     "lion_skinny_packed_floats": (_sz, [_i, _i]),
     "lion_skinny_pack_weights": (_i, [_vp, _i, _i, _vp, _vp]),
     "lion_skinny_splits": (_i, [_i, _i]),
@@ -97,6 +98,7 @@ SIGNATURES = {
     "lion_pwconv_grouped_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lion_pwconv_split_grouped_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "lion_internal_pwconv_walk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "lion_internal_pwconv_small_plain": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "lion_linear_attention_core": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "lion_internal_linear_attention_path": (_i, [_i, _i]),
     "lion_internal_linear_attention_core_plain": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

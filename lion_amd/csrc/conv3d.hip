@@ -538,6 +538,92 @@ __global__ __launch_bounds__(256) void conv_tconst_kernel(const float *__restric
   }
 }
 
+// gn_fold_se_kernel with ONE memory round trip, for H = 4 HV (the SE layers of the model: H = C / 8 in {4, 8, 16, 32}) and
+// 16-byte aligned w2: the thread's fac / gbias / gamma / beta, the wave's HV rows of w1 (CC coalesced loads each) and the
+// thread's row of w2 (HV 16-byte loads) are requested in front of the first wait instead of behind the barrier of the
+// phase that uses them -- none depends on a computed value -- and the tile sums in batches of 8 independent loads.
+// Clamped addresses, loads on every path.  The arithmetic, its orders and the expf are gn_fold_se_kernel's
+// (tests/test_small_launches_gpu.py: equal bit for bit).
+template <int HV, int CC>
+__global__ __launch_bounds__(256) void gn_fold_se_ahead_kernel(const float *__restrict__ stats, int C, int T, int G, float count,
+                                                               const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                               const float *__restrict__ fac, const float *__restrict__ gbias,
+                                                               int ld_fg, float eps, const float *__restrict__ w1,
+                                                               const float *__restrict__ w2, float *__restrict__ A,
+                                                               float *__restrict__ Bs) {
+  constexpr int H = 4 * HV;
+  __shared__ double cs[256][2];
+  __shared__ float sA[256], sB[256], sm[256], sh[128];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cpg = C / G;
+  const int tc = min(tid, C - 1);
+  const float p_f = fac[(size_t)b * ld_fg + tc], p_gb = gbias[(size_t)b * ld_fg + tc], p_gam = gamma[tc], p_bet = beta[tc];
+  float w1r[HV][CC];
+  float4 w2r[HV];
+#pragma unroll
+  for (int jj = 0; jj < HV; ++jj)
+#pragma unroll
+    for (int q = 0; q < CC; ++q) w1r[jj][q] = w1[(size_t)(wave + 4 * jj) * C + min(lane + 64 * q, C - 1)];
+#pragma unroll
+  for (int j = 0; j < HV; ++j) w2r[j] = reinterpret_cast<const float4 *>(w2 + (size_t)tc * H)[j];
+  int cp2 = 1;
+  while (cp2 < C) cp2 <<= 1;
+  const int LPC = 256 / cp2, ch = tid / LPC, sub = tid % LPC; // LPC in {1, ..., 64}
+  double s1 = 0.0, s2 = 0.0;
+  if (ch < C) {
+    const float2 *p = reinterpret_cast<const float2 *>(stats + (((size_t)b * C + ch) * T) * 2);
+    for (int t0 = sub; t0 < T; t0 += 8 * LPC) { // tiles sub, sub + LPC, ... in this order, eight requests at a time
+      float2 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = p[min(t0 + u * LPC, T - 1)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (t0 + u * LPC < T) { s1 += (double)v[u].x; s2 += (double)v[u].y; }
+    }
+  }
+  for (int m = 1; m < LPC; m <<= 1) { s1 += __shfl_xor(s1, m, 64); s2 += __shfl_xor(s2, m, 64); }
+  if (ch < C && sub == 0) { cs[ch][0] = s1; cs[ch][1] = s2; }
+  __syncthreads();
+  if (tid < C) {
+    const int g0 = (tid / cpg) * cpg;
+    double g1 = 0.0, g2 = 0.0;
+    for (int k = 0; k < cpg; ++k) { g1 += cs[g0 + k][0]; g2 += cs[g0 + k][1]; }
+    const double n = (double)count * cpg, mean = g1 / n;
+    double var = g2 / n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float a0 = rstd * p_gam;
+    const float a = a0 * p_f, bb = (p_bet - (float)mean * a0) * p_f + p_gb;
+    sA[tid] = a;
+    sB[tid] = bb;
+    sm[tid] = a * (float)(cs[tid][0] / count) + bb; // mean over the grid of AdaGN(y) (se_gate_kernel)
+  }
+  __syncthreads();
+#pragma unroll
+  for (int jj = 0; jj < HV; ++jj) { // one wave per hidden unit, rows wave, wave + 4, ...
+    float acc = 0.f;
+#pragma unroll
+    for (int q = 0; q < CC; ++q)
+      if (lane + 64 * q < C) acc += w1r[jj][q] * sm[lane + 64 * q];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if (lane == 0) sh[wave + 4 * jj] = acc > 0.f ? acc : 0.f;
+  }
+  __syncthreads();
+  if (tid < C) {
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < HV; ++j) {
+      acc += w2r[j].x * sh[4 * j];
+      acc += w2r[j].y * sh[4 * j + 1];
+      acc += w2r[j].z * sh[4 * j + 2];
+      acc += w2r[j].w * sh[4 * j + 3];
+    }
+    const float g = 1.0f / (1.0f + expf(-acc));
+    A[(size_t)b * C + tid] = sA[tid] * g;
+    Bs[(size_t)b * C + tid] = sB[tid] * g;
+  }
+}
+
 // [Cout][Cin][27] (PyTorch) -> [Cin_pad][27][Cout], Cin padded with zeros to a multiple of KC
 __global__ void conv3d_pack_kernel(const float *__restrict__ w, int Cout, int Cin, int Cin_pad,
                                    float *__restrict__ wp) {
@@ -688,12 +774,40 @@ int lion_conv3d_stat_tiles(int r, int Cout, int B, int sparse) {
 }
 
 // lion_groupnorm_fold followed by lion_se_gate (w1 f32[H,C], w2 f32[C,H]) in one launch: A, Bs already carry the gate
-int lion_groupnorm_fold_se(const float *stats, int B, int C, int T, int G, int voxels, const float *gamma,
-                           const float *beta, const float *fac, const float *gbias, int ld_fg, float eps, const float *w1,
-                           const float *w2, int H, float *A, float *Bs, lionStream_t stream) {
+static int gn_fold_se_args(const float *stats, int B, int C, int T, int G, const float *gamma, const float *beta,
+                           const float *fac, const float *gbias, int ld_fg, const float *w1, const float *w2, int H,
+                           float *A, float *Bs) {
   if (!stats || !gamma || !beta || !fac || !gbias || !w1 || !w2 || !A || !Bs) return LION_EINVAL;
   if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G != 0 || ld_fg < C || H <= 0) return LION_EINVAL;
   if (C > 256 || C < 4 || H > 128) return LION_EUNSUPPORTED;
+  return 0;
+}
+
+int lion_groupnorm_fold_se(const float *stats, int B, int C, int T, int G, int voxels, const float *gamma,
+                           const float *beta, const float *fac, const float *gbias, int ld_fg, float eps, const float *w1,
+                           const float *w2, int H, float *A, float *Bs, lionStream_t stream) {
+  if (int e = gn_fold_se_args(stats, B, C, T, G, gamma, beta, fac, gbias, ld_fg, w1, w2, H, A, Bs)) return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the one-round-trip kernel holds the wave's rows of w1 and the thread's row of w2 in registers: H in {4, 8, 16, 32} (the SE
+  // layers of the model) and w2 rows it can read 16 bytes at a time; everything else runs the plain kernel
+  if (H % 4 != 0 || H > 32 || (H & (H - 1)) != 0 || (((uintptr_t)w2) & 15) != 0)
+    return lion_launch<gn_fold_se_kernel>(B, 256, 0, st, stats, C, T, G, (float)voxels, gamma, beta, fac, gbias, ld_fg, eps, w1, w2,
+                                          H, A, Bs);
+  auto go = [&](auto HV, auto CC) {
+    return lion_launch<gn_fold_se_ahead_kernel<decltype(HV)::value, decltype(CC)::value>>(
+        B, 256, 0, st, stats, C, T, G, (float)voxels, gamma, beta, fac, gbias, ld_fg, eps, w1, w2, A, Bs);
+  };
+  auto rows = [&](auto CC) {
+    return H == 4 ? go(IntC<1>{}, CC) : H == 8 ? go(IntC<2>{}, CC) : H == 16 ? go(IntC<4>{}, CC) : go(IntC<8>{}, CC);
+  };
+  return C <= 64 ? rows(IntC<1>{}) : C <= 128 ? rows(IntC<2>{}) : rows(IntC<4>{});
+}
+
+// For tests only: the same through gn_fold_se_kernel, which requests each phase's operands behind the barrier before it
+int lion_internal_groupnorm_fold_se_plain(const float *stats, int B, int C, int T, int G, int voxels, const float *gamma,
+                                          const float *beta, const float *fac, const float *gbias, int ld_fg, float eps,
+                                          const float *w1, const float *w2, int H, float *A, float *Bs, lionStream_t stream) {
+  if (int e = gn_fold_se_args(stats, B, C, T, G, gamma, beta, fac, gbias, ld_fg, w1, w2, H, A, Bs)) return e;
   return lion_launch<gn_fold_se_kernel>(B, 256, 0, static_cast<hipStream_t>(stream), stats, C, T, G, (float)voxels,
                                         gamma, beta, fac, gbias, ld_fg, eps, w1, w2, H, A, Bs);
 }

@@ -496,6 +496,144 @@ __global__ __launch_bounds__(256) void pwconv_small_kernel(const float *__restri
   }
 }
 
+// pwconv_small_kernel without its dependent round trips (the library's kernel; the one above stays as the tests' twin,
+// lion_internal_pwconv_small_plain).  Two things move, no arithmetic does:
+//   * with a prologue the first round's operand loads are in flight BEFORE the scalars go through LDS and the barrier
+//     (MR = false: the thread's one pair of scalars is requested first and waited for alone; MR = true: the staging loop's
+//     wait covers the operands too) -- one round trip in front of the first MFMA instead of two;
+//   * MR (a wave owns more than one round, Cin > 256): round i + 1 is requested before the MFMAs of round i, two register
+//     buffers of UN = 16 k-steps (two of 32 do not fit 256 registers beside the accumulators); addresses clamped, loads on
+//     every path.  MR = false is the single round of 32, and then the loop is gone.
+// The k order of the MFMA chains, the masks, the combine, the bias add, the stores and the sums are pwconv_small_kernel's.
+template <bool PRO, bool STATS, bool MR, typename... G>
+__global__ __launch_bounds__(256) void pwconv_small_ahead_kernel(const float *__restrict__ x, const float *__restrict__ wp,
+                                                                 const float *__restrict__ bias, float *__restrict__ y,
+                                                                 int Cin, int Cout, int CoutY, int L,
+                                                                 const float *__restrict__ pro_a,
+                                                                 const float *__restrict__ pro_b, float *__restrict__ stats,
+                                                                 G... gather) {
+  constexpr bool GRP = sizeof...(G) > 0; // as in pwconv_kernel
+  static_assert(!(GRP && PRO), "the gathered operand is a first layer: no prologue");
+  [[maybe_unused]] const PwGather g = pw_gather(gather...);
+  __shared__ float part[4][2][1024];
+  extern __shared__ __attribute__((aligned(16))) float smem[]; // [2][Cin] prologue scalars (PRO)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cl = lane & 31, kh = lane >> 5;
+  const int b = blockIdx.z, co0 = blockIdx.y * 64, col = blockIdx.x * 32 + cl;
+  const bool cok = col < L;
+  const int colc = cok ? col : L - 1;
+  const int ksteps = (Cin + 1) >> 1, per = (ksteps + 3) >> 2;
+  const int s_lo = min(ksteps, wave * per), s_hi = min(ksteps, s_lo + per);
+  float *spa = smem, *spb = smem + Cin;
+  [[maybe_unused]] float ra = 0.f, rb = 0.f;
+  if (PRO && !MR) { // Cin <= 256: one pair per thread, requested in front of the operands and waited for alone
+    ra = pro_a[(size_t)b * Cin + min(tid, Cin - 1)];
+    rb = pro_b[(size_t)b * Cin + min(tid, Cin - 1)];
+  }
+  const float *xb = x + (size_t)b * Cin * L;
+  int gi = 0; // GRP: as in pwconv_kernel -- index and centre of this lane's column, gathers in place of the row reads
+  float gc0 = 0.f, gc1 = 0.f;
+  const float *gcb = nullptr, *gfb = nullptr;
+  int gfr = 0;
+  if constexpr (GRP) {
+    const int M = L / g.U, m = colc / g.U;
+    gcb = g.coords + (size_t)b * 3 * g.N;
+    gfb = g.feat ? g.feat + (size_t)b * g.C * g.N : gcb;
+    gfr = g.feat ? g.C - 1 : 0;
+    gc0 = g.centers[((size_t)b * 3 + kh) * M + m];
+    gc1 = g.centers[((size_t)b * 3 + 2) * M + m];
+    gi = min(max(g.idx[(size_t)b * L + colc], 0), g.N - 1);
+  }
+  constexpr int UN = MR ? 16 : 32;
+  auto load = [&](int s0, float (&av)[UN][2], float (&bv)[UN]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int k = min(2 * min(s0 + u, ksteps - 1) + kh, 2 * ksteps - 1); // packed rows exist up to ceil2(Cin)
+      av[u][0] = wp[(size_t)k * Cout + co0 + cl];
+      av[u][1] = wp[(size_t)k * Cout + co0 + 32 + cl];
+      if constexpr (GRP) {
+        const int kc = min(k, Cin - 1);
+        const float *row = kc < 3 ? gcb + (size_t)kc * g.N : gfb + (size_t)min(max(kc - 3, 0), gfr) * g.N;
+        bv[u] = row[gi];
+      } else {
+        bv[u] = xb[(size_t)min(k, Cin - 1) * L + colc];
+      }
+    }
+  };
+  f32x16 acc[2];
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[cb][i] = 0.f;
+  auto mma = [&](int s0, const float (&av)[UN][2], const float (&bv)[UN]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int k = 2 * (s0 + u) + kh;
+      float v = bv[u];
+      if (PRO) {
+        const int kc = min(k, Cin - 1);
+        const float t = v * spa[kc] + spb[kc];
+        v = swish_fast(t); // as in pwconv_kernel
+      }
+      if constexpr (GRP) v = k < 3 ? sub_rn(v, k == 2 ? gc1 : gc0) : v; // rows 0 / 1 are this lane's row kh
+      v = (s0 + u < s_hi && k < Cin && cok) ? v : 0.f;
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][0], v, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][1], v, acc[1], 0, 0, 0);
+    }
+  };
+  float av0[UN][2], bv0[UN];
+  load(s_lo, av0, bv0); // in flight across the prologue's barrier
+  float brow[8]; // this thread's 8 output rows (tid / 32 + 8 j): fetched now, not in front of the stores
+#pragma unroll
+  for (int j = 0; j < 8; ++j) brow[j] = (bias && co0 + (tid >> 5) + 8 * j < CoutY) ? bias[co0 + (tid >> 5) + 8 * j] : 0.f;
+  if (PRO) {
+    if (MR) {
+      for (int c = tid; c < Cin; c += 256) { spa[c] = pro_a[(size_t)b * Cin + c]; spb[c] = pro_b[(size_t)b * Cin + c]; }
+    } else if (tid < Cin) {
+      spa[tid] = ra;
+      spb[tid] = rb;
+    }
+    __syncthreads();
+  }
+  if constexpr (MR) {
+    float av1[UN][2], bv1[UN];
+    for (int s0 = s_lo; s0 < s_hi; s0 += 2 * UN) {
+      load(s0 + UN, av1, bv1);
+      mma(s0, av0, bv0);
+      load(s0 + 2 * UN, av0, bv0);
+      if (s0 + UN < s_hi) mma(s0 + UN, av1, bv1);
+    }
+  } else {
+    if (s_lo < s_hi) mma(s_lo, av0, bv0);
+  }
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) part[wave][cb][((i & 3) + 8 * (i >> 2) + 4 * kh) * 32 + cl] = acc[cb][i];
+  __syncthreads();
+  // thread -> (channel row = tid / 32 + 8 j, column = tid % 32): 8 channels per thread, coalesced 128-byte row stores
+  const int c = tid & 31, colo = blockIdx.x * 32 + c;
+  const bool ok = colo < L;
+  float *yb = y + ((size_t)b * CoutY + co0) * L;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = (tid >> 5) + 8 * j, cb = row >> 5, e = (row & 31) * 32 + c;
+    float o = ((part[0][cb][e] + part[1][cb][e]) + part[2][cb][e]) + part[3][cb][e];
+    const bool rok = co0 + row < CoutY;
+    o += brow[j];
+    if (ok && rok) yb[(size_t)row * L + colo] = o;
+    if (STATS) {
+      float s1 = ok ? o : 0.f, s2 = s1 * s1;
+      s1 = row16_sum_rn(s1); s2 = row16_sum_rn(s2);
+      s1 = row_pair_sum_odd_rows(s1); s2 = row_pair_sum_odd_rows(s2);
+      if (c == 16 && rok) { // the row pair's sum lives in the odd rows
+        float *so = stats + (((size_t)b * CoutY + co0 + row) * gridDim.x + blockIdx.x) * 2;
+        so[0] = s1;
+        so[1] = s2;
+      }
+    }
+  }
+}
+
 // nn.Linear on a [B, K] activation (time embedding MLP latent_points_ada.py:47-48, the AdaGN style projections
 // adagn.py:45-60 batched by models/adagn.py::StylePlan): y[b][o] = act(bias[o] + sum_k x[b][k] W[o][k]).
 // The batch (<= 32 rows per slab) sits on the MFMA columns, 32 output features on the rows, the four waves of a
@@ -646,13 +784,21 @@ template <PwForm FORM, int CB, int VB> static int launch_pw(const PwCall &c, Int
 }
 
 // pwconv_small_kernel (L <= PW_SMALL_L; PW_STORE or PW_GATHER): one workgroup per 32 columns x 64 channels
-template <PwForm FORM> static int launch_pw_small(const PwCall &c) {
+// plain: pwconv_small_kernel itself (the tests' twin); otherwise pwconv_small_ahead_kernel, in its multi-round form where a
+// wave owns more than 32 k-steps (Cin > 256)
+template <PwForm FORM> static int launch_pw_small(const PwCall &c, bool plain = false) {
   const dim3 grid(lion_cdiv(c.L, 32), pw_stride(c.Cout) / 64, c.B);
   const size_t lds = c.pa ? (size_t)2 * c.Cin * 4 : 0;
   if (lds > 64 * 1024) return LION_EUNSUPPORTED;
   return pw_with_form<FORM>(c, [&](auto PRO, auto ST, auto, auto... gather) {
-    return lion_launch<pwconv_small_kernel<decltype(PRO)::value, decltype(ST)::value, decltype(gather)...>>(
-        grid, 256, lds, c.st, c.x, c.wp, c.bias, c.y, c.Cin, pw_stride(c.Cout), c.Cout, c.L, c.pa, c.pb, c.stats, gather...);
+    if (plain)
+      return lion_launch<pwconv_small_kernel<decltype(PRO)::value, decltype(ST)::value, decltype(gather)...>>(
+          grid, 256, lds, c.st, c.x, c.wp, c.bias, c.y, c.Cin, pw_stride(c.Cout), c.Cout, c.L, c.pa, c.pb, c.stats, gather...);
+    return lion_with_flags(c.Cin > 256, [&](auto MR) {
+      return lion_launch<pwconv_small_ahead_kernel<decltype(PRO)::value, decltype(ST)::value, decltype(MR)::value,
+                                                   decltype(gather)...>>(
+          grid, 256, lds, c.st, c.x, c.wp, c.bias, c.y, c.Cin, pw_stride(c.Cout), c.Cout, c.L, c.pa, c.pb, c.stats, gather...);
+    });
   });
 }
 
@@ -756,6 +902,26 @@ int lion_internal_pwconv_walk(const float *x, const float *wp, const float *bias
     if (maxform) return launch_pw<PW_MAX>(c, CB, VB);
     return launch_pw<PW_STORE>(c, CB, VB);
   });
+}
+
+// For tests only: pwconv_small_kernel itself (L <= 4096), which waits for the prologue scalars before it requests an operand
+// and for each round's MFMAs before the next round's loads; lion_pwconv_forward / lion_pwconv_grouped_forward at such an L
+// run pwconv_small_ahead_kernel and must equal it bit for bit.  Arguments of lion_pwconv_forward; idx != NULL: the gathered
+// operand as in lion_internal_pwconv_walk (x unused, Cin = 3 + C, feat NULL when Cin = 3, L = M * U, no prologue).
+int lion_internal_pwconv_small_plain(const float *x, const float *wp, const float *bias, int B, int Cin, int Cout, int L,
+                                     const float *pro_a, const float *pro_b, const float *coords, const float *centers,
+                                     const float *feat, const int32_t *idx, int N, int U, float *y, float *stats,
+                                     lionStream_t stream) {
+  if (!wp || !y || B <= 0 || Cin <= 0 || Cout <= 0 || L <= 0) return LION_EINVAL;
+  if ((pro_a == nullptr) != (pro_b == nullptr)) return LION_EINVAL;
+  const bool grouped = idx != nullptr;
+  if (grouped ? (!coords || !centers || N <= 0 || U <= 0 || L % U != 0 || Cin < 3 || (Cin > 3 && !feat) || pro_a) : !x)
+    return LION_EINVAL;
+  if (L > PW_SMALL_L) return LION_EUNSUPPORTED;
+  PwCall c{grouped ? nullptr : x, wp, bias, y, stats, B, Cin, Cout, L, static_cast<hipStream_t>(stream), pro_a, pro_b};
+  if (!grouped) return launch_pw_small<PW_STORE>(c, true);
+  c.g = PwGather{coords, centers, Cin > 3 ? feat : nullptr, idx, Cin - 3, N, U};
+  return launch_pw_small<PW_GATHER>(c, true);
 }
 
 // y f32[B,O] = act(x f32[B,K] W^T + bias), wp = lion_pwconv_pack_weights(W f32[O,K]) (k-major, O padded to 32);
