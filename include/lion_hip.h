@@ -186,6 +186,29 @@ int lion_emd_matchcost(const float *xyz1, const float *xyz2, const float *match,
 int lion_emd_matchcost_backward(const float *grad_cost, const float *xyz1, const float *xyz2,
                                 const float *match, int B, int N, int M, float *grad1,
                                 float *grad2, lionStream_t stream);
+/* EMD reconstruction loss (utils/model_helper.py:82-96, 'emd' / 'chamfer_emd': earth_mover_distance = matchcost / N with the
+ * match held constant in the gradient) without the [B,M,N] match matrix, forward and gradient.
+ * loss_forward runs the auction of lion_emd_approxmatch operation for operation (the same expressions, quarters and merge
+ *   order in every pass; pass 1 of a level rides on pass 3 of the level before it, whose distances it shares: 23 launches),
+ *   so afterwards the first B * (2N + 2M) floats of the workspace hold the bits lion_emd_approxmatch leaves there on the same
+ *   inputs.  Workspace layout of both, in floats:
+ *     remainL[B,N] remainR[B,M] ratioL[B,N] ratioR[B,M] partial[B,ceil(N/256)] costrow[B,N]   (lion_emd_workspace_bytes)
+ *   With E = __expf(level * |x1[k] - x2[l]|^2) and one rounding per written operation, per level (10 of them, in order):
+ *     pass 3, row k:     w = (E * ratioL[k]) * ratioR[l];  crow += |..|^2 * w;  g += w * (x1[k] - x2[l])      (g: g1u != NULL)
+ *       each sum runs over l ascending inside the four 256-element quarters of every 1024 tile, the four partial sums merged
+ *       ((q0 + q1) + q2) + q3;  costrow[b,k] (+)= crow,  g1u[b,k,:] (+)= 2 * g: the first level stores, later levels add.
+ *     pass 2, column l:  v += (E * ratioL[k]) * (x2[l] - x1[k]) over k, same quarters and merge, beside the auction's own sum;
+ *       once ratioR[l] of the level is known  g2u[b,l,:] (+)= (2 * ratioR[l]) * v                              (g2u != NULL)
+ *   loss[b] = (sum_k costrow[b,k]) / (float)N, the sum in lion_emd_cost's order.  loss f32[B], g1u f32[B,N,3], g2u f32[B,M,3]
+ *   are fully written by plain stores (no pre-zeroing, no atomics); g1u and g2u may each be NULL and that gradient is compiled
+ *   out (both NULL: the match-free cost on the literal auction).  g1u / g2u are d(N * loss)/d(xyz1) / d(xyz2).
+ * loss_backward: one launch; gloss f32[B] (device memory) = d(objective)/d(loss);  c = gloss[b] / (float)N,
+ *   gxyz1[b] = c * g1u[b], gxyz2[b] = c * g2u[b].  A direction is its pair (g1u, gxyz1) / (g2u, gxyz2): both NULL skips it,
+ *   one NULL of a pair or both directions skipped is LION_EINVAL. */
+int lion_emd_loss_forward(const float *xyz1, const float *xyz2, int B, int N, int M, float *loss,
+                          float *g1u, float *g2u, void *ws, size_t ws_bytes, lionStream_t stream);
+int lion_emd_loss_backward(const float *gloss, const float *g1u, const float *g2u, int B, int N, int M,
+                           float *gxyz1, float *gxyz2, lionStream_t stream);
 
 /* ---- D1: one denoiser update, utils/diffusion_pvd.py -------------------------------------
  * DDIM (:451-467): out = x*s + (c*eps + sigma*z).            z may be NULL when sigma == 0.

@@ -47,6 +47,8 @@ SIGNATURES = {
     "lion_emd_cost": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "lion_emd_matchcost": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "lion_emd_matchcost_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "lion_emd_loss_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "lion_emd_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "lion_conv3d_packed_floats": (_sz, [_i, _i]),
     "lion_conv3d_pack_weights": (_i, [_vp, _i, _i, _vp, _vp]),
     "lion_conv3d_k3_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -46,7 +46,7 @@ class Cfg(dict):
 _RELEASED_PRIOR = {
     "ddpm": dict(beta_1=1e-4, beta_T=0.02, sched_mode="linear", num_steps=1000, time_dim=64,
                  dropout=0.1, input_dim=3, model_var_type="fixedlarge", model_mean_type="eps",
-                 loss_type="l1_sum", use_p2_weight=0, p2_k=1.0, p2_gamma=1.0, ddim_step=200),
+                 loss_type="l1_sum", loss_weight_emd=0.02, use_p2_weight=0, p2_k=1.0, p2_gamma=1.0, ddim_step=200),
     "sde": dict(mixed_prediction=False, mixing_logit_init=-6, learn_mixing_logit=1,
                 num_channels_dae=2048, num_cell_per_scale_dae=8, num_scales_dae=2,
                 embedding_dim=128, embedding_scale=1.0, embedding_type="positional", dropout=0.2,

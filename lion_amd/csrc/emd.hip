@@ -77,20 +77,31 @@ __global__ __launch_bounds__(256) void emd_pass1_kernel(const float *__restrict_
   if (wave == 0 && k < n) ratioL[(size_t)b * n + k] = div_rn(remainL[(size_t)b * n + k], suml);
 }
 
-// pass 2 (emd_kernel.cu:83-117)
+// sqdist3(a, b) that also hands out its three differences a - b: the loss kernels' gradient terms reuse them
+__device__ __forceinline__ float sqdist3_diff(float ax, float ay, float az, float bx, float by, float bz, float &dx,
+                                              float &dy, float &dz) {
+  dx = sub_rn(ax, bx); dy = sub_rn(ay, by); dz = sub_rn(az, bz);
+  return add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
+}
+
+// pass 2 (emd_kernel.cu:83-117).  G2 (lion_emd_loss_forward): column l also sums v = sum_k (E * ratioL[k]) * (x2[l] - x1[k])
+// in the order of sumr and, once this level's ratioR[l] is known, g2u[b,l,:] (+)= (2 * ratioR[l]) * v -- pass 3 forms its
+// weight from the same E, so this is its w up to one rounding; the column owns its output (FIRST: the first level stores).
+template <bool G2, bool FIRST>
 __global__ __launch_bounds__(256) void emd_pass2_kernel(const float *__restrict__ xyz1,
                                                         const float *__restrict__ xyz2, int n, int m,
                                                         float level,
                                                         const float *__restrict__ ratioL,
                                                         float *__restrict__ remainR,
-                                                        float *__restrict__ ratioR) {
+                                                        float *__restrict__ ratioR,
+                                                        float *__restrict__ g2u) {
   __shared__ float4 tile[EMD_TILE];
   __shared__ float red[4 * EMD_ROWS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, l = blockIdx.x * EMD_ROWS + lane;
   const float *p1 = xyz1 + (size_t)b * n * 3, *p2 = xyz2 + (size_t)b * m * 3;
   float x2 = 0, y2 = 0, z2 = 0;
   if (l < m) { x2 = p2[l * 3]; y2 = p2[l * 3 + 1]; z2 = p2[l * 3 + 2]; }
-  float sumr = 0;
+  float sumr = 0, vx = 0, vy = 0, vz = 0;
   for (int k0 = 0; k0 < n; k0 += EMD_TILE) {
     const int kn = min(EMD_TILE, n - k0);
     __syncthreads();
@@ -102,17 +113,36 @@ __global__ __launch_bounds__(256) void emd_pass2_kernel(const float *__restrict_
 #pragma unroll 8
     for (int k = wave * EMD_SUB; k < k1; ++k) {
       const float4 v = tile[k];
-      const float w = mul_rn(__expf(lvl_d(level, x2, y2, z2, v.x, v.y, v.z)), v.w);
+      float dx, dy, dz;   // the exponent is lvl_d(level, x2, y2, z2, v.x, v.y, v.z), operation for operation
+      const float w = mul_rn(__expf(mul_rn(level, sqdist3_diff(x2, y2, z2, v.x, v.y, v.z, dx, dy, dz))), v.w);
       sumr = add_rn(sumr, w);
+      if (G2) {
+        vx = add_rn(vx, mul_rn(w, dx));
+        vy = add_rn(vy, mul_rn(w, dy));
+        vz = add_rn(vz, mul_rn(w, dz));
+      }
     }
   }
   EMD_MERGE(red, wave, lane, sumr)
+  if (G2) {
+    EMD_MERGE(red, wave, lane, vx)
+    EMD_MERGE(red, wave, lane, vy)
+    EMD_MERGE(red, wave, lane, vz)
+  }
   if (wave == 0 && l < m) {
     const float rr = remainR[(size_t)b * m + l];
     sumr = mul_rn(sumr, rr);
     const float consumption = fminf(div_rn(rr, add_rn(sumr, 1e-9f)), 1.0f);
-    ratioR[(size_t)b * m + l] = mul_rn(consumption, rr);
+    const float ro = mul_rn(consumption, rr);
+    ratioR[(size_t)b * m + l] = ro;
     remainR[(size_t)b * m + l] = fmaxf(0.0f, sub_rn(rr, sumr));
+    if (G2) {
+      const float c = mul_rn(2.0f, ro);
+      float *g = g2u + ((size_t)b * m + l) * 3;
+      g[0] = FIRST ? mul_rn(c, vx) : add_rn(g[0], mul_rn(c, vx));
+      g[1] = FIRST ? mul_rn(c, vy) : add_rn(g[1], mul_rn(c, vy));
+      g[2] = FIRST ? mul_rn(c, vz) : add_rn(g[2], mul_rn(c, vz));
+    }
   }
 }
 
@@ -160,43 +190,73 @@ __global__ __launch_bounds__(256) void emd_pass3_kernel(const float *__restrict_
 // pass 3 without the match matrix (evaluation path, emd_nograd.py:19-44 only needs the cost): the reference builds
 // match[b][l][k] (16.8 MB per pair at 2048^2, read and rewritten at each of the 10 levels) and then sums
 // match * d^2; the sum over levels commutes with that product, so row k accumulates sum_l w * d^2 on the fly
-// (levels in order) and nothing of size N*M ever reaches memory.
-template <bool FIRST>
+// (levels in order) and nothing of size N*M ever reaches memory.  The gradient of that cost with the match held constant is
+// linear in w as well: G1 sums g = sum_l w * (x1[k] - x2[l]) beside crow and g1u[b,k,:] (+)= 2 * g; the row owns its output.
+// NEXT: pass 1 of the next level walks the same row over the same tiles, so it rides along on this pass's distance -- its
+// exponent mul_rn(next_level, d2), its sum (1e-9 first, the order of emd_pass1_kernel) and its division are emd_pass1_kernel's
+// own operations on remainR as pass 2 of this level left it and on the remainL this row has just written: the same bits.
+template <bool FIRST, bool G1, bool NEXT>
 __global__ __launch_bounds__(256) void emd_pass3_cost_kernel(const float *__restrict__ xyz1,
                                                              const float *__restrict__ xyz2, int n, int m,
-                                                             float level, const float *__restrict__ ratioL,
+                                                             float level, float next_level, float *__restrict__ ratioL,
                                                              const float *__restrict__ ratioR,
+                                                             const float *__restrict__ remainR,
                                                              float *__restrict__ remainL,
-                                                             float *__restrict__ costrow) {
+                                                             float *__restrict__ costrow,
+                                                             float *__restrict__ g1u) {
   __shared__ float4 tile[EMD_TILE];
+  __shared__ float trem[NEXT ? EMD_TILE : 1];
   __shared__ float red[4 * EMD_ROWS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y, k = blockIdx.x * EMD_ROWS + lane;
   const float *p1 = xyz1 + (size_t)b * n * 3, *p2 = xyz2 + (size_t)b * m * 3;
   float x1 = 0, y1 = 0, z1 = 0, rl = 0;
   if (k < n) { x1 = p1[k * 3]; y1 = p1[k * 3 + 1]; z1 = p1[k * 3 + 2]; rl = ratioL[(size_t)b * n + k]; }
-  float suml = 0, crow = 0;
+  float suml = 0, crow = 0, gx = 0, gy = 0, gz = 0, sum1 = wave == 0 ? 1e-9f : 0.f;
   for (int l0 = 0; l0 < m; l0 += EMD_TILE) {
     const int ln = min(EMD_TILE, m - l0);
     __syncthreads();
-    for (int l = tid; l < ln; l += 256)
+    for (int l = tid; l < ln; l += 256) {
       tile[l] = make_float4(p2[(size_t)(l0 + l) * 3], p2[(size_t)(l0 + l) * 3 + 1],
                             p2[(size_t)(l0 + l) * 3 + 2], ratioR[(size_t)b * m + l0 + l]);
+      if (NEXT) trem[l] = remainR[(size_t)b * m + l0 + l];
+    }
     __syncthreads();
     const int l1 = min(ln, (wave + 1) * EMD_SUB);
 #pragma unroll 8
     for (int l = wave * EMD_SUB; l < l1; ++l) {
       const float4 v = tile[l];
-      const float d2 = sqdist3(v.x, v.y, v.z, x1, y1, z1);
+      float dx, dy, dz;   // x2[l] - x1[k]
+      const float d2 = sqdist3_diff(v.x, v.y, v.z, x1, y1, z1, dx, dy, dz);
       const float w = mul_rn(mul_rn(__expf(mul_rn(level, d2)), rl), v.w);
       suml = add_rn(suml, w);
       crow = add_rn(crow, mul_rn(d2, w));
+      if (G1) {   // g + w * (x1[k] - x2[l]): the negation is exact, so subtracting w * (x2[l] - x1[k]) is the same bits
+        gx = sub_rn(gx, mul_rn(w, dx));
+        gy = sub_rn(gy, mul_rn(w, dy));
+        gz = sub_rn(gz, mul_rn(w, dz));
+      }
+      if (NEXT) sum1 = add_rn(sum1, mul_rn(__expf(mul_rn(next_level, d2)), trem[l]));
     }
   }
   EMD_MERGE(red, wave, lane, suml)
   EMD_MERGE(red, wave, lane, crow)
+  if (G1) {
+    EMD_MERGE(red, wave, lane, gx)
+    EMD_MERGE(red, wave, lane, gy)
+    EMD_MERGE(red, wave, lane, gz)
+  }
+  if (NEXT) { EMD_MERGE(red, wave, lane, sum1) }
   if (wave == 0 && k < n) {
-    remainL[(size_t)b * n + k] = fmaxf(0.0f, sub_rn(remainL[(size_t)b * n + k], suml));
+    const float rem = fmaxf(0.0f, sub_rn(remainL[(size_t)b * n + k], suml));
+    remainL[(size_t)b * n + k] = rem;
+    if (NEXT) ratioL[(size_t)b * n + k] = div_rn(rem, sum1);   // pass 1 of the next level (emd_kernel.cu:50-81)
     costrow[(size_t)b * n + k] = FIRST ? crow : add_rn(costrow[(size_t)b * n + k], crow);
+    if (G1) {
+      float *g = g1u + ((size_t)b * n + k) * 3;
+      g[0] = FIRST ? mul_rn(2.0f, gx) : add_rn(g[0], mul_rn(2.0f, gx));
+      g[1] = FIRST ? mul_rn(2.0f, gy) : add_rn(g[1], mul_rn(2.0f, gy));
+      g[2] = FIRST ? mul_rn(2.0f, gz) : add_rn(g[2], mul_rn(2.0f, gz));
+    }
   }
 }
 
@@ -390,7 +450,8 @@ __global__ __launch_bounds__(256) void emd_fast_pass31_kernel(const float *__res
     }
 }
 
-// cost[b] = sum_k costrow[b][k]: 256 strided partials, then a fixed tree (deterministic)
+// cost[b] = sum_k costrow[b][k]: 256 strided partials, then a fixed tree (deterministic); PER_POINT: that sum / (float)n
+template <bool PER_POINT>
 __global__ __launch_bounds__(256) void emd_costrow_sum_kernel(const float *__restrict__ costrow, int n,
                                                               float *__restrict__ cost) {
   __shared__ float red[4];
@@ -400,7 +461,20 @@ __global__ __launch_bounds__(256) void emd_costrow_sum_kernel(const float *__res
   for (int q = 32; q >= 1; q >>= 1) s = add_rn(s, __shfl_xor(s, q, 64));
   if (lane == 0) red[wave] = s;
   __syncthreads();
-  if (tid == 0) cost[b] = add_rn(add_rn(red[0], red[1]), add_rn(red[2], red[3]));
+  if (tid == 0) {
+    const float c = add_rn(add_rn(red[0], red[1]), add_rn(red[2], red[3]));
+    cost[b] = PER_POINT ? div_rn(c, (float)n) : c;
+  }
+}
+
+// lion_emd_loss_backward: gxyz = (gloss[b] / n) * gu, the direction of a NULL output is skipped
+__global__ __launch_bounds__(256) void emd_loss_bwd_kernel(const float *__restrict__ gloss, const float *__restrict__ g1u,
+                                                           const float *__restrict__ g2u, int n, int m,
+                                                           float *__restrict__ gxyz1, float *__restrict__ gxyz2) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  const float c = div_rn(gloss[b], (float)n);
+  if (gxyz1 && i < n * 3) gxyz1[(size_t)b * n * 3 + i] = mul_rn(c, g1u[(size_t)b * n * 3 + i]);
+  if (gxyz2 && i < m * 3) gxyz2[(size_t)b * m * 3 + i] = mul_rn(c, g2u[(size_t)b * m * 3 + i]);
 }
 
 // matchcost (emd_kernel.cu:199-241): per-k partial sums over l, reduced per block into
@@ -555,7 +629,8 @@ int lion_emd_approxmatch(const float *xyz1, const float *xyz2, int B, int N, int
     if (j == -2) level = 0.f;
     if (int e = lion_launch<emd_pass1_kernel>(gn, 256, 0, st, xyz1, xyz2, N, M, level, remainL, remainR, ratioL))
       return e;
-    if (int e = lion_launch<emd_pass2_kernel>(gm, 256, 0, st, xyz1, xyz2, N, M, level, ratioL, remainR, ratioR))
+    if (int e = lion_launch<emd_pass2_kernel<false, false>>(gm, 256, 0, st, xyz1, xyz2, N, M, level, ratioL, remainR, ratioR,
+                                                            nullptr))
       return e;
     const int e3 = lion_with_flags(j == 7, [&](auto FIRST) {
       return lion_launch<emd_pass3_kernel<decltype(FIRST)::value>>(gn, 256, 0, st, xyz1, xyz2, N, M, level, ratioL, ratioR,
@@ -607,7 +682,64 @@ int lion_emd_cost(const float *xyz1, const float *xyz2, int B, int N, int M, flo
                              : pass31(BoolC<false>{}, BoolC<true>{}, next_ratio);
     if (e31) return e31;
   }
-  return lion_launch<emd_costrow_sum_kernel>(B, 256, 0, st, costrow, N, cost);
+  return lion_launch<emd_costrow_sum_kernel<false>>(B, 256, 0, st, costrow, N, cost);
+}
+
+// The literal auction of lion_emd_approxmatch with pass 3 in its cost form: loss = cost / N and, where asked for, the two
+// gradients of N * loss with the match held constant, accumulated level by level (layout and order: include/lion_hip.h).
+int lion_emd_loss_forward(const float *xyz1, const float *xyz2, int B, int N, int M, float *loss, float *g1u, float *g2u,
+                          void *ws, size_t ws_bytes, lionStream_t stream) {
+  if (!xyz1 || !xyz2 || !loss || B <= 0 || N <= 0 || M <= 0) return LION_EINVAL;
+  if (!ws || ws_bytes < lion_emd_workspace_bytes(B, N, M)) return LION_EWORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float *remainL = static_cast<float *>(ws);
+  float *remainR = remainL + (size_t)B * N;
+  float *ratioL = remainR + (size_t)B * M;
+  float *ratioR = ratioL + (size_t)B * N;
+  float *costrow = ratioR + (size_t)B * M + (size_t)B * lion_cdiv(N, 256);
+  float multiL, multiR; // emd_kernel.cu:27-33 (integer division)
+  if (N >= M) { multiL = 1.f; multiR = (float)(N / M); }
+  else { multiL = (float)(M / N); multiR = 1.f; }
+  const int nmax = N > M ? N : M;
+  if (int e = lion_launch<emd_init_kernel>(dim3(lion_cdiv(nmax, 256), B), 256, 0, st, N, M, multiL, multiR, remainL,
+                                           remainR))
+    return e;
+  const dim3 gn(lion_cdiv(N, EMD_ROWS), B), gm(lion_cdiv(M, EMD_ROWS), B);
+  auto level_of = [](int j) { return j == -2 ? 0.f : -powf(4.0f, (float)j); };   // :45-48
+  // pass 1 of the first level, then per level [pass 2, pass 3 + pass 1 of the next level]
+  if (int e = lion_launch<emd_pass1_kernel>(gn, 256, 0, st, xyz1, xyz2, N, M, level_of(7), remainL, remainR, ratioL))
+    return e;
+  for (int j = 7; j >= -2; --j) {
+    const float level = level_of(j);
+    auto pass2 = [&](auto G2, auto FIRST) {
+      return lion_launch<emd_pass2_kernel<decltype(G2)::value, decltype(FIRST)::value>>(gm, 256, 0, st, xyz1, xyz2, N, M, level,
+                                                                                      ratioL, remainR, ratioR, g2u);
+    };
+    const int e2 = g2u ? lion_with_flags(j == 7, [&](auto FIRST) { return pass2(BoolC<true>{}, FIRST); })
+                       : pass2(BoolC<false>{}, BoolC<false>{});   // lion_emd_approxmatch's own instantiation
+    if (e2) return e2;
+    auto pass31 = [&](auto FIRST, auto NEXT) {
+      return lion_with_flags(g1u != nullptr, [&](auto G1) {
+        return lion_launch<emd_pass3_cost_kernel<decltype(FIRST)::value, decltype(G1)::value, decltype(NEXT)::value>>(
+            gn, 256, 0, st, xyz1, xyz2, N, M, level, NEXT ? level_of(j - 1) : 0.f, ratioL, ratioR, remainR, remainL, costrow,
+            g1u);
+      });
+    };
+    const int e3 = j == -2  ? pass31(BoolC<false>{}, BoolC<false>{})   // the last level prepares no next one
+                   : j == 7 ? pass31(BoolC<true>{}, BoolC<true>{})
+                            : pass31(BoolC<false>{}, BoolC<true>{});
+    if (e3) return e3;
+  }
+  return lion_launch<emd_costrow_sum_kernel<true>>(B, 256, 0, st, costrow, N, loss);
+}
+
+int lion_emd_loss_backward(const float *gloss, const float *g1u, const float *g2u, int B, int N, int M, float *gxyz1,
+                           float *gxyz2, lionStream_t stream) {
+  if (!gloss || B <= 0 || N <= 0 || M <= 0) return LION_EINVAL;
+  if (!g1u != !gxyz1 || !g2u != !gxyz2 || (!gxyz1 && !gxyz2)) return LION_EINVAL;   // half a pair; nothing to do
+  const int cols = 3 * (gxyz1 && gxyz2 ? (N > M ? N : M) : gxyz1 ? N : M);
+  return lion_launch<emd_loss_bwd_kernel>(dim3(lion_cdiv(cols, 256), B), 256, 0, static_cast<hipStream_t>(stream), gloss, g1u,
+                                          g2u, N, M, gxyz1, gxyz2);
 }
 
 int lion_emd_matchcost(const float *xyz1, const float *xyz2, const float *match, int B, int N, int M,

@@ -6,7 +6,7 @@ from torch.amp import custom_fwd, custom_bwd
 from . import _lib
 
 __all__ = ["emd_ext", "emd_cuda", "earth_mover_distance", "earth_mover_distance_nograd",
-           "EarthMoverDistanceFunction", "EarthMoverDistanceFunctionNoGrad"]
+           "EarthMoverDistanceFunction", "EarthMoverDistanceFunctionNoGrad", "EmdLossFunction", "emd_loss"]
 
 
 def _ws(b, n, m, dev):
@@ -84,6 +84,46 @@ class EarthMoverDistanceFunctionNoGrad(torch.autograd.Function):
         ws, nbytes = _ws(b, n, m, xyz1.device)
         _lib.call("lion_emd_cost", xyz1, xyz2, b, n, m, cost, ws, nbytes)
         return cost
+
+
+class EmdLossFunction(torch.autograd.Function):
+    """(pred [B,N,3], target [B,M,3]) -> loss [B] = matchcost / N on lion_emd_approxmatch's auction, the match held constant
+    in the gradient (EarthMoverDistanceFunction's value and semantics) -- without the [B,M,N] match matrix: one call of
+    lion_emd_loss_forward accumulates the cost and, for the inputs that need a gradient, d(N * loss)/d(input) level by
+    level; those [B,N,3] / [B,M,3] buffers are what is saved, and the backward is one elementwise launch.  Every output is a
+    torch.empty buffer its kernel writes in full; no atomics, no host synchronisation (orders: include/lion_hip.h)."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, pred, target):
+        _lib.require_cuda(pred, target)
+        b, n, _ = pred.shape
+        m = target.shape[1]
+        loss = torch.empty((b,), device=pred.device, dtype=torch.float32)
+        g1u = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        g2u = torch.empty_like(target) if ctx.needs_input_grad[1] else None
+        ws, nbytes = _ws(b, n, m, pred.device)
+        _lib.call("lion_emd_loss_forward", pred, target, b, n, m, loss, g1u, g2u, ws, nbytes)
+        ctx.save_for_backward(g1u, g2u)
+        ctx.dims = (b, n, m)
+        return loss
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, gloss):
+        g1u, g2u = ctx.saved_tensors
+        gpred = None if g1u is None else torch.empty_like(g1u)
+        gtarget = None if g2u is None else torch.empty_like(g2u)
+        _lib.call("lion_emd_loss_backward", gloss.contiguous(), g1u, g2u, *ctx.dims, gpred, gtarget)
+        return gpred, gtarget
+
+
+def emd_loss(pred, target):
+    """EMD reconstruction loss per sample, [B] (utils/model_helper.py:82-96: earth_mover_distance(pred, target,
+    transpose=False)); pred [B,N,3], target [B,M,3].  Without grad mode no gradient buffer is allocated or accumulated."""
+    if not torch.is_grad_enabled():   # a Function's needs_input_grad ignores the grad mode
+        pred, target = pred.detach(), target.detach()
+    return EmdLossFunction.apply(pred.contiguous(), target.contiguous())
 
 
 def _prep(xyz1, xyz2, transpose):

@@ -7,11 +7,13 @@ from . import import_model
 from .distributions import Normal
 
 
-def loss_fn(predict, target, loss_type, point_dim, batch_size):
-    """utils/model_helper.py:17-75, per sample [B]: the pointwise variants 'mse_sum', 'l1_sum', 'mse', 'l1' and the Chamfer
+def loss_fn(predict, target, loss_type, point_dim, batch_size, loss_weight_emd=0.02):
+    """utils/model_helper.py:17-96, per sample [B]: the pointwise variants 'mse_sum', 'l1_sum', 'mse', 'l1'; the Chamfer
     variants 'chamfer' (:49-52, mean over the points of both directions) and 'cd_sum' (:43-47, their sum), which need no point
-    correspondence between prediction and target (lion_amd.chamfer3d.chamfer_loss: HIP only, gradient without atomics).
-    Everything else ('emd', 'chamfer_emd', 'cd1_sum_emd', 'cd1_sum', 'dcd', 'l1_cd') raises NotImplementedError."""
+    correspondence between prediction and target (lion_amd.chamfer3d.chamfer_loss: HIP only, gradient without atomics); and
+    'emd' (:94-96) / 'chamfer_emd' (:88-93, chamfer + loss_weight_emd * emd) on lion_amd.emd.emd_loss (HIP only, no match
+    matrix).  The reference's get_loss never forwards ddpm.loss_weight_emd to this function; Model.get_loss here does (same
+    default, 0.02).  Everything else ('cd1_sum_emd', 'cd1_sum', 'dcd', 'l1_cd') raises NotImplementedError."""
     if loss_type == 'mse_sum':
         return ((predict - target) ** 2).view(batch_size, -1).sum(1)
     if loss_type == 'l1_sum':
@@ -24,6 +26,15 @@ def loss_fn(predict, target, loss_type, point_dim, batch_size):
         from ..chamfer3d import chamfer_loss
         return chamfer_loss(predict.view(batch_size, -1, point_dim), target.view(batch_size, -1, point_dim),
                             "mean" if loss_type == 'chamfer' else "sum")
+    if loss_type in ('emd', 'chamfer_emd'):
+        if not (predict.is_cuda and target.is_cuda):   # a RuntimeError, as everywhere: the product has no CPU fallback
+            raise NotImplementedError(f"{loss_type}: no CPU path")
+        from ..chamfer3d import chamfer_loss
+        from ..emd import emd_loss
+        pred, tgt = predict.view(batch_size, -1, point_dim), target.view(batch_size, -1, point_dim)
+        if loss_type == 'emd':
+            return emd_loss(pred, tgt)
+        return chamfer_loss(pred, tgt, "mean") + loss_weight_emd * emd_loss(pred, tgt)
     raise NotImplementedError(loss_type)
 
 
@@ -169,7 +180,7 @@ class Model(nn.Module):
         assert x.shape[2] == self.input_dim
         output = self.recont(noisy_input if noisy_input is not None else x, target=x, class_label=class_label)
         rec_loss = loss_fn(output['x_0_pred'], output['x_0_target'], a.ddpm.loss_type,
-                           self.input_dim, batch_size).mean()
+                           self.input_dim, batch_size, getattr(a.ddpm, 'loss_weight_emd', 0.02)).mean()
         output['print/loss_0'] = rec_loss
         output['rec_loss'] = rec_loss
         weighted, plain = [], []
