@@ -391,6 +391,39 @@ int lion_voxel_surface_points_keyed(const float *x, int B, int N, int r, const u
                                     void *ws, size_t ws_bytes, lionStream_t stream);
 int lion_perturb_points_keyed(int mode, const float *x, int B, int N, float p0, const uint32_t *keys, uint32_t stream_id,
                               float *out, lionStream_t stream);
+/* Voxel grids as inputs of guided synthesis and the voxel IoU (csrc/perturb.hip): the occupancy grid that
+ * lion_voxel_surface_points_keyed builds and discards, as an object of its own.  The contract is the one above: one rounding
+ * per written operation, integer arithmetic for everything that selects or counts, no atomics, one workgroup per cloud, no
+ * workspace, no allocation, no host synchronisation (capturable); a sample's output depends on neither B nor b.
+ *   Frame f32[4] = (lo_x, lo_y, lo_z, side): the cube a grid covers.  s = side/r, inv = r/side.  A cloud's OWN frame is the box
+ *   above: lo = c - h per axis, side = 2h -- s and inv then are the very values lion_voxel_surface_points_keyed uses.
+ *   Grid u8[B][r][r][r], flat id x*r*r + y*r + z; a non-zero byte is an occupied voxel (the memory of a torch.bool tensor;
+ *   inputs may hold any non-zero byte, outputs hold 0 or 1).
+ * lion_voxel_occupancy: grid = the voxels of cloud x f32[B][N][3] in a frame: point p sets voxel i_axis =
+ *   clamp((int)floorf((p - lo)*inv), 0, r-1) -- ALWAYS clamped, in the cloud's own frame (frame_in NULL; there the grid is exactly
+ *   the occupancy of lion_voxel_surface_points_keyed) or in a given one (frame_in f32[B][4] on the device).  frame_out f32[B][4]
+ *   (may be NULL) receives the frame that was used; clamped_out i32[B] (may be NULL) the number of points whose index the clamp
+ *   changed on at least one axis.  LION_EINVAL before any launch: x or grid NULL, B <= 0 or B > 65535, N <= 0, r < 1 or r > 32.
+ * lion_voxel_surface_points_grid_keyed: out f32[B][K][3] = K points on the exposed faces of the grid, in frame f32[B][4]:
+ *   faces, their numbering, point k's draw at counter (k, LION_VOXEL_STEP_WORD, stream_id) and out = lo + t*s exactly as in
+ *   lion_voxel_surface_points_keyed, so the grid and frame lion_voxel_occupancy reports for a cloud reproduce that entry point's
+ *   output to the bit.  faces_out[b] = F.  An empty grid has F = 0 and every one of its K points is the frame's centre,
+ *   lo + side*0.5 per axis.  LION_EINVAL before any launch: grid, frame, keys or out NULL (faces_out may be NULL), B <= 0 or
+ *   B > 65535, K <= 0, r < 1 or r > 32.
+ * lion_voxel_iou: counts i32[B][2] = (|A and B|, |A or B|) over the r^3 voxels of grids a and b, iou f32[B] (may be NULL) =
+ *   (float)inter / (float)union, correctly rounded, and 1 where the union is empty.  LION_EINVAL before any launch: a, b or
+ *   counts NULL, B <= 0 or B > 65535, r < 1 or r > 32.
+ * Frames live on the device and cannot be vetted by the host: whatever a frame holds (a zero, negative, NaN or infinite
+ * side), every LDS and global index is clamped into range before it is used -- a bad frame gives a meaningless grid or
+ * meaningless points, never an access out of range. */
+int lion_voxel_occupancy(const float *x, int B, int N, int r, const float *frame_in /* device f32[B][4] or NULL = own frame */,
+                         uint8_t *grid, float *frame_out /* may be NULL */, int32_t *clamped_out /* may be NULL */,
+                         lionStream_t stream);
+int lion_voxel_surface_points_grid_keyed(const uint8_t *grid, const float *frame, int B, int r, const uint32_t *keys,
+                                         uint32_t stream_id, int K, float *out, int32_t *faces_out /* may be NULL */,
+                                         lionStream_t stream);
+int lion_voxel_iou(const uint8_t *a, const uint8_t *b, int B, int r, int32_t *counts /* i32[B][2] = inter, union */,
+                   float *iou /* f32[B], may be NULL */, lionStream_t stream);
 /* x f32[B][N][D] (point-major latent; 3 <= D <= 8) -> channel-major all f32[B][D][N], coords f32[B][3][N] (rows 0-2),
  * rest f32[B][D-3][N]; each output may be NULL: the view / permute / slice / contiguous head of
  * models/latent_points_ada_localprior.py:72-84 + models/latent_points_ada.py:118-121 in one launch. */

@@ -7,7 +7,10 @@ Sub-packages:
   models/      host-side mirror of models.pvcnn2_ada / latent_points_ada / score_sde / vae_adain / lion
   diffusion    DiffusionDiscretized (utils/diffusion_pvd.py) with a fused per-step update
   editing      diffuse-denoise of an encoded shape (trainers/denoise_pts.py) on the captured chain; voxel-guided synthesis
-  perturb      the inputs of guided synthesis: voxel-surface points, normal / uniform / outlier corruption, keyed per sample
+               from a cloud or from a voxel grid
+  perturb      the inputs of guided synthesis: voxel-surface points of a cloud or of a given grid, a cloud's occupancy grid,
+               normal / uniform / outlier corruption, keyed per sample
+  metrics      MMD / COV / 1-NNA under Chamfer and EMD, JSD, and the voxel IoU of guided synthesis
   dist         data-parallel gradient step (utils/utils.py:717-770) over RCCL
 
 Nothing here falls back to a CPU implementation: without the built HIP library every

@@ -167,6 +167,9 @@ SIGNATURES = {
     "lion_voxel_surface_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "lion_voxel_surface_points_keyed": (_i, [_vp, _i, _i, _i, _vp, C.c_uint32, _i, _vp, _vp, _vp, _sz, _vp]),
     "lion_perturb_points_keyed": (_i, [_i, _vp, _i, _i, _f, _vp, C.c_uint32, _vp, _vp]),
+    "lion_voxel_occupancy": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lion_voxel_surface_points_grid_keyed": (_i, [_vp, _vp, _i, _i, _vp, C.c_uint32, _i, _vp, _vp, _vp]),
+    "lion_voxel_iou": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "lion_latent_unpack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "lion_concat_broadcast": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "lion_three_nn_interpolate_cat_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -8,7 +8,8 @@ call of the same batch shape captured is the one replayed here.  One ``time_star
 reference.  With ``solver_steps=S`` the tail is instead at most S replays of the few-step solver's captured step
 (``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
 
-``voxel_guided`` is the recipe on the surface of the input's voxelisation (``perturb.voxel_surface_points``).
+``voxel_guided`` is the recipe on the surface of the input's voxelisation (``perturb.voxel_surface_points``);
+``voxel_grid_guided`` starts from a voxel grid instead of a cloud.  Both can report the voxel IoU of input and output.
 """
 from __future__ import annotations
 
@@ -144,16 +145,50 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
 
 
 @torch.no_grad()
-def voxel_guided(vae, dae, diffusion, x, resolution, time_start, **diffuse_denoise_kwargs):
+def voxel_guided(vae, dae, diffusion, x, resolution, time_start, *, iou=False, **diffuse_denoise_kwargs):
     """Voxel-guided synthesis: x [B, N, 3] -> (points [B, N, 3], info).  The input is replaced by N points on the surface of
     its voxelisation at `resolution` (perturb.voxel_surface_points) and that cloud goes through diffuse_denoise(vae, dae,
     diffusion, ., time_start, **diffuse_denoise_kwargs), which is not changed.  `seeds` (or `seed`) of the keyword arguments
     address both: sample b's voxel points are drawn under seeds[b] at LION_VOXEL_STEP_WORD, a step word no draw of
     diffuse_denoise uses, so the two never share a counter.  info is diffuse_denoise's with 'input' (the voxel-surface cloud
-    that was denoised) and 'faces' (int32[B], the exposed faces per cloud)."""
+    that was denoised) and 'faces' (int32[B], the exposed faces per cloud).
+    iou=True adds the paper's measure of the experiment, the voxel IoU between the input's voxels and the voxelised output in
+    the input's frame: 'input grid' and 'frame' (perturb.voxel_occupancy(x, resolution)), 'iou' (float32[B]) and 'iou_counts'
+    (int32[B, 2]: intersection, union) -- three more launches; the default issues none and adds no key."""
     from . import perturb
     pts, made = perturb.voxel_surface_points(x, resolution, x.shape[1], seeds=diffuse_denoise_kwargs.get("seeds"),
                                              seed=diffuse_denoise_kwargs.get("seed"))
     points, info = diffuse_denoise(vae, dae, diffusion, pts, time_start, **diffuse_denoise_kwargs)
     info["input"], info["faces"] = pts, made["faces"]
+    if iou:
+        grid, occ = perturb.voxel_occupancy(x, resolution)
+        _add_iou(info, grid, occ["frame"], points)
+    return points, info
+
+
+def _add_iou(info, grid, frame, points):
+    """info['iou'], ['iou_counts'], ['input grid'], ['frame']: the output `points` against the input's grid, in its frame"""
+    from . import metrics
+    value, m = metrics.voxel_iou(grid, points, frame=frame)
+    info["input grid"], info["frame"], info["iou"] = grid, frame, value
+    info["iou_counts"] = m["counts"]
+
+
+@torch.no_grad()
+def voxel_grid_guided(vae, dae, diffusion, grid, time_start, frame=None, num_points=2048, iou=False,
+                      **diffuse_denoise_kwargs):
+    """Voxel-guided synthesis from voxels: grid [B, r, r, r] (bool or uint8, r <= 32; an editor's, a scan's, a coarse shape's)
+    -> (points [B, num_points, 3], info).  num_points points are drawn on the exposed faces of the grid, placed in `frame`
+    (perturb.voxel_surface_points_from_grid; None: the cube [-1, 1]^3), and that cloud goes through diffuse_denoise(vae, dae,
+    diffusion, ., time_start, **diffuse_denoise_kwargs) under the same `seeds` / `seed`, as in voxel_guided.  info is
+    diffuse_denoise's with 'input' (the cloud that was denoised), 'faces' (int32[B]), 'input grid' and 'frame' (float32[B, 4]
+    on the device).  iou=True adds 'iou' (float32[B]: the voxel IoU of the input grid and the output voxelised in the same
+    frame, metrics.voxel_iou) and 'iou_counts' (int32[B, 2]: intersection, union)."""
+    from . import perturb
+    pts, made = perturb.voxel_surface_points_from_grid(grid, frame, num_points, seeds=diffuse_denoise_kwargs.get("seeds"),
+                                                       seed=diffuse_denoise_kwargs.get("seed"))
+    points, info = diffuse_denoise(vae, dae, diffusion, pts, time_start, **diffuse_denoise_kwargs)
+    info["input"], info["faces"], info["input grid"], info["frame"] = pts, made["faces"], grid, made["frame"]
+    if iou:
+        _add_iou(info, grid, made["frame"], points)
     return points, info

@@ -6,7 +6,8 @@ Differences: a pair matrix is evaluated in large batches (``pair_batch`` pairs p
 of one sample against N_ref/2 references), rows of the matrix can be sharded over ranks and
 all-gathered (the reference computes everything on rank 0, base_trainer.py:491-495), and M_rs is
 computed once (the reference computes it twice, :481-490 / :524-533).  JSD (CPU numpy/sklearn in the
-reference) is out of scope."""
+reference) is out of scope.  ``voxel_iou`` (no counterpart in the released tree) is the measure of the paper's
+voxel-guided synthesis experiment, on kernels of its own (csrc/perturb.hip)."""
 from __future__ import annotations
 
 import torch
@@ -198,3 +199,59 @@ def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
     """JSD between the voxel-occupancy histograms of two sets of clouds in the unit sphere (reference :587-598)."""
     return jensen_shannon_divergence(occupancy_histogram(sample_pcs, resolution, True)[1],
                                      occupancy_histogram(ref_pcs, resolution, True)[1])
+
+
+# ---- voxel IoU: the measure of the paper's voxel-guided synthesis experiment (DESIGN.md 4.6.8) ------------------------------
+
+def _is_grid(t):
+    return isinstance(t, torch.Tensor) and t.dim() == 4 and t.dtype in (torch.bool, torch.uint8)
+
+
+@torch.no_grad()
+def voxel_iou(a, b, resolution=None, frame=None):
+    """(iou float32 [B], info): per sample the intersection over union of two voxel occupancies, |A and B| / |A or B| over
+    the r^3 voxels (1 where both are empty).  Each of a and b is a cloud, float32 [B, N, >= 3], or a grid, bool / uint8
+    [B, r, r, r] (perturb.voxel_occupancy, perturb.voxel_surface_points_from_grid).  A cloud is voxelised at `resolution` in
+    `frame` (perturb.voxel_occupancy: a device float32 [B, 4] tensor or a host frame; points outside the frame are clamped into
+    its boundary voxels).  frame=None: if a is a cloud, a's own frame serves both arguments -- voxel_iou(input, output, r)
+    measures an output in the input's frame; a grid a beside a cloud b needs the frame the grid lives in.  With a grid among
+    the arguments `resolution` may be None (the grid's) and must agree with it otherwise; two grids need equal resolutions.
+    info: 'intersection' and 'union' (int32 [B] on the device, exact; the columns of 'counts', int32 [B, 2]), 'frame' (the device frame the clouds were voxelised in,
+    None for two grids without one) and 'clamped' (a pair, one entry per argument: int32 [B] on the device for a cloud -- its
+    points beyond the frame -- and None for a grid).
+    Launches: one for two grids, two for a grid and a cloud, three for two clouds; nothing else runs on the device in between
+    and nothing synchronises with the host.  Exact arithmetic: include/lion_hip.h, lion_voxel_occupancy / lion_voxel_iou.
+    ValueError before the device is touched: an argument that is neither a cloud nor a grid, different batch sizes, a
+    resolution outside 1 ... 32, missing, or different from a grid's, a grid a with a cloud b and no frame, a bad frame."""
+    from . import _lib, perturb
+    who = "voxel_iou"
+    shapes = [perturb._grid_shape(t, who) if _is_grid(t) else perturb._cloud_shape(t, who) for t in (a, b)]
+    grids = [_is_grid(a), _is_grid(b)]
+    B = shapes[0][0]
+    if shapes[1][0] != B:
+        raise ValueError(f"{who}: {B} and {shapes[1][0]} samples")
+    given = sorted({s[1] for s, g in zip(shapes, grids) if g})     # the grids' resolutions
+    if len(given) > 1:
+        raise ValueError(f"{who}: grids of resolutions {shapes[0][1]} and {shapes[1][1]}")
+    if resolution is None and not given:
+        raise ValueError(f"{who}: resolution = None: two clouds need one")
+    r = given[0] if resolution is None else perturb._resolution(resolution, who)
+    if given and given[0] != r:
+        raise ValueError(f"{who}: resolution = {r} beside a grid of resolution {given[0]}")
+    if grids[0] and not grids[1] and frame is None:
+        raise ValueError(f"{who}: a grid beside a cloud needs the frame the grid lives in")
+    frame = perturb._host_frame(frame, B, who)
+    made, clamped = [None, None], [None, None]
+    for i, t in enumerate((a, b)):
+        if grids[i]:
+            _lib.require_cuda(t)
+            made[i] = t
+        else:
+            made[i], info = perturb.voxel_occupancy(t, r, frame)
+            frame, clamped[i] = info["frame"], info["clamped"]     # a's own frame (or the given one, now on the device) serves b
+    counts = torch.empty((B, 2), device=made[0].device, dtype=torch.int32)
+    iou = torch.empty((B,), device=made[0].device, dtype=torch.float32)
+    _lib.call("lion_voxel_iou", made[0], made[1], B, r, counts, iou)
+    if frame is not None and not frame.is_cuda:
+        frame = frame.to(iou.device)
+    return iou, {"intersection": counts[:, 0], "union": counts[:, 1], "counts": counts, "frame": frame, "clamped": tuple(clamped)}

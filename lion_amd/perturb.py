@@ -1,7 +1,9 @@
 """Perturbed inputs for guided synthesis: the clouds ``editing.diffuse_denoise`` denoises and ``training.vae_forward_backward(...,
 noisy_input=)`` fine-tunes the encoder on -- points on the surface of a cloud's voxelisation, and the three corruptions of the
 paper's denoising experiments (normal noise, uniform noise, outliers).  Made on the device from clouds resident in HBM
-(csrc/perturb.hip), one launch each, nothing synchronises with the host.
+(csrc/perturb.hip), one launch each, nothing synchronises with the host.  The voxelisation is also an
+object of its own: ``voxel_occupancy`` returns a cloud's grid and frame, ``voxel_surface_points_from_grid``
+starts from a grid that is given (an editor's, a scan's), ``metrics.voxel_iou`` compares grids.
 
 Every sample is addressed by its own 64-bit key: sample b's output under seeds[b] is the same bits alone, first
 or last of a batch and beside any batchmates.  The draws come from the chain's Philox generator at reserved step words of their
@@ -16,7 +18,8 @@ import torch
 from . import _lib, diffusion_ops
 from . import chain as _chain
 
-__all__ = ["voxel_surface_points", "add_noise", "KINDS", "MAX_RESOLUTION"]
+__all__ = ["voxel_surface_points", "voxel_occupancy", "voxel_surface_points_from_grid", "add_noise", "KINDS", "MAX_RESOLUTION",
+           "UNIT_FRAME"]
 
 # the step words of include/lion_hip.h: beside chain.START_STEP_WORD / DIFFUSE_STEP_WORD, above every chain step's row index
 VOXEL_STEP_WORD, PERTURB_STEP_WORD = 0xFFFFFFFD, 0xFFFFFFFC
@@ -71,12 +74,11 @@ def voxel_surface_points(x, resolution, num_points=None, *, seeds=None, seed=Non
     x not a float32 [B, N, >= 3] tensor."""
     who = "voxel_surface_points"
     B, N = _cloud_shape(x, who)
-    if isinstance(resolution, bool) or not isinstance(resolution, numbers.Integral) or not 1 <= resolution <= MAX_RESOLUTION:
-        raise ValueError(f"{who}: resolution = {resolution!r}: an int in [1, {MAX_RESOLUTION}]")
+    r = _resolution(resolution, who)
     K = N if num_points is None else num_points
     if isinstance(K, bool) or not isinstance(K, numbers.Integral) or K < 1:
         raise ValueError(f"{who}: num_points = {num_points!r}: None or an int >= 1")
-    r, K = int(resolution), int(K)
+    K = int(K)
     keys = _keys(seeds, seed, B, who)
     xyz = _xyz(x)
     words = diffusion_ops._device_keys(keys, B, xyz.device, who)
@@ -86,6 +88,111 @@ def voxel_surface_points(x, resolution, num_points=None, *, seeds=None, seed=Non
     ws = torch.empty((ws_bytes,), device=xyz.device, dtype=torch.uint8) if ws_bytes else None
     _lib.call("lion_voxel_surface_points_keyed", xyz, B, N, r, words, int(stream_id), K, out, faces, ws, ws_bytes)
     return out, {"faces": faces, "seeds": keys}
+
+
+def _resolution(resolution, who):
+    if isinstance(resolution, bool) or not isinstance(resolution, numbers.Integral) or not 1 <= resolution <= MAX_RESOLUTION:
+        raise ValueError(f"{who}: resolution = {resolution!r}: an int in [1, {MAX_RESOLUTION}]")
+    return int(resolution)
+
+
+def _grid_shape(grid, who):
+    """(B, r) of an occupancy grid: a bool or uint8 [B, r, r, r] tensor, 1 <= r <= 32"""
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 4 or grid.shape[0] < 1 or len(set(grid.shape[1:])) != 1:
+        raise ValueError(f"{who}: a grid is [B, r, r, r], got {tuple(getattr(grid, 'shape', ()))!r}")
+    if grid.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{who}: a grid is bool or uint8 (non-zero: occupied), got {grid.dtype}")
+    if not 1 <= grid.shape[1] <= MAX_RESOLUTION:
+        raise ValueError(f"{who}: grid resolution {grid.shape[1]}: in [1, {MAX_RESOLUTION}]")
+    return int(grid.shape[0]), int(grid.shape[1])
+
+
+def _host_frame(frame, B, who):
+    """None, a device f32[B, 4] tensor (passed on: the host cannot vet it), or a host frame -- 4 numbers for the whole batch or
+    B x 4, a sequence or a CPU tensor -- validated here (finite, side > 0) and returned as a CPU f32[B, 4] tensor to upload"""
+    if frame is None:
+        return None
+    if isinstance(frame, torch.Tensor) and frame.is_cuda:
+        if frame.dtype != torch.float32 or tuple(frame.shape) != (B, 4):
+            raise ValueError(f"{who}: a device frame is float32 [{B}, 4], got {frame.dtype} {tuple(frame.shape)}")
+        return frame
+    try:
+        f = torch.as_tensor(frame, dtype=torch.float64, device="cpu")
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{who}: frame = {frame!r}: (lo_x, lo_y, lo_z, side), one for the batch or one per sample") from e
+    if tuple(f.shape) == (4,):
+        f = f.expand(B, 4)
+    if tuple(f.shape) != (B, 4):
+        raise ValueError(f"{who}: frame of shape {tuple(f.shape)}: 4 numbers or [{B}, 4]")
+    f = f.to(torch.float32)
+    if not bool(torch.isfinite(f).all()) or not bool((f[:, 3] > 0).all()):
+        raise ValueError(f"{who}: a frame is finite with side > 0, got {f.tolist()!r}")
+    return f.contiguous()
+
+
+def _device_frame(frame, device):
+    return frame if frame is None or frame.is_cuda else frame.to(device)
+
+
+@torch.no_grad()
+def voxel_occupancy(x, resolution, frame=None):
+    """x [B, N, 3] (or [B, N, D], D > 3: xyz is read) -> (grid bool [B, r, r, r], info): the voxels of every cloud at r =
+    `resolution` (1 ... 32), indexed [x, y, z].  A frame is (lo_x, lo_y, lo_z, side), the cube the grid covers.  frame=None: every
+    cloud in its OWN frame, the box of voxel_surface_points -- the grid is then exactly the occupancy that function builds.
+    Otherwise a device float32 [B, 4] tensor (used as it is; the host cannot vet it, and whatever it holds no access leaves
+    its range), or a host frame: 4 numbers (one frame for the batch) or B x 4, a sequence or a CPU tensor, validated here
+    (finite, side > 0) and uploaded.  A point's voxel index is ALWAYS clamped to 0 ... r-1, so points outside a given frame land
+    in its boundary voxels.  Exact arithmetic: include/lion_hip.h, lion_voxel_occupancy.
+    info: 'frame' (float32 [B, 4] on the device: the frame that was used) and 'clamped' (int32 [B] on the device: the points of
+    each cloud whose index the clamp changed on at least one axis).
+    One launch, no host synchronisation; with frame None or a device frame the call can be captured.
+    ValueError before the device is touched: resolution outside 1 ... 32, x not a float32 [B, N, >= 3] tensor, a host frame of
+    another shape, not finite, or with side <= 0, a device frame that is not float32 [B, 4]."""
+    who = "voxel_occupancy"
+    B, N = _cloud_shape(x, who)
+    r = _resolution(resolution, who)
+    frame = _host_frame(frame, B, who)
+    xyz = _xyz(x)
+    frame = _device_frame(frame, xyz.device)
+    grid = torch.empty((B, r, r, r), device=xyz.device, dtype=torch.bool)
+    used = torch.empty((B, 4), device=xyz.device, dtype=torch.float32)
+    clamped = torch.empty((B,), device=xyz.device, dtype=torch.int32)
+    _lib.call("lion_voxel_occupancy", xyz, B, N, r, frame, grid, used, clamped)
+    return grid, {"frame": used, "clamped": clamped}
+
+
+UNIT_FRAME = (-1.0, -1.0, -1.0, 2.0)   # the cube [-1, 1]^3: the frame of a grid that comes without one
+
+
+@torch.no_grad()
+def voxel_surface_points_from_grid(grid, frame=None, num_points=2048, *, seeds=None, seed=None, stream_id=0):
+    """grid [B, r, r, r] (bool, or uint8 where any non-zero byte is an occupied voxel; indexed [x, y, z], r <= 32) ->
+    (points [B, K, 3], info): K = num_points points drawn uniformly over the exposed faces of the grid, placed in `frame` --
+    voxel_surface_points for a voxelisation that is given, not made from a cloud.  frame: as in voxel_occupancy; None is the
+    cube [-1, 1]^3, i.e. (-1, -1, -1, 2) (UNIT_FRAME).  With the grid and info['frame'] that voxel_occupancy(x, r) returns, the
+    points are voxel_surface_points(x, r, K)'s under the same seeds, bit for bit.  An empty grid has no face: its 'faces' entry
+    is 0 and all its K points are the frame's centre.  Exact arithmetic: include/lion_hip.h,
+    lion_voxel_surface_points_grid_keyed.
+    seeds / seed / neither, stream_id: as in voxel_surface_points (counter (k, LION_VOXEL_STEP_WORD, stream_id) under seeds[b]).
+    info: 'faces' (int32 [B] on the device), 'seeds' (as given, or the expanded list) and 'frame' (float32 [B, 4] on the device).
+    One launch, no host synchronisation; with device key words and a device frame the call can be captured.
+    ValueError before the device is touched: grid not a bool / uint8 [B, r, r, r] tensor with 1 <= r <= 32, num_points < 1, a
+    wrong seed count, seeds with seed, a bad frame (voxel_occupancy)."""
+    who = "voxel_surface_points_from_grid"
+    B, r = _grid_shape(grid, who)
+    K = num_points
+    if isinstance(K, bool) or not isinstance(K, numbers.Integral) or K < 1:
+        raise ValueError(f"{who}: num_points = {num_points!r}: an int >= 1")
+    K = int(K)
+    frame = _host_frame(UNIT_FRAME if frame is None else frame, B, who)
+    keys = _keys(seeds, seed, B, who)
+    _lib.require_cuda(grid)
+    frame = _device_frame(frame, grid.device)
+    words = diffusion_ops._device_keys(keys, B, grid.device, who)
+    out = torch.empty((B, K, 3), device=grid.device, dtype=torch.float32)
+    faces = torch.empty((B,), device=grid.device, dtype=torch.int32)
+    _lib.call("lion_voxel_surface_points_grid_keyed", grid, frame, B, r, words, int(stream_id), K, out, faces)
+    return out, {"faces": faces, "seeds": keys, "frame": frame}
 
 
 @torch.no_grad()
