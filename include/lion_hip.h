@@ -357,6 +357,27 @@ int lion_chain_update_multistep_noise_cm_keyed(const float *x, const float *eps_
                                                float *out, float *hist_out, float *z_out, lionStream_t stream);
 int lion_chain_diffuse_keyed(const float *x0, int B, int n, float m, float s, const uint32_t *keys, uint32_t stream_id,
                              float *out, float *z_out, lionStream_t stream);
+/* Per-sample start steps: the keyed DDIM / DDPM update and the keyed forward draw with one start per sample,
+ * on the keyed kernels' grid (x over a sample's quads, y = sample: what a sample does is uniform per workgroup).
+ *   lion_chain_update_noise_keyed_from / _cm_keyed_from
+ *       first_row is device int32[B]; i is the row index in cur[7], as lion_chain_begin_step leaves it.  Where i < first_row[b]
+ *       sample b is HELD: out[b] = x[b] bit for bit (nothing is stored where out == x), nothing is drawn, no key is read and
+ *       z_out[b] = 0.  Otherwise sample b gets exactly the arithmetic and the draw of lion_chain_update_noise_keyed / _cm_keyed
+ *       for that row's coefficients cur[1..6], with step word i - first_row[b]: the sample counts its own rows, so its noise is
+ *       that of a chain which started at its first row.  out may alias x.
+ *   lion_chain_diffuse_keyed_at
+ *       ms is device f32[B][2] = (m_b, s_b): sample b is lion_chain_diffuse_keyed with (m_b, s_b), bit for bit.  A sample with
+ *       m_b == 1 and s_b == 0 is copied bit for bit (not stored where out == x0), draws nothing, and its z_out is 0: "start 0".
+ * LION_EINVAL before any launch: the rules of the keyed forms above (lion_chain_diffuse_keyed's for the draw), or a NULL
+ * first_row / ms. */
+int lion_chain_update_noise_keyed_from(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                       const int32_t *first_row /* device i32[B] */, const uint32_t *keys, uint32_t stream_id,
+                                       float *out, float *z_out, lionStream_t stream);
+int lion_chain_update_noise_cm_keyed_from(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
+                                          const int32_t *first_row, const uint32_t *keys, uint32_t stream_id, float *out,
+                                          float *z_out, lionStream_t stream);
+int lion_chain_diffuse_keyed_at(const float *x0, int B, int n, const float *ms /* device f32[B][2] */, const uint32_t *keys,
+                                uint32_t stream_id, float *out, float *z_out, lionStream_t stream);
 /* Inputs of guided synthesis (csrc/perturb.hip): perturbed copies of clouds x f32[B][N][3], every cloud on its
  * own and under its own key (keys as above).  One Philox4x32-10 call per output point at counter = (point index WITHIN the
  * sample, a reserved step word, stream_id), words w0..w3; a fraction is u(w) = (w >> 8) * 2^-24, exact.  LION_VOXEL_STEP_WORD

@@ -47,6 +47,10 @@ UPDATE = {
 # of the same name, which takes the chain's `keys` (int32[B, 2]: a 64-bit Philox key per sample) where the spec says "seed" and
 # (num_samples, elements per sample) where it says "size".  DPMPP and ENCODE draw nothing and have no keyed form.
 KEYED_MODES = (DDIM, DDPM, SDE_DPMPP)
+# Per-sample start steps (GraphedChain(keyed=True, from_rows=True)): the keyed ancestral step ends with the
+# "_from" entry point of the same name instead, which takes the chain's `first_row` (int32[B]) before the keys: sample b is held
+# at the rows below first_row[b] and counts its own rows from there.  The same launch count as the keyed step.
+FROM_ROWS_MODES = (DDPM,)
 # the step words no chain step can have (a step's word is its row index < the table's capacity): include/lion_hip.h
 START_STEP_WORD, DIFFUSE_STEP_WORD = 0xFFFFFFFE, 0xFFFFFFFF
 _MASK64 = 0xFFFFFFFFFFFFFFFF
@@ -78,6 +82,14 @@ def sample_keys(seeds, num_samples, who="seeds") -> list:
     if len(keys) != int(num_samples):
         raise ValueError(f"{who}: {len(keys)} seeds for {num_samples} samples")
     return keys
+
+
+def first_rows(first_row, num_samples) -> list:
+    """`first_row` of a from_rows chain as a list of num_samples ints in 0 ... 2^31 - 1; ValueError otherwise.  Host work only."""
+    rows = [int(r) for r in first_row]
+    if len(rows) != int(num_samples) or any(not 0 <= r < 2 ** 31 for r in rows):
+        raise ValueError(f"GraphedChain: first_row = {rows!r}: {num_samples} ints in [0, 2^31)")
+    return rows
 
 
 def key_words(keys, device=None):
@@ -264,13 +276,19 @@ class CapturedStep:
 
 class GraphedChain:
     def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
-                 record_noise=False, keyed=False):
+                 record_noise=False, keyed=False, from_rows=False):
         """keyed: sample b draws its noise under its own key, seed[b], at counters that count within the sample (the "_keyed"
-        update kernels) -- `seed` is then int32[num_samples, 2] and prepare() / run() take num_samples keys."""
+        update kernels) -- `seed` is then int32[num_samples, 2] and prepare() / run() take num_samples keys.
+        from_rows (keyed DDPM chains only, else ValueError): the chain owns `first_row`, int32[num_samples], which prepare()
+        uploads with the table; sample b is held at the rows below first_row[b] and then runs as a chain of its own that starts
+        there (the "_from" update kernel)."""
         self.model, self.mode, self.capacity, self.keyed = model, mode, int(capacity), bool(keyed)
+        self.from_rows = bool(from_rows)
         dev = torch.device(device)
         size = [num_samples] + list(shape)
         per_sample = int(np.prod(shape))
+        if self.from_rows and not (keyed and mode in FROM_ROWS_MODES):
+            raise ValueError(f"GraphedChain: from_rows needs a keyed DDPM chain, got mode {mode}, keyed={bool(keyed)}")
         if keyed and mode not in KEYED_MODES:
             raise ValueError(f"GraphedChain: mode {mode} draws nothing and has no keyed form")
         if keyed and per_sample % 4 != 0:
@@ -284,6 +302,7 @@ class GraphedChain:
         # two 32-bit words of the Philox key -- of the chain, or (keyed) of every sample
         self.seed = torch.zeros((num_samples, 2) if keyed else 2, dtype=torch.int32, device=dev)
         self.cur = torch.zeros(8, device=dev)
+        self.first_row = torch.zeros(num_samples, dtype=torch.int32, device=dev) if self.from_rows else None   # 0: never held
         self.z = torch.zeros(size, device=dev) if record_noise and mode != ENCODE else None   # tests: the noise each step used
         self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
         self.base = torch.zeros(size, device=dev) if mode == ENCODE else None   # ENCODE: the state at the leg's low end
@@ -327,10 +346,13 @@ class GraphedChain:
                 given["keys"] = [self.seed]
                 if not self.cm_out:
                     given["size"] = [num_samples, per_sample]
+            if self.from_rows:
+                given["keys"] = [self.first_row, self.seed]
             args = []
             for a in spec:
                 args += given[a] if a in given else [getattr(self, a) if isinstance(a, str) else a]
-            _lib.call(entry + ("_cm" if self.cm_out else "") + ("_keyed" if self.keyed else ""), *args)
+            _lib.call(entry + ("_cm" if self.cm_out else "") + ("_keyed" if self.keyed else "")
+                      + ("_from" if self.from_rows else ""), *args)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
 
     def matches(self, condition_input, clip_feat):
@@ -338,7 +360,7 @@ class GraphedChain:
 
     @torch.no_grad()
     def run(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None, trajectory=None,
-            trajectory_before_last=False, noise_trajectory=None, state_hook=None, trajectory_rows=None):
+            trajectory_before_last=False, noise_trajectory=None, state_hook=None, trajectory_rows=None, first_row=None):
         """x_init: the chain's start; table [S, 8] float32 rows {t_model, a0..a5, a6} (a6: SDE_DPMPP's noise scale, 0 in
         every other mode); seed: the chain's 64-bit key -- of a keyed chain, a sequence or tensor of one key per sample.  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after
         every step (before the last step's update if `trajectory_before_last`, as run_denoising_diffusion reports it); with
@@ -346,8 +368,10 @@ class GraphedChain:
         row).
         `state_hook(i, x)`: called before step i's replay with the chain's latent buffer, which it may overwrite IN PLACE
         with launches on the current stream (no host synchronisation): inpainting / known-region replacement, or a
-        benchmark forcing the states a trained model would visit (bench.py's forced clouds)."""
-        S = self.prepare(x_init, table, seed, condition_input, clip_feat)
+        benchmark forcing the states a trained model would visit (bench.py's forced clouds).
+        `first_row` (a from_rows chain, where it is required): num_samples ints, the first table row each sample takes part in
+        (S or more: held throughout)."""
+        S = self.prepare(x_init, table, seed, condition_input, clip_feat, first_row)
         if RECORD is not None and self.z is not None and noise_trajectory is None:
             noise_trajectory = []
             RECORD.append((x_init.detach().clone(), noise_trajectory))
@@ -365,12 +389,17 @@ class GraphedChain:
         return self.x.clone()
 
     @torch.no_grad()
-    def prepare(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None) -> int:
+    def prepare(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None, first_row=None) -> int:
         """everything a chain needs in device memory before its first replay (on the current stream): the start latent, the
         conditioning, the schedule table, the time-embedding rows, the step counter and the Philox key (keyed: the keys, a
-        sequence or tensor of one per sample).  Returns S."""
+        sequence or tensor of one per sample; from_rows: `first_row`, one non-negative int per sample).  Returns S."""
         S = int(table.shape[0])
         assert 1 <= S <= self.capacity and table.shape[1] == 8
+        if self.from_rows != (first_row is not None):
+            raise ValueError("GraphedChain: first_row goes with a from_rows chain, and only with it")
+        if self.from_rows:
+            rows = first_rows(first_row, self.x.shape[0])
+            self.first_row.copy_(torch.tensor(rows, dtype=torch.int32))
         self.x.copy_(x_init)
         if self.cond is not None:
             self.cond.copy_(condition_input)
@@ -400,18 +429,21 @@ for _name in ("replay", "graph", "graphs", "graph_b", "geo_graphs", "pinned", "p
 
 
 class ChainCache(LRU):
-    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed) -> GraphedChain.  A keyed and an
-    unkeyed capture of one (model, mode, shape) coexist, each in a slot of its own; the modes that draw nothing have the
-    unkeyed capture only and serve a keyed call with it."""
+    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed, from_rows) -> GraphedChain.  A keyed
+    and an unkeyed capture of one (model, mode, shape) coexist, each in a slot of its own; the modes that draw nothing have the
+    unkeyed capture only and serve a keyed call with it.  The per-sample-start capture (from_rows: keyed DDPM only, ValueError
+    otherwise) is a third entry beside them and takes one of the four slots."""
 
-    def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity, keyed=False):
+    def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity, keyed=False,
+            from_rows=False):
         rec = RECORD is not None
-        keyed = bool(keyed) and mode in KEYED_MODES
+        from_rows = bool(from_rows)
+        keyed = bool(keyed) and (mode in KEYED_MODES or from_rows)   # from_rows on a mode without a keyed form: refused below
         return self.lookup(
-            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed),
+            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed, from_rows),
             lambda hit: hit.model is model and hit.capacity >= table_capacity and hit.matches(condition_input, clip_feat),
             lambda: GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity,
-                                 record_noise=rec, keyed=keyed))
+                                 record_noise=rec, keyed=keyed, from_rows=from_rows))
 
 
 def draw_seed() -> int:

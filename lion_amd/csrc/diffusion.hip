@@ -153,10 +153,11 @@ __global__ void begin_step_kernel(const float *__restrict__ table, int n_steps, 
 
 // MODE 0: DDIM  out = x*a0 + (a1*eps + a2*z)                     (a = {s, c, sigma})
 // MODE 1: DDPM  a5 != 0 (t == 0): out = a0*(x - a1*eps);  else out = a0*(x - a1*eps/a2) + (a3*z)*a4
+// `step` is the counter's step word: cur[7], the row's index, but in the per-sample-start form below.
 template <int MODE, bool KEYED>
 __device__ __forceinline__ void update_noise_body(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
                                                   uint32_t sample_quads, const float *__restrict__ cur,
-                                                  const uint32_t *__restrict__ seed_words, uint32_t stream_id,
+                                                  const uint32_t *__restrict__ seed_words, uint32_t step, uint32_t stream_id,
                                                   float *__restrict__ out, float *__restrict__ z_out, int cm_points) {
   size_t q;
   uint64_t ctr;
@@ -164,7 +165,6 @@ __device__ __forceinline__ void update_noise_body(const float *__restrict__ x, c
   if (!own_quad<KEYED>(numel, sample_quads, seed_words, q, ctr, key)) return;
   const size_t i = q * 4;
   const float a0 = cur[1], a1 = cur[2], a2 = cur[3], a3 = cur[4], a4 = cur[5], a5 = cur[6];
-  const uint32_t step = (uint32_t)__float_as_int(cur[7]);
   const uint64_t seed = (uint64_t)key[0] | ((uint64_t)key[1] << 32);
   float z[4];
   normal4(ctr, step, stream_id, seed, z);
@@ -190,7 +190,8 @@ template <int MODE>
 __global__ void update_noise_kernel(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
                                     const float *__restrict__ cur, const uint32_t *__restrict__ seed_words,
                                     uint32_t stream_id, float *__restrict__ out, float *__restrict__ z_out, int cm_points) {
-  update_noise_body<MODE, false>(x, eps, numel, 0, cur, seed_words, stream_id, out, z_out, cm_points);
+  update_noise_body<MODE, false>(x, eps, numel, 0, cur, seed_words, (uint32_t)__float_as_int(cur[7]), stream_id, out, z_out,
+                                 cm_points);
 }
 
 // the keyed form: grid (ceil(sample_quads / 256), B), keys u32[2*B]
@@ -199,7 +200,42 @@ __global__ void update_noise_keyed_kernel(const float *__restrict__ x, const flo
                                           uint32_t sample_quads, const float *__restrict__ cur,
                                           const uint32_t *__restrict__ keys, uint32_t stream_id, float *__restrict__ out,
                                           float *__restrict__ z_out, int cm_points) {
-  update_noise_body<MODE, true>(x, eps, numel, sample_quads, cur, keys, stream_id, out, z_out, cm_points);
+  update_noise_body<MODE, true>(x, eps, numel, sample_quads, cur, keys, (uint32_t)__float_as_int(cur[7]), stream_id, out, z_out,
+                                cm_points);
+}
+
+// a sample that an "_at" / "_from" kernel leaves alone: out = x bit for bit (nothing is stored where out IS x), z_out = 0;
+// nothing is drawn and no key is read.  `full` as in load_quad: a keyed quad always lies below numel.
+__device__ __forceinline__ void hold_quad(const float *x, size_t numel, uint32_t sample_quads, bool full, float *out,
+                                          float *z_out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // own_quad<true>'s quad, without a key
+  if (t >= sample_quads) return;
+  const size_t i = ((size_t)blockIdx.y * sample_quads + t) * 4;
+  if (out != x) {
+    float v[4];
+    load_quad(x, i, numel, full, v);
+    store_quad(out, i, numel, full, v);
+  }
+  if (z_out) {
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    store_quad(z_out, i, numel, full, zero);
+  }
+}
+
+// the keyed form with a first row per sample (first_row i32[B]): at row i = cur[7], sample b = blockIdx.y is held where
+// i < first_row[b] and else takes the keyed update with the row's coefficients under step word i - first_row[b] -- its own row
+// count.  One sample per grid.y: the branch is uniform per workgroup.  x and out are not __restrict__ here: they are compared.
+template <int MODE>
+__global__ void update_noise_keyed_from_kernel(const float *x, const float *__restrict__ eps, size_t numel,
+                                               uint32_t sample_quads, const float *__restrict__ cur,
+                                               const int32_t *__restrict__ first_row, const uint32_t *__restrict__ keys,
+                                               uint32_t stream_id, float *out, float *z_out, int cm_points) {
+  const int32_t local = __float_as_int(cur[7]) - first_row[blockIdx.y];
+  if (local < 0) {
+    hold_quad(x, numel, sample_quads, true, out, z_out);
+    return;
+  }
+  update_noise_body<MODE, true>(x, eps, numel, sample_quads, cur, keys, (uint32_t)local, stream_id, out, z_out, cm_points);
 }
 
 // out[b][.] = z alone: sample b's draw at counter (j, step, stream_id) under keys[b] -- the start latent of a keyed chain
@@ -241,12 +277,19 @@ static int keyed_grid(int B, int n, dim3 *grid, uint32_t *sample_quads) {
   return LION_OK;
 }
 
+// first_row: NULL for the plain keyed form, else the per-sample-start form on the same grid
 static int update_noise_keyed_launch(int mode, hipStream_t st, const float *x, const float *eps, int B, int n, const float *cur,
-                                     const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, int cm_points) {
+                                     const int32_t *first_row, const uint32_t *keys, uint32_t stream_id, float *out,
+                                     float *z_out, int cm_points) {
   dim3 grid;
   uint32_t sq;
   if (keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
   const size_t numel = (size_t)B * n;
+  if (first_row)
+    return mode == 0 ? lion_launch<update_noise_keyed_from_kernel<0>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,
+                                                                      stream_id, out, z_out, cm_points)
+                     : lion_launch<update_noise_keyed_from_kernel<1>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,
+                                                                      stream_id, out, z_out, cm_points);
   return mode == 0 ? lion_launch<update_noise_keyed_kernel<0>>(grid, 256, 0, st, x, eps, numel, sq, cur, keys, stream_id, out,
                                                                z_out, cm_points)
                    : lion_launch<update_noise_keyed_kernel<1>>(grid, 256, 0, st, x, eps, numel, sq, cur, keys, stream_id, out,
@@ -456,6 +499,18 @@ __global__ void diffuse_keyed_kernel(const float *x0, size_t numel, uint32_t sam
   diffuse_body<VEC, true>(x0, nullptr, numel, sample_quads, m, s, keys, stream_id, out, z_out);
 }
 
+// the keyed draw with its scalars per sample (ms f32[B][2] = (m_b, s_b)); a sample with m_b == 1 and s_b == 0 is held
+template <bool VEC>
+__global__ void diffuse_keyed_at_kernel(const float *x0, size_t numel, uint32_t sample_quads, const float *__restrict__ ms,
+                                        const uint32_t *__restrict__ keys, uint32_t stream_id, float *out, float *z_out) {
+  const float m = ms[2 * (size_t)blockIdx.y], s = ms[2 * (size_t)blockIdx.y + 1];
+  if (m == 1.f && s == 0.f) {
+    hold_quad(x0, numel, sample_quads, VEC, out, z_out);
+    return;
+  }
+  diffuse_body<VEC, true>(x0, nullptr, numel, sample_quads, m, s, keys, stream_id, out, z_out);
+}
+
 } // namespace
 
 extern "C" {
@@ -614,15 +669,36 @@ int lion_chain_update_noise_keyed(int mode, const float *x, const float *eps, in
                                   const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
   if (!x || !eps || !cur || !keys || !out || (mode != 0 && mode != 1)) return LION_EINVAL;
   if (!aligned16({x, eps, out, z_out})) return LION_EINVAL;
-  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, keys, stream_id, out, z_out, 0);
+  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, nullptr, keys, stream_id, out,
+                                   z_out, 0);
 }
 
 int lion_chain_update_noise_cm_keyed(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
                                      const uint32_t *keys, uint32_t stream_id, float *out, float *z_out, lionStream_t stream) {
   if (!x || !eps_cm || !cur || !keys || !out || N <= 0 || N > 0x1fffffff || (mode != 0 && mode != 1)) return LION_EINVAL;
   if (!aligned16({x, out, z_out})) return LION_EINVAL;
-  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, keys, stream_id, out,
-                                   z_out, N);
+  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, nullptr, keys, stream_id,
+                                   out, z_out, N);
+}
+
+// ---- per-sample start steps: a first row (or a forward draw's scalars) per sample, on the keyed kernels' grid ---------------
+int lion_chain_update_noise_keyed_from(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                       const int32_t *first_row, const uint32_t *keys, uint32_t stream_id, float *out,
+                                       float *z_out, lionStream_t stream) {
+  if (!x || !eps || !cur || !first_row || !keys || !out || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!aligned16({x, eps, out, z_out})) return LION_EINVAL;
+  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, first_row, keys, stream_id, out,
+                                   z_out, 0);
+}
+
+int lion_chain_update_noise_cm_keyed_from(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
+                                          const int32_t *first_row, const uint32_t *keys, uint32_t stream_id, float *out,
+                                          float *z_out, lionStream_t stream) {
+  if (!x || !eps_cm || !cur || !first_row || !keys || !out || N <= 0 || N > 0x1fffffff || (mode != 0 && mode != 1))
+    return LION_EINVAL;
+  if (!aligned16({x, out, z_out})) return LION_EINVAL;
+  return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, first_row, keys, stream_id,
+                                   out, z_out, N);
 }
 
 int lion_chain_update_multistep_noise_keyed(const float *x, const float *eps, const float *hist, int B, int n, const float *cur,
@@ -653,6 +729,18 @@ int lion_chain_diffuse_keyed(const float *x0, int B, int n, float m, float s, co
   return aligned16({x0, out, z_out})
              ? lion_launch<diffuse_keyed_kernel<true>>(grid, 256, 0, st, x0, numel, sq, m, s, keys, stream_id, out, z_out)
              : lion_launch<diffuse_keyed_kernel<false>>(grid, 256, 0, st, x0, numel, sq, m, s, keys, stream_id, out, z_out);
+}
+
+int lion_chain_diffuse_keyed_at(const float *x0, int B, int n, const float *ms, const uint32_t *keys, uint32_t stream_id,
+                                float *out, float *z_out, lionStream_t stream) {
+  dim3 grid;
+  uint32_t sq;
+  if (!x0 || !ms || !keys || !out || keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t numel = (size_t)B * n;
+  return aligned16({x0, out, z_out})
+             ? lion_launch<diffuse_keyed_at_kernel<true>>(grid, 256, 0, st, x0, numel, sq, ms, keys, stream_id, out, z_out)
+             : lion_launch<diffuse_keyed_at_kernel<false>>(grid, 256, 0, st, x0, numel, sq, ms, keys, stream_id, out, z_out);
 }
 
 } // extern "C"

@@ -360,14 +360,18 @@ class DiffusionDiscretized(object):
             return _mixed(model, pred, mixing).float().contiguous()
 
     def _replay(self, model, num_samples, shape, mode, x, table, seed, condition_input, clip_feat, capacity=None, keys=None,
-                **run):
+                first_row=None, **run):
         """the graphed branch of every sampler: the captured chain of (model, mode, batch shape) from this object's cache, run
         from x over `table`; seed None: one is drawn with chain.draw_seed() once the chain is there; `run`: GraphedChain.run's
         keywords.  keys (a list of num_samples 64-bit keys) in place of seed: the keyed capture of a mode that draws.
+        first_row (num_samples ints, with keys; DDPM only): the per-sample-start capture, a cache entry of its own.
         Returns the final latent."""
         keyed = keys is not None and mode in _chain.KEYED_MODES
         ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, self.device, mode,
-                              self._diffusion_steps if capacity is None else capacity, keyed=keyed)
+                              self._diffusion_steps if capacity is None else capacity, keyed=keyed,
+                              from_rows=first_row is not None)
+        if first_row is not None:
+            return ch.run(x, table, keys, condition_input, clip_feat, first_row=first_row, **run)
         if keyed:
             return ch.run(x, table, keys, condition_input, clip_feat, **run)
         return ch.run(x, table, _chain.draw_seed() if seed is None else seed, condition_input, clip_feat, **run)
@@ -384,6 +388,40 @@ class DiffusionDiscretized(object):
             if value is not None:
                 raise ValueError(f"{who}: seeds cannot be combined with {name}")
         return keys
+
+    # ---- per-sample start steps --------------------------------------------------------------------------
+    @staticmethod
+    def per_sample_indices(who, value, num_samples, lo, hi, lists=False):
+        """`value` as B per-sample schedule indices: None where it is not that form (an int, or anything the caller's own check
+        refuses), else a list of num_samples ints in lo ... hi.  The form is a 1-D integer tensor or numpy array; with `lists`
+        a list or tuple of ints too.  ValueError -- host work only, before any launch -- on bool entries, another dtype or
+        rank, a wrong count, or an entry outside the range."""
+        if isinstance(value, torch.Tensor):
+            ok = value.dim() == 1 and value.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+            entries = value.detach().cpu().tolist() if ok else None
+        elif isinstance(value, np.ndarray):
+            ok = value.ndim == 1 and value.dtype.kind in "iu"
+            entries = value.tolist() if ok else None
+        elif lists and isinstance(value, (list, tuple)):
+            ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in value)
+            entries = [int(v) for v in value] if ok else None
+        else:
+            return None
+        if not ok:
+            raise ValueError(f"{who}: per-sample indices are a 1-D integer tensor or array (no bools), got {value!r}")
+        if len(entries) != int(num_samples):
+            raise ValueError(f"{who}: {len(entries)} per-sample indices for {num_samples} samples")
+        if any(not lo <= v <= hi for v in entries):
+            raise ValueError(f"{who}: per-sample indices {entries!r} outside [{lo}, {hi}]")
+        return entries
+
+    @staticmethod
+    def _call_keys(keys, seed, num_samples):
+        """the keys of a per-sample-start call, which is always keyed: `keys` (from seeds=) where given, else one key per sample
+        split from `seed` (None: chain.draw_seed(), so torch.manual_seed governs it)"""
+        if keys is not None:
+            return keys
+        return _chain.split_seed(_chain.draw_seed() if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF, int(num_samples))
 
     def _keyed_start(self, keys, num_samples, shape):
         """the start latent of a keyed chain: sample b under keys[b] at LION_START_STEP_WORD, stream 0"""
@@ -476,7 +514,21 @@ class DiffusionDiscretized(object):
         a chain run under the same seed repeats none of it.  return_noise: (x_t, z).
         seeds: x0.shape[0] ints, one key per sample, in place of noise / seed (ValueError with either, or on a wrong count):
         sample b's z is drawn under seeds[b] at counters within the sample (lion_chain_diffuse_keyed), so it depends on
-        neither the batch size nor the sample's position; torch's generators are not touched."""
+        neither the batch size nor the sample's position; torch's generators are not touched.
+        t may also be B per-sample indices, a 1-D integer tensor or numpy array with entries up to T-1, a NEGATIVE entry
+        meaning "skip this sample" (it comes back bit for bit and draws nothing): one launch of lion_chain_diffuse_keyed_at on
+        the same host scalars, so that sample b is the bits of diffuse(x0, t[b], seeds=...).  This form is always keyed: the
+        keys are `seeds`, or split_seed(seed, B) (seed None: one is drawn).  ValueError with noise, on a wrong count, bool
+        entries or an entry above T-1."""
+        B = x0.shape[0]
+        per = self.per_sample_indices("diffuse", t, B, -2 ** 63, self._diffusion_steps - 1)
+        if per is not None:
+            if noise is not None:
+                raise ValueError("diffuse: per-sample indices draw under per-sample keys and cannot be combined with noise")
+            keys = self._call_keys(self._sample_keys("diffuse", seeds, B, seed=seed), seed, B)
+            sqrt = lambda v: float(torch.sqrt(v))
+            ms = [(1.0, 0.0) if i < 0 else (sqrt(self._h_alpha_bars[i]), sqrt(1.0 - self._h_alpha_bars[i])) for i in per]
+            return diffusion_ops.diffuse_at(x0.contiguous(), ms, keys, return_noise=return_noise)
         if not isinstance(t, (int, np.integer)) or isinstance(t, bool) or not 0 <= t <= self._diffusion_steps - 1:
             raise ValueError(f"diffuse: t = {t!r} is not an index in [0, {self._diffusion_steps - 1}]")
         keys = self._sample_keys("diffuse", seeds, x0.shape[0], noise=noise, seed=seed)
@@ -507,8 +559,21 @@ class DiffusionDiscretized(object):
         loop's device generator -- in place of a draw from torch's global generators (graphed: chain.draw_seed()).
         seeds: one key per sample, as in run_denoising_diffusion: the tail's row i (t = time_start - 1 - i) adds to sample b the
         noise of counter word i under seeds[b]; graphed and eager tails give the same bits.  ValueError before any launch:
-        len(seeds) != num_samples, or seeds with seed or given_noise."""
+        len(seeds) != num_samples, or seeds with seed or given_noise.
+        time_start may also be num_samples per-sample starts, a 1-D integer tensor or numpy array with entries in 0 ... T
+        (DESIGN.md 4.6.9): sample b then comes back as from the uniform call with time_start[b] under the same seeds, bit for
+        bit at equal num_samples, and a sample with start 0 as it went in.  The call runs S = max(time_start) replays of the
+        per-sample-start capture (chain.GraphedChain(from_rows=True), a cache entry of its own) over ddpm_table(S, temp) with
+        first_row[b] = S - time_start[b]: every sample is evaluated at every row and held -- its update discarded -- below its
+        first row.  S = 0 returns (x_noisy, []) with no launch.  This form is always keyed: the keys are `seeds`, or
+        split_seed(seed, num_samples) (seed None: one is drawn).  graph=False is the debug path: the uniform eager tail on the
+        whole batch once per distinct start, merged per sample; the same bits.  ValueError: given_noise, a wrong count, bool
+        entries, an entry outside 0 ... T."""
         keys = self._sample_keys("run_denoising_diffusion_from_t", seeds, num_samples, seed=seed, given_noise=given_noise)
+        starts = self.per_sample_indices("run_denoising_diffusion_from_t", time_start, num_samples, 0, self._diffusion_steps)
+        if starts is not None:
+            return self._tails_from_rows(model, num_samples, shape, starts, x_noisy, temp, enable_autocast, condition_input,
+                                         given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys)
         if isinstance(time_start, bool) or not isinstance(time_start, (int, np.integer)) \
                 or not 0 <= time_start <= self._diffusion_steps:
             raise ValueError(f"run_denoising_diffusion_from_t: time_start = {time_start!r} outside [0, {self._diffusion_steps}]")
@@ -530,6 +595,45 @@ class DiffusionDiscretized(object):
                 gen = None if seed is None else torch.Generator(device=dev).manual_seed(seed & 0x7FFFFFFFFFFFFFFF)
                 x = self._ancestral_steps(model, x_noisy, int(time_start), temp, enable_autocast, condition_input, given_noise,
                                           clip_feat, {}, states, generator=gen, keys=keys)
+            return x, output_list
+
+    def _tails_from_rows(self, model, num_samples, shape, starts, x_noisy, temp, enable_autocast, condition_input, given_noise,
+                         clip_feat, graph, keep_trajectory, conv_precision, seed, keys):
+        """run_denoising_diffusion_from_t for per-sample starts (a list of num_samples ints in 0 ... T)"""
+        who = "run_denoising_diffusion_from_t"
+        if given_noise is not None:
+            raise ValueError(f"{who}: per-sample starts draw under per-sample keys and cannot be combined with given_noise")
+        output_list = []
+        S = max(starts)
+        if S == 0:
+            return x_noisy, output_list
+        if not x_noisy.is_cuda:
+            raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
+        if list(x_noisy.shape) != [num_samples] + list(shape):
+            raise ValueError(f"{who}: x_noisy {tuple(x_noisy.shape)} for {[num_samples] + list(shape)}")
+        keys = self._call_keys(keys, seed, num_samples)
+        first_row = [S - s for s in starts]
+        with _sampling(model, conv_precision):
+            x_noisy = x_noisy.to(self.device).contiguous()
+            if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
+                x = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, self.ddpm_table(S, temp), None,
+                                 condition_input, clip_feat, keys=keys, first_row=first_row,
+                                 trajectory=output_list if keep_trajectory else None, trajectory_before_last=True)
+                return x, output_list
+            # the uniform eager tail on the WHOLE batch once per distinct start (equal batch size: equal kernel plans); sample b
+            # takes its result, and its state at row i, from the run of its own start, at that run's row i - first_row[b]
+            x = x_noisy.clone()
+            states = [x_noisy.clone() for _ in range(S)] if keep_trajectory else None
+            for s in sorted(set(starts) - {0}):
+                mine = [b for b in range(num_samples) if starts[b] == s]
+                run_states = [] if keep_trajectory else None
+                x_s = self._ancestral_steps(model, x_noisy, s, temp, enable_autocast, condition_input, None, clip_feat, {},
+                                            run_states, keys=keys)
+                x[mine] = x_s[mine]
+                for j in range(s if keep_trajectory else 0):
+                    states[S - s + j][mine] = run_states[j][mine]
+            if keep_trajectory:
+                output_list.extend(states)
             return x, output_list
 
     @torch.no_grad()

@@ -1,6 +1,7 @@
 """Fused denoiser-step updates (D1) over the C ABI: lion_ddim_update / lion_ddpm_update, the multistep solver
 step lion_dpmpp_update and its stochastic form lion_sde_dpmpp_update, the deterministic encoder's row lion_ddim_encode_update,
-the forward-process draw lion_chain_diffuse, and the per-sample-key draws lion_philox_normal_keyed / lion_chain_diffuse_keyed."""
+the forward-process draw lion_chain_diffuse, and the per-sample-key draws lion_philox_normal_keyed / lion_chain_diffuse_keyed /
+lion_chain_diffuse_keyed_at."""
 import numpy as np
 import torch
 
@@ -8,7 +9,7 @@ from . import _lib
 from .chain import key_words, sample_keys
 
 __all__ = ["ddim_update", "ddpm_update", "dpmpp_update", "sde_dpmpp_update", "ddim_encode_update", "diffuse",
-           "philox_normal_keyed"]
+           "diffuse_at", "philox_normal_keyed"]
 
 
 def ddim_update(x, eps, z, s, c, sigma, out=None):
@@ -80,6 +81,25 @@ def diffuse(x0, m, s, noise=None, seed=None, stream_id=1, out=None, return_noise
     z_out = torch.empty_like(x0) if return_noise else None
     _lib.call("lion_chain_diffuse", x0, noise, x0.numel(), float(m), float(s),
               None if noise is not None else seed_words(int(seed), x0.device), int(stream_id), out, z_out)
+    return (out, z_out) if return_noise else out
+
+
+def diffuse_at(x0, ms, seeds, stream_id=1, out=None, return_noise=False):
+    """diffuse(seeds=...) with its two scalars per sample (lion_chain_diffuse_keyed_at): ms is B pairs (m_b, s_b) of host floats,
+    and sample b is diffuse's keyed draw with (m_b, s_b) bit for bit.  A sample with (1, 0) is copied bit for bit and draws
+    nothing; its z is 0.  out may be x0."""
+    B = x0.shape[0]
+    pairs = np.asarray(ms, dtype=np.float32)
+    if pairs.shape != (B, 2):
+        raise ValueError(f"diffuse_at: ms {pairs.shape} for {B} samples")
+    _lib.require_cuda(x0, out)
+    words = _device_keys(seeds, B, x0.device, "diffuse_at")
+    n = x0.numel() // max(B, 1)
+    if n <= 0 or n % 4 != 0:
+        raise ValueError(f"diffuse_at: {n} elements per sample, keyed noise needs a positive multiple of 4")
+    out = torch.empty_like(x0) if out is None else out
+    z_out = torch.empty_like(x0) if return_noise else None
+    _lib.call("lion_chain_diffuse_keyed_at", x0, B, n, torch.from_numpy(pairs).to(x0.device), words, int(stream_id), out, z_out)
     return (out, z_out) if return_noise else out
 
 

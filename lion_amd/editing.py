@@ -4,9 +4,10 @@ of noisy or voxelised inputs, editing.
 
 Per latent the device work is one forward draw (``DiffusionDiscretized.diffuse``: lion_chain_diffuse, noise on the chip) and
 ``time_start`` replays of the prior's captured ancestral step (``run_denoising_diffusion_from_t``) -- the chain a sampling
-call of the same batch shape captured is the one replayed here.  One ``time_start`` per latent for the whole batch, as in the
-reference.  With ``solver_steps=S`` the tail is instead at most S replays of the few-step solver's captured step
-(``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
+call of the same batch shape captured is the one replayed here.  ``time_start`` is one index per latent for the whole batch, as
+in the reference, or one per latent AND sample (per-sample start steps, DESIGN.md 4.6.9: one keyed forward draw and
+max(time_start) replays of the per-sample-start capture, each sample held until its own first row).  With ``solver_steps=S``
+the tail is instead at most S replays of the few-step solver's captured step (``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
 
 ``voxel_guided`` is the recipe on the surface of the input's voxelisation (``perturb.voxel_surface_points``);
 ``voxel_grid_guided`` starts from a voxel grid instead of a cloud.  Both can report the voxel IoU of input and output.
@@ -39,6 +40,13 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     begins with the step at index time_start - 1: the chain runs time_start steps and treats its start as one step less noisy
     than it was drawn.  That off-by-one is the reference's and is kept.  0 skips diffusion for that latent; with both at 0
     the result is the VAE's reconstruction from its sampled latents.
+    Per-sample start steps: time_start itself (a 1-D integer tensor or numpy array), or either element of the pair (there a
+    list or tuple too), may be B indices, one per sample -- a strength sweep of one shape, or a batch of scans that each need
+    their own amount of denoising, in ONE call.  A top-level tuple or list of length 2 is always the (global, local) pair.
+    Sample b of the call is, bit for bit at equal B and equal `seeds`, sample b of the call with the ints (g[b], l[b]); a
+    sample with 0 keeps that latent.  The latent costs max(time_start) prior evaluations of the whole batch.  The draws are
+    always keyed: under `seed` each draw's key is split once more into one key per sample.  ValueError: a wrong count, bool
+    entries, an index outside 0 ... T-1, or per-sample indices with solver_steps.
     keep_first: sample 0 keeps its own latents (the reference's ``eps[0:1] = eps_ori[0:1]``), so the batch shows the input's
     reconstruction next to its variations.
     seed: makes the whole call repeatable and leaves torch's global generators alone; None draws one from torch's CPU
@@ -47,9 +55,9 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     package pass it; the reference's recipe passes the latent itself, which is the same tensor whenever style_mlp is '' (every
     released configuration).
     info: 'global_original', 'global_edited', 'local_original', 'local_edited' (the four latents, [B] + latent_shape()),
-    'condition_input' (what the local prior was conditioned on), 'time_start' (the pair), 'seeds' (the call's seed and the
-    key of every draw derived from it) and 'tail_steps' (per latent the list of schedule indices its tail evaluated the prior
-    at, in order; [] where time_start is 0).
+    'condition_input' (what the local prior was conditioned on), 'time_start' (the pair that ran: ints, or tuples of B ints),
+    'seeds' (the call's seed and the key of every draw derived from it) and 'tail_steps' (per latent the list of schedule
+    indices its tail evaluated the prior at, in order: max(time_start) - 1 ... 0; [] where time_start is 0).
     solver_steps: None (default) is the ancestral tail above.  An int S >= 2 runs each latent's tail with the few-step solver,
     run_dpm_solver(steps=S, t_start=time_start[i], stochastic=stochastic, seed=seeds['chain_*']): at most S evaluations of the
     prior, at the indices solver_schedule(S, 'logsnr', time_start[i]), instead of time_start[i].  The solver tail STARTS AT
@@ -66,13 +74,24 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     (other batch sizes select other kernel plans).  info['seeds'] then holds 'seeds' (the list) and a list per sub-key.
     ValueError before any launch: len(seeds) != B, or seeds with seed."""
     T = diffusion._diffusion_steps
+    B = x.shape[0]
     pair = tuple(time_start) if isinstance(time_start, (tuple, list)) else (time_start, time_start)
-    if len(pair) != 2 or any(isinstance(t, bool) or not isinstance(t, numbers.Integral) or not 0 <= t <= T - 1 for t in pair):
+    if len(pair) != 2:
         raise ValueError(f"diffuse_denoise: time_start = {time_start!r}: an int or a (global, local) pair in [0, {T - 1}]")
-    pair = (int(pair[0]), int(pair[1]))
+    # per latent: an int, or (per-sample start steps) a tuple of B ints -- inside the pair a list is one too
+    inside = isinstance(time_start, (tuple, list))
+    starts = [diffusion.per_sample_indices("diffuse_denoise: time_start", t, B, 0, T - 1, lists=inside) for t in pair]
+    if any(s is None and (isinstance(t, bool) or not isinstance(t, numbers.Integral) or not 0 <= t <= T - 1)
+           for s, t in zip(starts, pair)):
+        raise ValueError(f"diffuse_denoise: time_start = {time_start!r}: an int or a (global, local) pair in [0, {T - 1}], "
+                         f"each an int or {B} per-sample indices")
+    pair = tuple(int(t) if s is None else tuple(s) for s, t in zip(starts, pair))
     if solver_steps is not None and (isinstance(solver_steps, bool) or not isinstance(solver_steps, numbers.Integral)
                                      or solver_steps < 2):
         raise ValueError(f"diffuse_denoise: solver_steps = {solver_steps!r}: None or an int >= 2")
+    if solver_steps is not None and any(isinstance(t, tuple) for t in pair):
+        raise ValueError("diffuse_denoise: per-sample time_start cannot be combined with solver_steps (a per-sample solver "
+                         "schedule would need per-sample timesteps)")
     visited = [[], []]
     names = SUBKEYS
     keyed = seeds is not None
@@ -109,6 +128,20 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
         if pair[i] == 0:
             return eps_ori
         which = ("global", "local")[i]
+        if isinstance(pair[i], tuple):   # per-sample starts: one keyed forward draw, max(start) replays of the from-rows capture
+            top = max(pair[i])
+            if top == 0:
+                return eps_ori
+            visited[i] = list(range(top - 1, -1, -1))
+            at = torch.tensor([t if t > 0 else -1 for t in pair[i]], dtype=torch.int64)   # start 0: neither diffused nor denoised
+            eps_t = diffusion.diffuse(eps_ori, at, **key("diffuse_" + which))
+            eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], torch.tensor(pair[i], dtype=torch.int64),
+                                                              eps_t, temp=temp, condition_input=condition_input,
+                                                              clip_feat=clip_feat, graph=graph, keep_trajectory=False,
+                                                              conv_precision=conv_precision, **key("chain_" + which))
+            if keep_first:
+                eps[0:1] = eps_ori[0:1]
+            return eps.contiguous()
         eps_t = diffusion.diffuse(eps_ori, pair[i], **key("diffuse_" + which))
         if solver_steps is not None:
             visited[i] = diffusion.solver_schedule(int(solver_steps), 'logsnr', pair[i])
