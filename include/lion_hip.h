@@ -77,6 +77,16 @@ int lion_voxel_scatter(const float *feat, const void *plan, size_t plan_bytes, i
  * full scatter and has no reader). */
 int lion_voxel_scatter_read(const float *feat, const void *plan, size_t plan_bytes, int B, int C, int N, int r,
                             const int32_t *occ_m1, float *out, lionStream_t stream);
+/* For tests only, pure host calls that launch nothing: the launch plans of the kernels above and of the devoxelize forward,
+ * written into out, a HOST array of 8 ints.  stream is not used (every entry with a pointer parameter takes one).
+ * lion_internal_voxelize_plan: kind 0 the fused kernel (lion_avg_voxelize_forward, lion_voxelize_points_forward, and with
+ * C = 0 lion_voxel_index), 1 lion_voxel_scatter, 2 lion_voxel_scatter_read -> {slabs per cloud S, channel ranges CS, voxels
+ * per slab SV, points per thread NP, plan words per slab, LDS arena words, LDS bytes, grid}; LION_OK, or LION_EUNSUPPORTED
+ * for a shape the fast path (kind 0: the fallback runs) or the scatter launcher refuses.
+ * lion_internal_devoxelize_path: the forward at (B, C, N, r) with (aligned != 0) or without a 16-byte aligned grid ->
+ * {kind (0 ring, 1 slab, 2 gather), PX, XS, CI, ld (0 unless slab), channels per workgroup, LDS bytes, grid.x}. */
+int lion_internal_voxelize_plan(int B, int C, int N, int r, int kind, int32_t *out, lionStream_t stream);
+int lion_internal_devoxelize_path(int B, int C, int N, int r, int aligned, int32_t *out, lionStream_t stream);
 
 /* ---- K3: avg_voxelize_backward, vox.cpp:54-79 (vox.cu:86-110) --------------------------
  * gy f32[B,C,r3], ind i32[B,N], cnt i32[B,r3] -> gx f32[B,C,N]. */

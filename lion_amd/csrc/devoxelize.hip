@@ -658,24 +658,43 @@ __global__ __launch_bounds__(DVR_NT) void devox_ring_kernel(const float *__restr
 // 128-KiB slab allowed ONE workgroup per CU, so its zero / atomic / store phases ran back to back with nothing beside them;
 // two 64-KiB halves let a second workgroup's atomics run under the first one's stores; every workgroup scans all 8 N
 // entries and keeps those that fall into its part).
-__global__ __launch_bounds__(1024) void devox_bwd_lds_kernel(const float *__restrict__ gy,
-                                                             const int32_t *__restrict__ inds,
-                                                             const float *__restrict__ wgts, int C,
-                                                             int N, int r3,
+// AFF: the same scatter with the AdaGN(+SE) backward's elementwise pass folded in (training, round 6): the voxel branch of a
+// PVConv ends AdaGN -> SE3d -> devoxelize, all linear, so the gradient of the AdaGN's INPUT x is
+//     dx = A' scatter(gy) + Q + R x        (A', Q, R f32[B, C] from lion_gn_train_bwd_fold with the gate)
+// and the dense gradient of the devoxelisation never has to exist: the slab starts as Q + R x (one read of x) instead of zeros,
+// the corner contributions are added scaled by A', the slab is stored (one write of dx).  Was: store the scatter, read it twice
+// with x (reduction + apply), store dx.
+template <bool AFF>   // x, Ap, Q, R: the affine form's (nullptr without)
+__global__ __launch_bounds__(1024) void devox_bwd_lds_kernel(const float *__restrict__ gy, const int32_t *__restrict__ inds,
+                                                             const float *__restrict__ wgts, const float *__restrict__ x,
+                                                             const float *__restrict__ Ap, const float *__restrict__ Q,
+                                                             const float *__restrict__ R, int C, int N, int r3,
                                                              float *__restrict__ gx) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float *slab = reinterpret_cast<float *>(smem);
   const int tid = threadIdx.x, nt = blockDim.x;
   const int c = blockIdx.x, b = blockIdx.y;
   const int part = r3 / gridDim.z, lo = blockIdx.z * part;    // (r3 % (4 gridDim.z) == 0: checked by the launcher)
-  for (int v = tid * 4; v < part; v += nt * 4)
-    *reinterpret_cast<float4 *>(slab + v) = make_float4(0.f, 0.f, 0.f, 0.f);
+  const size_t row = (size_t)b * C + c;
+  float a = 1.f;
+  if constexpr (AFF) {
+    a = Ap[row];
+    const float q = Q[row], rr = R[row];
+    const float *xr = x + row * r3 + lo;
+    for (int v = tid * 4; v < part; v += nt * 4) {
+      const float4 t = *reinterpret_cast<const float4 *>(xr + v);
+      *reinterpret_cast<float4 *>(slab + v) = make_float4(q + rr * t.x, q + rr * t.y, q + rr * t.z, q + rr * t.w);
+    }
+  } else {
+    for (int v = tid * 4; v < part; v += nt * 4)
+      *reinterpret_cast<float4 *>(slab + v) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   __syncthreads();
-  const float *g = gy + ((size_t)b * C + c) * N;
+  const float *g = gy + row * N;
   const int32_t *id = inds + (size_t)b * 8 * N;
   const float *wg = wgts + (size_t)b * 8 * N;
   for (int i = tid; i < N; i += nt) {
-    const float gv = g[i];
+    const float gv = AFF ? a * g[i] : g[i];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int ix = min(max(id[(size_t)q * N + i], 0), r3 - 1) - lo;
@@ -683,48 +702,7 @@ __global__ __launch_bounds__(1024) void devox_bwd_lds_kernel(const float *__rest
     }
   }
   __syncthreads();
-  float *o = gx + ((size_t)b * C + c) * r3 + lo;
-  for (int v = tid * 4; v < part; v += nt * 4)
-    *reinterpret_cast<float4 *>(o + v) = *reinterpret_cast<const float4 *>(slab + v);
-}
-
-// The same scatter with the AdaGN(+SE) backward's elementwise pass folded in (training, round 6): the voxel branch of a PVConv ends
-// AdaGN -> SE3d -> devoxelize, all linear, so the gradient of the AdaGN's INPUT x is
-//     dx = A' scatter(gy) + Q + R x        (A', Q, R f32[B, C] from lion_gn_train_bwd_fold with the gate)
-// and the dense gradient of the devoxelisation never has to exist: the slab starts as Q + R x (one read of x) instead of zeros,
-// the corner contributions are added scaled by A', the slab is stored (one write of dx).  Was: store the scatter, read it twice
-// with x (reduction + apply), store dx.
-__global__ __launch_bounds__(1024) void devox_bwd_affine_kernel(const float *__restrict__ gy, const int32_t *__restrict__ inds,
-                                                                const float *__restrict__ wgts, const float *__restrict__ x,
-                                                                const float *__restrict__ Ap, const float *__restrict__ Q,
-                                                                const float *__restrict__ R, int C, int N, int r3,
-                                                                float *__restrict__ dx) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float *slab = reinterpret_cast<float *>(smem);
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int c = blockIdx.x, b = blockIdx.y;
-  const int part = r3 / gridDim.z, lo = blockIdx.z * part;
-  const size_t row = (size_t)b * C + c;
-  const float a = Ap[row], q = Q[row], rr = R[row];
-  const float *xr = x + row * r3 + lo;
-  for (int v = tid * 4; v < part; v += nt * 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(xr + v);
-    *reinterpret_cast<float4 *>(slab + v) = make_float4(q + rr * t.x, q + rr * t.y, q + rr * t.z, q + rr * t.w);
-  }
-  __syncthreads();
-  const float *g = gy + row * N;
-  const int32_t *id = inds + (size_t)b * 8 * N;
-  const float *wg = wgts + (size_t)b * 8 * N;
-  for (int i = tid; i < N; i += nt) {
-    const float gv = a * g[i];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int ix = min(max(id[(size_t)k * N + i], 0), r3 - 1) - lo;
-      if (ix >= 0 && ix < part) atomicAdd(slab + ix, mul_rn(wg[(size_t)k * N + i], gv)); // ds_add_f32
-    }
-  }
-  __syncthreads();
-  float *o = dx + row * r3 + lo;
+  float *o = gx + row * r3 + lo;
   for (int v = tid * 4; v < part; v += nt * 4)
     *reinterpret_cast<float4 *>(o + v) = *reinterpret_cast<const float4 *>(slab + v);
 }
@@ -759,14 +737,19 @@ static int devox_ring_depth() { // LION_DEVOX_RING: A/B switch (2 = one channel 
   return d < 2 ? 2 : d;
 }
 
+static int devox_ring_ct(int B, int C) {
+  int CT = 8; // one workgroup per CU: the per-cloud setup is amortised over CT channels
+  while (CT > 1 && (long)B * lion_cdiv(C, CT) < 256) CT >>= 1;
+  return CT;
+}
+
 // The ring kernel's gather (MODE 0: corners from the coordinates, MODE 1: from a stored plan), with the one choice of
 // its channels per workgroup and grid.
 template <int MODE>
 static int devox_ring_launch(const float *coords, const float *feat, int B, int C, int N, int training, float *out,
                              int32_t *inds, float *wgts, const float *scale, const float *shift, unsigned char *plan,
                              hipStream_t st) {
-  int CT = 8; // one workgroup per CU: the per-cloud setup is amortised over CT channels
-  while (CT > 1 && (long)B * lion_cdiv(C, CT) < 256) CT >>= 1;
+  const int CT = devox_ring_ct(B, C);
   return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
     return lion_launch<devox_ring_kernel<decltype(AFFINE)::value, DVR_G, MODE>>(
         dim3(lion_cdiv(C, CT), B), DVR_NT, DVR_LDS, st, coords, feat, C, N, CT, training, out, inds, wgts, scale, shift,
@@ -774,64 +757,109 @@ static int devox_ring_launch(const float *coords, const float *feat, int B, int 
   });
 }
 
+// Which forward kernel takes (B, C, N, r) with or without a 16-byte aligned grid, and everything its launch needs.
+enum DevoxKind { DEVOX_RING = 0, DEVOX_SLAB = 1, DEVOX_GATHER = 2 };
+struct DevoxPlan {
+  DevoxKind kind;
+  int PX, XS, CI, ld, slab_floats;   // the slab kernel's
+  int ct;                            // channels per workgroup: the ring's and the slab's CT, the gather's tile
+  size_t lds;
+  dim3 grid;
+};
+
+static DevoxPlan devox_plan(int B, int C, int N, int r, bool aligned) {
+  DevoxPlan p = {DEVOX_GATHER, 0, 0, 0, 0, 0, 0, 0, dim3()};
+  const int r2 = r * r;
+  if (r == DVR_R && N <= 2048 && aligned) {
+    // r = 32 (the large calls): compacted needed pieces of rows through a ring of LDS buffers
+    p.kind = DEVOX_RING;
+    p.ct = devox_ring_ct(B, C);
+    p.lds = DVR_LDS;
+    p.grid = dim3(lion_cdiv(C, p.ct), B);
+  } else if ((r2 % 4) == 0 && N <= 2048 && r2 <= 4608 && aligned) {
+    // LDS-staged path: slabs of <= 9216 floats (36 KiB), two buffers
+    p.kind = DEVOX_SLAB;
+    const int planes_max = 9216 / r2;
+    p.PX = planes_max >= r ? r : planes_max - 1;
+    p.XS = lion_cdiv(r, p.PX);
+    // small grids: CI whole channel grids per slab (<= 36 KiB), so that an iteration is worth its barrier
+    p.CI = p.XS == 1 ? (9216 / (r2 * r) < 16 ? 9216 / (r2 * r) : 16) : 1;
+    // DMA instructions per lane and slab; several slabs: PX + 1 = planes_max planes are more than 9216 - r^2 >= 4608
+    // floats, so ld is always 9 there
+    const int ld0 = lion_cdiv((p.XS == 1 ? p.CI * r2 * r : (p.PX + 1) * r2) / 4, 256);
+    p.ld = ld0 <= 1 ? 1 : ld0 <= 2 ? 2 : ld0 <= 4 ? 4 : 9;
+    p.slab_floats = p.ld * 1024; // buffer stride: every lane of every DMA instruction lands inside it
+    p.lds = (size_t)2 * p.slab_floats * 4 + (size_t)((N + 1) & ~1) * 2 + (size_t)p.XS * 4 + (size_t)((r2 + 31) / 32) * 4;
+    // channels per workgroup: amortise the per-point setup over >= 4 slabs of channels, keep >= 512 workgroups
+    p.ct = 4 * p.CI;
+    while (p.ct > p.CI && (long)B * lion_cdiv(C, p.ct) < 512) p.ct >>= 1;
+    p.grid = dim3(lion_cdiv(C, p.ct), B);
+  } else {
+    const int pt = lion_cdiv(N, 256);
+    // channel tile: keep >= ~2048 workgroups in flight, amortise the corner computation
+    p.ct = 16;
+    while (p.ct > 2 && (long)B * pt * lion_cdiv(C, p.ct) < 2048) p.ct >>= 1;
+    p.grid = dim3(pt, lion_cdiv(C, p.ct), B);
+  }
+  return p;
+}
+
+// the slab kernel's LD in {1, 2, 4, 9} and the gather kernel's channel tile in {2, 4, 8, 16} -> f(IntC<..>)
+template <typename F> static int devox_ld_dispatch(int ld, F f) {
+  switch (ld) {
+  case 1: return f(IntC<1>{});
+  case 2: return f(IntC<2>{});
+  case 4: return f(IntC<4>{});
+  default: return f(IntC<9>{});
+  }
+}
+template <typename F> static int devox_ct_dispatch(int ct, F f) {
+  switch (ct) {
+  case 16: return f(IntC<16>{});
+  case 8: return f(IntC<8>{});
+  case 4: return f(IntC<4>{});
+  default: return f(IntC<2>{});
+  }
+}
+
 extern "C" {
 
 static int devox_launch(const float *coords, const float *feat, int B, int C, int N, int r,
                         int training, float *out, int32_t *inds, float *wgts, const float *scale,
                         const float *shift, hipStream_t st) {
-  const int r2 = r * r;
-  // r = 32 (the large calls): compacted needed pieces of rows through a ring of LDS buffers
-  if (r == DVR_R && N <= 2048 && (((uintptr_t)feat) & 15) == 0) {
+  const DevoxPlan p = devox_plan(B, C, N, r, (((uintptr_t)feat) & 15) == 0);
+  if (p.kind == DEVOX_RING)
     return devox_ring_launch<0>(coords, feat, B, C, N, training, out, inds, wgts, scale, shift, nullptr, st);
-  }
-  // LDS-staged path: slabs of <= 9216 floats (36 KiB), two buffers
-  if ((r2 % 4) == 0 && N <= 2048 && r2 <= 4608 && (((uintptr_t)feat) & 15) == 0) {
-    const int planes_max = 9216 / r2;
-    const int PX = planes_max >= r ? r : planes_max - 1;
-    const int XS = lion_cdiv(r, PX);
-    // small grids: CI whole channel grids per slab (<= 36 KiB), so that an iteration is worth its barrier
-    const int CI = XS == 1 ? (9216 / (r2 * r) < 16 ? 9216 / (r2 * r) : 16) : 1;
-    const int ld0 = lion_cdiv((XS == 1 ? CI * r2 * r : (PX + 1) * r2) / 4, 256);
-    const int ld = ld0 <= 1 ? 1 : ld0 <= 2 ? 2 : ld0 <= 4 ? 4 : 9;
-    const int slab_floats = ld * 1024; // buffer stride: every lane of every DMA instruction lands inside it
-    const size_t lds = (size_t)2 * slab_floats * 4 + (size_t)((N + 1) & ~1) * 2 + (size_t)XS * 4 +
-                       (size_t)((r2 + 31) / 32) * 4;
-    // channels per workgroup: amortise the per-point setup over >= 4 slabs of channels, keep >= 512 workgroups
-    int CT = 4 * CI;
-    while (CT > CI && (long)B * lion_cdiv(C, CT) < 512) CT >>= 1;
-    dim3 grid(lion_cdiv(C, CT), B);
+  if (p.kind == DEVOX_SLAB) {
     auto slab = [&](auto LD, auto SPLIT, auto ONE) {
       return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
         return lion_launch<devox_slab_kernel<decltype(LD)::value, decltype(AFFINE)::value, decltype(SPLIT)::value,
                                              decltype(ONE)::value>>(
-            grid, 256, lds, st, coords, feat, C, N, r, PX, XS, CT, CI, slab_floats, training, out, inds, wgts, scale, shift);
+            p.grid, 256, p.lds, st, coords, feat, C, N, r, p.PX, p.XS, p.ct, p.CI, p.slab_floats, training, out, inds, wgts,
+            scale, shift);
       });
     };
-    // several slabs: PX + 1 = planes_max planes are more than 9216 - r^2 >= 4608 floats, so ld is always 9
-    if (XS > 1) {
-      if (ld != 9) return LION_EUNSUPPORTED;
-      return (r & 3) != 0 ? slab(IntC<9>{}, BoolC<true>{}, BoolC<false>{}) : slab(IntC<9>{}, BoolC<false>{}, BoolC<false>{});
+    if (p.XS > 1) {   // several slabs: the row filter, with the row-end rule when r = 4k + 2
+      if (p.ld != 9) return LION_EUNSUPPORTED;
+      return lion_with_flags((r & 3) != 0, [&](auto SPLIT) { return slab(IntC<9>{}, SPLIT, BoolC<false>{}); });
     }
-    return ld <= 1 ? slab(IntC<1>{}, BoolC<false>{}, BoolC<true>{}) : ld <= 2 ? slab(IntC<2>{}, BoolC<false>{}, BoolC<true>{})
-         : ld <= 4 ? slab(IntC<4>{}, BoolC<false>{}, BoolC<true>{}) : slab(IntC<9>{}, BoolC<false>{}, BoolC<true>{});
+    return devox_ld_dispatch(p.ld, [&](auto LD) { return slab(LD, BoolC<false>{}, BoolC<true>{}); });
   }
-  const int pt = lion_cdiv(N, 256);
-  // channel tile: keep >= ~2048 workgroups in flight, amortise the corner computation
-  int ct = 16;
-  while (ct > 2 && (long)B * pt * lion_cdiv(C, ct) < 2048) ct >>= 1;
-  dim3 grid(pt, lion_cdiv(C, ct), B);
-  auto fwd = [&](auto CT) {
+  return devox_ct_dispatch(p.ct, [&](auto CT) {
     return lion_with_flags(scale != nullptr, [&](auto AFFINE) {
       return lion_launch<devox_fwd_kernel<decltype(CT)::value, decltype(AFFINE)::value>>(
-          grid, 256, 0, st, coords, feat, C, N, r, training, out, inds, wgts, scale, shift);
+          p.grid, 256, 0, st, coords, feat, C, N, r, training, out, inds, wgts, scale, shift);
     });
-  };
-  switch (ct) {
-  case 16: return fwd(IntC<16>{});
-  case 8:  return fwd(IntC<8>{});
-  case 4:  return fwd(IntC<4>{});
-  default: return fwd(IntC<2>{});
-  }
+  });
+}
+
+// For tests only: what devox_plan decides.  out = {kind (0 ring, 1 slab, 2 gather), PX, XS, CI, ld, CT or ct, LDS bytes, grid.x}
+int lion_internal_devoxelize_path(int B, int C, int N, int r, int aligned, int32_t *out, lionStream_t) {
+  if (!out || B <= 0 || C <= 0 || N <= 0 || r <= 0) return LION_EINVAL;
+  const DevoxPlan p = devox_plan(B, C, N, r, aligned != 0);
+  const int32_t v[8] = {p.kind, p.PX, p.XS, p.CI, p.ld, p.ct, (int32_t)p.lds, (int32_t)p.grid.x};
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
+  return LION_OK;
 }
 
 int lion_trilinear_devoxelize_forward(const float *coords, const float *feat, int B, int C, int N,
@@ -887,19 +915,25 @@ int lion_trilinear_devoxelize_planned_forward(const void *plan, size_t plan_byte
   return devox_ring_launch<1>(coords, feat, B, C, N, 0, out, nullptr, nullptr, scale, shift, pl, st);
 }
 
+// The LDS backward's launch from r3 (r3 * 4 <= 128 KiB, r3 % 4 == 0): parts of a (b, c) slab, threads, LDS bytes per workgroup.
+// (64, 2048, 32), B = 32, one box: 1 part 203 us, 2 parts 189 us, 4 parts 254 us, 8 parts 349 us -- every workgroup scans
+// all 8 N (index, weight) pairs, so more parts cost more than their overlap returns
+struct DevoxBwdPlan { int parts, nt; size_t lds; };
+static DevoxBwdPlan devox_bwd_plan(int r3) {
+  int parts = (size_t)r3 * 4 > 64 * 1024 ? 2 : 1;
+  if (r3 % (4 * parts) != 0) parts = 1;
+  return {parts, r3 >= 16384 ? 1024 : 256, (size_t)(r3 / parts) * 4};
+}
+
 int lion_trilinear_devoxelize_backward(const float *gy, const int32_t *inds, const float *wgts,
                                        int B, int C, int N, int r3, float *gx,
                                        lionStream_t stream) {
   if (!gy || !inds || !wgts || !gx || B <= 0 || C <= 0 || N <= 0 || r3 <= 0) return LION_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if ((size_t)r3 * 4 <= 128 * 1024 && (r3 % 4) == 0) {
-    // (64, 2048, 32), B = 32, one box: 1 part 203 us, 2 parts 189 us, 4 parts 254 us, 8 parts 349 us -- every workgroup scans
-    // all 8 N (index, weight) pairs, so more parts cost more than their overlap returns
-    int parts = (size_t)r3 * 4 > 64 * 1024 ? 2 : 1;
-    if (r3 % (4 * parts) != 0) parts = 1;
-    const size_t lds = (size_t)(r3 / parts) * 4;
-    const int nt = r3 >= 16384 ? 1024 : 256;
-    return lion_launch<devox_bwd_lds_kernel>(dim3(C, B, parts), nt, lds, st, gy, inds, wgts, C, N, r3, gx);
+    const DevoxBwdPlan p = devox_bwd_plan(r3);
+    return lion_launch<devox_bwd_lds_kernel<false>>(dim3(C, B, p.parts), p.nt, p.lds, st, gy, inds, wgts, nullptr, nullptr,
+                                                    nullptr, nullptr, C, N, r3, gx);
   }
   hipError_t e = hipMemsetAsync(gx, 0, (size_t)B * C * r3 * 4, st);
   if (e != hipSuccess) return (int)e;
@@ -908,18 +942,15 @@ int lion_trilinear_devoxelize_backward(const float *gy, const int32_t *inds, con
                                               C, N, r3, CT, gx);
 }
 
-// dx f32[B,C,r3] = A' scatter(gy) + Q + R x  (see devox_bwd_affine_kernel); x f32[B,C,r3] 16-byte aligned, r3 * 4 <= 128 KiB, r3 % 8 == 0
+// dx f32[B,C,r3] = A' scatter(gy) + Q + R x  (devox_bwd_lds_kernel<true>); x f32[B,C,r3] 16-byte aligned, r3 * 4 <= 128 KiB, r3 % 8 == 0
 int lion_trilinear_devoxelize_backward_affine(const float *gy, const int32_t *inds, const float *wgts, const float *x,
                                               const float *Ap, const float *Q, const float *R, int B, int C, int N, int r3,
                                               float *dx, lionStream_t stream) {
   if (!gy || !inds || !wgts || !x || !Ap || !Q || !R || !dx || B <= 0 || C <= 0 || N <= 0 || r3 <= 0) return LION_EINVAL;
   if ((size_t)r3 * 4 > 128 * 1024 || (r3 % 8) != 0 || (((uintptr_t)x | (uintptr_t)dx) & 15) != 0) return LION_EUNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int parts = (size_t)r3 * 4 > 64 * 1024 ? 2 : 1;
-  const size_t lds = (size_t)(r3 / parts) * 4;
-  const int nt = r3 >= 16384 ? 1024 : 256;
-  return lion_launch<devox_bwd_affine_kernel>(dim3(C, B, parts), nt, lds, st, gy, inds, wgts, x, Ap, Q, R, C, N, r3,
-                                              dx);
+  const DevoxBwdPlan p = devox_bwd_plan(r3);   // (r3 % 8 == 0: two parts stay two)
+  return lion_launch<devox_bwd_lds_kernel<true>>(dim3(C, B, p.parts), p.nt, p.lds, static_cast<hipStream_t>(stream), gy, inds,
+                                                 wgts, x, Ap, Q, R, C, N, r3, dx);
 }
 
 } // extern "C"

@@ -29,9 +29,59 @@ constexpr int VT = 1024;    // threads of the per-cloud index kernel
 constexpr int MAXP = 8;     // points per thread kept in registers  (N <= 8192)
 constexpr int LDS_LIMIT = 160 * 1024;
 constexpr int PREFETCH_PAD = 2 * 16 * 4;   // bytes: 2 * PW words behind the arena (vox_means_and_store, phase B2)
+// channel chunk (as many as the arena holds).  Round 3 sweep at (64,2048,32), us with / without P1: 8: 77.5 / 75.3,
+// 16: 72.9 / 67.6, 24: 65.9 / 63.4, 32: 66.7 / 64.0, 64: 64.3 / 62.1
+constexpr int CH_CAP = 64;
 
 __device__ __forceinline__ int padv(int v) { return v + (v >> 5); }
 __host__ __device__ inline int align4i(int x) { return (x + 3) & ~3; }
+
+// The dynamic LDS of the two kernels: where each region starts, from the start of the allocation.  The kernel asks with
+// Cur = its int32 pointer to smem, vox_plan with Cur = a word count from 0 (arena = the fixed part; arena_words and
+// PREFETCH_PAD bytes follow it).  n_words comes as ptrdiff_t: the caller widens it once, in front of its other uses.
+#define LDS_AT static __host__ __device__ __forceinline__ Cur
+template <typename Cur> struct FusedLds {   // slot[svp] | ust[n_words] | fscr[FSCR] | iscr[ISCR] | arena
+  static constexpr int FSCR = 64, ISCR = 32;
+  static __host__ __device__ __forceinline__ int svp(int SV) { return ((SV + (SV >> 5) + 3) & ~3) + 4; }   // padded (1 word per 32) + 16-byte aligned
+  LDS_AT ust(Cur slot, int SV) { return slot + svp(SV); }
+  LDS_AT fscr(Cur slot, int SV, ptrdiff_t n_words) { return ust(slot, SV) + n_words; }
+  LDS_AT iscr(Cur slot, int SV, ptrdiff_t n_words) { return fscr(slot, SV, n_words) + FSCR; }
+  LDS_AT arena(Cur slot, int SV, ptrdiff_t n_words) { return iscr(slot, SV, n_words) + ISCR; }
+  LDS_AT tmp(Cur slot, int SV, ptrdiff_t n_words) { return arena(slot, SV, n_words) + svp(SV); }   // phase A: hist[svp] | tmp[n_words] in the arena
+  LDS_AT end_a(Cur slot, int SV, ptrdiff_t n_words) { return tmp(slot, SV, n_words) + n_words; }
+};
+template <typename Cur> struct ScatterLds {   // slot[SV] | ust[n_words] | hdr[HDR] | arena
+  static constexpr int HDR = 64;   // [16][4]: points, occupied voxels, channels per chunk, chunks left with the owner
+  LDS_AT ust(Cur slot, int SV) { return slot + SV; }
+  LDS_AT hdr(Cur slot, int SV, ptrdiff_t n_words) { return ust(slot, SV) + n_words; }
+  LDS_AT arena(Cur slot, int SV, ptrdiff_t n_words) { return hdr(slot, SV, n_words) + HDR; }
+};
+#undef LDS_AT
+constexpr int ROWNEED_BYTES = 1024;   // static LDS of the READ scatter: one byte per z-row of a slab (SV / r <= 1024)
+
+// Workgroup L of either kernel -> (cloud, voxel slab, channel range).  Workgroups go round-robin over the 8 XCDs: the
+// S * CS workgroups of a cloud stay on one XCD so that its feature rows are fetched into one L2 only; clouds come in
+// groups of 8 (vox_grid rounds B up), wq = slab + S * cs.
+struct VoxWg { int b, slab, cs, wq; };
+__device__ __forceinline__ VoxWg vox_wg(int L, int S, int CS) {
+  const int W = S * CS; // workgroups per cloud: S voxel slabs x CS channel ranges
+  const int grp = L / (8 * W), j8 = L - grp * 8 * W;
+  const int b = grp * 8 + (j8 & 7), wq = j8 >> 3, slab = wq % S, cs = wq / S;
+  return {b, slab, cs, wq};
+}
+inline int vox_grid(int B, int S, int CS) { return ((B + 7) / 8) * 8 * S * CS; }
+
+// P1 (pvcnn2_ada.py:173-188), bit-exact against the oracle: the normalisation's denominator from the largest centred
+// norm, and a centred coordinate -> voxel coordinate in [0, r - 1] (its voxel is rintf of it)
+__device__ __forceinline__ float p1_denom(float max_norm, float eps) { return add_rn(mul_rn(max_norm, 2.0f), eps); }
+__device__ __forceinline__ float p1_voxel_coord(float c, float mean, float denom, int normalize, int r) {
+  const float hi = (float)(r - 1), rf = (float)r;
+  float v = sub_rn(c, mean);
+  v = normalize ? add_rn(div_rn(v, denom), 0.5f) : div_rn(add_rn(v, 1.0f), 2.0f);
+  v = mul_rn(v, rf);
+  v = v < 0.0f ? 0.0f : v;
+  return v > hi ? hi : v;
+}
 
 // LDS counter increment of every valid lane's slot, aggregated per wave: the lanes that share a slot send ONE atomic (their
 // number), each takes base + its rank among them.  The latents of the sampling chain put 100+ of a cloud's 2048 points into
@@ -216,21 +266,19 @@ __global__ __launch_bounds__(VT) void vox_fused_kernel(
     int arena_words, int ch_cap, int normalize, float eps, float *__restrict__ out,
     float *__restrict__ norm_coords, int32_t *__restrict__ ind, int32_t *__restrict__ cnt, void *plan) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int SVP = ((SV + (SV >> 5) + 3) & ~3) + 4;         // padded (1 word per 32) + 16-byte aligned
-  int32_t *slot = reinterpret_cast<int32_t *>(smem);       // [SVP] arrival counters, later dense slots
-  int32_t *ust = slot + SVP;                               // [nw] (start << 16) | count per occupied voxel
-  float *fscr = reinterpret_cast<float *>(ust + n_words);  // 64
-  int *iscr = reinterpret_cast<int *>(fscr + 64);          // 32
-  float *arena = reinterpret_cast<float *>(iscr + 32);     // [arena_words]
-  uint32_t *hist = reinterpret_cast<uint32_t *>(arena);    // [SVP] count, later (urank << 16) | count
-  int32_t *tmp = reinterpret_cast<int32_t *>(hist + SVP);  // [nw] bucket contents in arrival order
+  using Lds = FusedLds<int32_t *>;
+  const int SVP = Lds::svp(SV);
+  int32_t *slot = reinterpret_cast<int32_t *>(smem);                       // [SVP] arrival counters, later dense slots
+  int32_t *ust = Lds::ust(slot, SV);                                       // [nw] (start << 16) | count per occupied voxel
+  float *fscr = reinterpret_cast<float *>(Lds::fscr(slot, SV, n_words));
+  int *iscr = Lds::iscr(slot, SV, n_words);
+  float *arena = reinterpret_cast<float *>(Lds::arena(slot, SV, n_words)); // [arena_words]
+  uint32_t *hist = reinterpret_cast<uint32_t *>(arena);                    // [SVP] count, later (urank << 16) | count
+  int32_t *tmp = Lds::tmp(slot, SV, n_words);                              // [nw] bucket contents in arrival order
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // workgroups go round-robin over the 8 XCDs: keep the S slabs of a cloud on one XCD so that
-  // its feature rows are fetched into one L2 only
-  const int W = S * CS; // workgroups per cloud: S voxel slabs x CS channel ranges
-  const int L = blockIdx.x, grp = L / (8 * W), j8 = L - grp * 8 * W;
-  const int b = grp * 8 + (j8 & 7), wq = j8 >> 3, slab = wq % S, cs = wq / S;
+  const VoxWg wg = vox_wg(blockIdx.x, S, CS);
+  const int b = wg.b, wq = wg.wq, slab = wg.slab, cs = wg.cs;
   if (b >= B) return;
   const int r2 = r * r, r3 = r2 * r;
   const int lo = slab * SV;
@@ -294,10 +342,9 @@ __global__ __launch_bounds__(VT) void vox_fused_kernel(
       __syncthreads();
       float m2 = fscr[48 + (lane & 15)];
       m2 = row16_max(m2);
-      denom = add_rn(mul_rn(m2, 2.0f), eps);
+      denom = p1_denom(m2, eps);
     }
     float *nc = norm_coords + (size_t)b * 3 * N;
-    const float rf = (float)r, hi = (float)(r - 1);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int i = tid + p * VT;
@@ -307,11 +354,7 @@ __global__ __launch_bounds__(VT) void vox_fused_kernel(
         int q[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-          float v = sub_rn(c3[a], mean[a]);
-          v = normalize ? add_rn(div_rn(v, denom), 0.5f) : div_rn(add_rn(v, 1.0f), 2.0f);
-          v = mul_rn(v, rf);
-          v = v < 0.0f ? 0.0f : v;
-          v = v > hi ? hi : v;
+          const float v = p1_voxel_coord(c3[a], mean[a], denom, normalize, r);
           if (wq == 0) nc[i + a * N] = v;
           q[a] = (int)rintf(v);
         }
@@ -446,7 +489,7 @@ __device__ __forceinline__ bool vox_row_has_reader(const int32_t *fl, int row, i
   return need != 0;
 }
 
-// vox_scatter_kernel: phases B + C from a stored plan.  LDS (dynamic): slot[SV] | ust[n_words] | arena.
+// vox_scatter_kernel: phases B + C from a stored plan.  LDS (dynamic): ScatterLds.
 template <int NP, bool READ>
 __global__ __launch_bounds__(VT) void vox_scatter_kernel(
     const float *__restrict__ feat, const void *__restrict__ plan, int B, int C, int N, int r3, int S, int CS, int SV,
@@ -454,13 +497,12 @@ __global__ __launch_bounds__(VT) void vox_scatter_kernel(
     int TH) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int32_t *slot = reinterpret_cast<int32_t *>(smem);
-  int32_t *ust = slot + SV;
-  int32_t *hdr_s = ust + n_words;   // [16][4]: points, occupied voxels, channels per chunk, chunks left with the owner
-  float *arena = reinterpret_cast<float *>(hdr_s + 64);
+  using Lds = ScatterLds<int32_t *>;
+  int32_t *ust = Lds::ust(slot, SV), *hdr_s = Lds::hdr(slot, SV, n_words);
+  float *arena = reinterpret_cast<float *>(Lds::arena(slot, SV, n_words));
   const int tid = threadIdx.x;
-  const int W = S * CS;
-  const int L = blockIdx.x, grp = L / (8 * W), j8 = L - grp * 8 * W;
-  const int b = grp * 8 + (j8 & 7), wq = j8 >> 3, slab = wq % S, cs = wq / S;
+  const VoxWg wg = vox_wg(blockIdx.x, S, CS);
+  const int b = wg.b, slab = wg.slab, cs = wg.cs;
   if (b >= B) return;
   const VoxPlanPtrs pl = vox_plan_ptrs(const_cast<void *>(plan), B, N, S);
   // Round 5 -- empty slabs adopt the extra chunks of crowded ones.  A slab whose points x channels do not fit the LDS arena
@@ -606,7 +648,7 @@ __global__ __launch_bounds__(VT) void vox_scatter_kernel(
     // it stages the halo -- one voxel in d and h, all of w -- of the tiles with a point within one voxel, nothing else.  A
     // z-row (d, h) outside every such halo is never read: its voxels (all empty -- a point's own row lies inside an occupied
     // tile) get slot -2 and phase C stores nothing there.  The chain's clouds leave ~70 % of an r = 32 grid unread.
-    __shared__ unsigned char rowneed[1024];   // rows of this slab (SV / r <= 1024)
+    __shared__ unsigned char rowneed[ROWNEED_BYTES];   // rows of this slab
     const int nth = r / TH, ntiles = (r / TD) * nth, row0 = (slab_u * SV) / r, nrows = SV / r;
     const int32_t *fl = occ_flags + (size_t)b * ntiles;
     for (int q = tid; q < nrows; q += VT) rowneed[q] = vox_row_has_reader(fl, row0 + q, r, TD, TH, nth);
@@ -691,16 +733,11 @@ __global__ __launch_bounds__(VT) void p1_kernel(const float *__restrict__ coords
     __syncthreads();
     float m2 = fscr[lane & 15];
     for (int s = 1; s < 16; s <<= 1) { const float o = __shfl_xor(m2, s, 64); m2 = o > m2 ? o : m2; }
-    denom = add_rn(mul_rn(m2, 2.0f), eps);
+    denom = p1_denom(m2, eps);
   }
-  const float rf = (float)r, hi = (float)(r - 1);
   for (int a = 0; a < 3; ++a)
     for (int k = tid; k < N; k += VT) {
-      float v = sub_rn(co[k + (size_t)a * N], mean[a]);
-      v = normalize ? add_rn(div_rn(v, denom), 0.5f) : div_rn(add_rn(v, 1.0f), 2.0f);
-      v = mul_rn(v, rf);
-      v = v < 0.0f ? 0.0f : v;
-      v = v > hi ? hi : v;
+      const float v = p1_voxel_coord(co[k + (size_t)a * N], mean[a], denom, normalize, r);
       norm_coords[(size_t)b * 3 * N + k + (size_t)a * N] = v;
       vox[(size_t)b * 3 * N + k + (size_t)a * N] = (int)rintf(v);
     }
@@ -724,55 +761,74 @@ __global__ __launch_bounds__(256) void vox_grad_kernel(const float *__restrict__
   }
 }
 
+// Everything a launch site needs, for the fused kernel (the index kernel is its C = 0 form), the scatter kernel and the
+// scatter kernel whose grid has a single reader (lion_voxel_scatter_read).
+enum VoxKind { VOX_FUSED = 0, VOX_SCATTER = 1, VOX_SCATTER_READ = 2 };
 struct VoxPlan {
-  bool fast;
-  int S, CS, SV, n_words, arena_words, NP;
+  bool fast;          // the kernel takes the shape; otherwise: the fallback (fused) or LION_EUNSUPPORTED (scatter)
+  int S, CS, SV, NP, n_words, arena_words, grid;
   size_t lds;
-  size_t off_vox, total;
+  size_t ws_bytes;    // the fallback's workspace: the int coordinates of its stand-alone P1
 };
 
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static VoxPlan make_plan(int B, int C, int N, int r) {
+static VoxPlan vox_plan(int B, int C, int N, int r, VoxKind kind) {
   VoxPlan p;
   const long r3 = (long)r * r * r;
   // Clouds of <= 1024 points (one point per thread: 42 registers, 8 waves per SIMD) run TWO workgroups per CU on half the
   // LDS each: one's index / mean phases overlap the other's store phase ((128,1024,16), B = 32: 41 -> 35 us).  The
   // 2048-point kernel needs 74 registers (one workgroup per CU); forced to 62 and split into 16 slabs it is slower
-  // (70 -> 74 us), so r = 32 keeps one workgroup per CU.
+  // (70 -> 74 us), so r = 32 keeps one workgroup per CU.  (The scatter kernel needs 40 registers at every N, but two
+  // workgroups per CU for every cloud size measured slower there too: round 4, (64,2048,32), 66 us against 58.)
   const bool two_per_cu = N <= VT;
   const long wgs = two_per_cu ? 512 : 256;
-  // PREFETCH_PAD: phase B2's double-buffered operand fetch reads up to 2 * PW (= 32) words past a voxel's run; for the last
-  // row of the arena that is past the arena itself -- the words are never added, but they are allocated
-  const size_t lds_limit = (two_per_cu ? (size_t)LDS_LIMIT / 2 : (size_t)LDS_LIMIT) - PREFETCH_PAD;
   // slabs per cloud: enough workgroups to touch every CU, slabs of >= 512 voxels (int4 groups)
   int S = 1;
   while (S < 16 && (long)B * S < wgs && r3 / (S * 2) >= 512 && (r3 % (S * 2 * 4)) == 0) S *= 2;
   p.S = S;
-  // ... and, for small grids, ranges of channels (each workgroup redoes the cheap index phase)
+  p.SV = (int)(r3 / S);
+  // ... and, for small grids, ranges of channels (each workgroup redoes the cheap index phase / the plan's prologue)
   int CS = 1;
   while ((long)B * S * CS < wgs && C / (CS * 2) >= 8) CS *= 2;
+  // ... but a 1024-thread scatter workgroup that stores fewer than 8192 floats is mostly launch and prologue: it takes twice
+  // the channels as long as one workgroup per CU remains.  r = 8, B = 32, C = 128 (512 workgroups of 8 channels -> 256 of 16):
+  // 10.3 -> 7.7 us per launch; a plain "256 workgroups" rule costs the r = 16 calls (8 slabs, 128 channels) 28 -> 34 us
+  // (profiles/small_grid_vox_devox_ab.txt).
+  if (kind != VOX_FUSED && two_per_cu)
+    while (CS > 1 && (long)p.SV * ((C + CS - 1) / CS) < 8192 && (long)B * S * (CS / 2) >= 256) CS /= 2;
   p.CS = CS;
-  p.SV = (int)(r3 / S);
   p.n_words = align4i(N);
   p.NP = N <= VT ? 1 : N <= 2 * VT ? 2 : N <= 4 * VT ? 4 : 8;
-  const size_t svp = (((size_t)p.SV + (p.SV >> 5) + 3) & ~(size_t)3) + 4;
-  const size_t fixed = (svp + (size_t)p.n_words + 64 + 32) * 4;
-  // arena: phase A needs hist + tmp; afterwards (points + occupied voxels of the slab) floats per
-  // channel, for as many channels as fit
-  const size_t need_a = (svp + (size_t)p.n_words) * 4;
-  const size_t nocc = (size_t)(N < p.SV ? N : p.SV);
-  size_t want = ((size_t)N + 1 + nocc) * (C > 0 ? C : 1) * 4;   // (rows of N | 1 words: vox_means_and_store)
-  if (want < need_a) want = need_a;
-  const size_t avail = fixed < lds_limit ? lds_limit - fixed : 0;
-  const size_t arena = want < avail ? want : avail;
-  p.arena_words = (int)(arena / 4);
-  p.lds = fixed + (size_t)p.arena_words * 4 + PREFETCH_PAD;
-  p.fast = r3 <= (1L << 17) && (r3 % 4 == 0) && (p.SV % 4 == 0) && N <= MAXP * VT && N >= 1 &&
-           arena >= need_a && (size_t)p.arena_words >= (size_t)N + 1 + nocc;
-  size_t o = 0;
-  p.off_vox = o; o += up256((size_t)B * 3 * N * 4); // int coords (fallback P1)
-  p.total = o;
+  p.grid = vox_grid(B, S, CS);
+  p.ws_bytes = up256((size_t)B * 3 * N * 4);
+  // PREFETCH_PAD: phase B2's double-buffered operand fetch reads up to 2 * PW (= 32) words past a voxel's run; for the last
+  // row of the arena that is past the arena itself -- the words are never added, but they are allocated
+  const size_t lds_limit = (two_per_cu ? (size_t)LDS_LIMIT / 2 : (size_t)LDS_LIMIT) - PREFETCH_PAD;
+  // arena: (points + occupied voxels of the slab) floats per channel (rows of N | 1 words: vox_means_and_store), for as
+  // many channels as fit in what `fixed` bytes leave of `limit`, asking for `floor` bytes at least.  -> words (all sizes
+  // are multiples of 4); the shape fits when they hold the floor and one channel's row.
+  const size_t nocc = (size_t)(N < p.SV ? N : p.SV), row = (size_t)N + 1 + nocc;
+  auto arena_words = [&](size_t fixed, size_t limit, size_t floor) {
+    size_t want = row * (C > 0 ? C : 1) * 4;
+    if (want < floor) want = floor;
+    const size_t avail = fixed < limit ? limit - fixed : 0;
+    return (want < avail ? want : avail) / 4;
+  };
+  // the fused kernel's phase A needs hist + tmp in the arena; a shape it refuses has no index plan, so no scatter either
+  using Fused = FusedLds<size_t>;
+  const size_t phase_a = Fused::end_a(0, p.SV, p.n_words) - Fused::arena(0, p.SV, p.n_words);
+  size_t fixed = Fused::arena(0, p.SV, p.n_words) * 4, aw = arena_words(fixed, lds_limit, phase_a * 4);
+  p.fast = r3 <= (1L << 17) && (r3 % 4 == 0) && (p.SV % 4 == 0) && N <= MAXP * VT && N >= 1 && aw >= phase_a && aw >= row;
+  if (kind != VOX_FUSED) {
+    // (the static LDS of the reader-aware instantiation -- its row map and 64 bytes of margin -- comes out of the same budget)
+    const size_t read = kind == VOX_SCATTER_READ ? ROWNEED_BYTES + 64 : 0;
+    fixed = ScatterLds<size_t>::arena(0, p.SV, p.n_words) * 4;
+    aw = arena_words(fixed, lds_limit - read, 0);
+    p.fast = p.fast && aw >= row;
+  }
+  p.arena_words = (int)aw;
+  p.lds = fixed + aw * 4 + PREFETCH_PAD;
   return p;
 }
 
@@ -795,20 +851,17 @@ static int voxelize_impl(const float *feat, const int32_t *coords_i, const float
   if (!coords_i && !coords_f) return LION_EINVAL;
   if (coords_f && !norm_coords) return LION_EINVAL;
   if ((long)r * r * r > (1L << 30)) return LION_EUNSUPPORTED;
-  const VoxPlan p = make_plan(B, feat ? C : 0, N, r);
+  const VoxPlan p = vox_plan(B, feat ? C : 0, N, r, VOX_FUSED);
   if (plan) {   // index mode (lion_voxel_index): fast path only, no workspace
     if (!p.fast || ((((uintptr_t)cnt) & 15) != 0)) return LION_EUNSUPPORTED;
-  } else if (!ws || ws_bytes < p.total) return LION_EWORKSPACE;
+  } else if (!ws || ws_bytes < p.ws_bytes) return LION_EWORKSPACE;
   const int r3 = r * r * r;
-  char *w = static_cast<char *>(ws);
   const bool aligned = (((uintptr_t)out | (uintptr_t)cnt) & 15) == 0;   // (out == nullptr in index mode)
   if (p.fast && aligned) {
-    const int grid = ((B + 7) / 8) * 8 * p.S * p.CS;
-    const int ch_cap = 64; // channel chunk (as many as the arena holds).  Round 3 sweep at (64,2048,32), us with / without P1: 8: 77.5 / 75.3, 16: 72.9 / 67.6, 24: 65.9 / 63.4, 32: 66.7 / 64.0, 64: 64.3 / 62.1
     return lion_with_flags(coords_f != nullptr, [&](auto P1) {
       return vox_np_dispatch(p.NP, [&](auto NPV) {
         return lion_launch<vox_fused_kernel<decltype(P1)::value, decltype(NPV)::value>>(
-            grid, VT, p.lds, st, feat, coords_i, coords_f, B, C, N, r, p.S, p.CS, p.SV, p.n_words, p.arena_words, ch_cap,
+            p.grid, VT, p.lds, st, feat, coords_i, coords_f, B, C, N, r, p.S, p.CS, p.SV, p.n_words, p.arena_words, CH_CAP,
             normalize, eps, out, norm_coords, ind, cnt, plan);
       });
     });
@@ -816,7 +869,7 @@ static int voxelize_impl(const float *feat, const int32_t *coords_i, const float
   // fallback
   const int32_t *ci = coords_i;
   if (coords_f) {
-    int32_t *vox = reinterpret_cast<int32_t *>(w + p.off_vox);
+    int32_t *vox = static_cast<int32_t *>(ws);
     if (int e = lion_launch<p1_kernel>(B, VT, 0, st, coords_f, N, r, normalize, eps, norm_coords, vox)) return e;
     ci = vox;
   }
@@ -842,9 +895,8 @@ extern "C" {
 int lion_abi_version(void) { return 1; }
 
 size_t lion_avg_voxelize_workspace_bytes(int B, int C, int N, int r) {
-  (void)C;
   if (B <= 0 || N <= 0 || r <= 0) return 0;
-  return make_plan(B, C, N, r).total;
+  return vox_plan(B, C, N, r, VOX_FUSED).ws_bytes;
 }
 
 int lion_avg_voxelize_forward(const float *feat, const int32_t *coords, int B, int C, int N, int r,
@@ -866,7 +918,7 @@ int lion_voxelize_points_forward(const float *feat, const float *coords, int B, 
 
 size_t lion_voxel_plan_bytes(int B, int N, int r) {
   if (B <= 0 || N <= 0 || r <= 0 || (long)r * r * r > (1L << 30)) return 0;
-  const VoxPlan p = make_plan(B, 0, N, r);
+  const VoxPlan p = vox_plan(B, 0, N, r, VOX_FUSED);
   if (!p.fast) return 0;
   return vox_plan_words(B, N, p.S) * 4;
 }
@@ -887,36 +939,8 @@ static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_b
   const size_t need = lion_voxel_plan_bytes(B, N, r);
   if (need == 0 || (((uintptr_t)out) & 15) != 0) return LION_EUNSUPPORTED;
   if (plan_bytes < need) return LION_EWORKSPACE;
-  const VoxPlan p0 = make_plan(B, C, N, r);
-  if (!p0.fast) return LION_EUNSUPPORTED;
-  VoxPlan p = p0;
-  // Option: TWO workgroups per CU for every cloud size (the scatter kernel needs 40 registers): one's mean phase (B) under
-  // the other's store phase (C).  Half the LDS each -> more channel chunks; 512 workgroups -> channel ranges (the plan
-  // makes the per-workgroup prologue cheap).  Measured (round 4, (64,2048,32)): 66 us against 58 with one workgroup per CU -- off; -DLION_VOXS_TWO=1 builds it.
-#ifndef LION_VOXS_TWO
-#define LION_VOXS_TWO 0
-#endif
-  const bool two_per_cu = LION_VOXS_TWO || N <= VT;
-  if (two_per_cu) {
-    int CS = 1;
-    while ((long)B * p.S * CS < 512 && C / (CS * 2) >= 8) CS *= 2;
-    // ... but a 1024-thread workgroup that stores fewer than 8192 floats is mostly launch and prologue: it takes twice the
-    // channels as long as one workgroup per CU remains.  r = 8, B = 32, C = 128 (512 workgroups of 8 channels -> 256 of 16):
-    // 10.3 -> 7.7 us per launch; a plain "256 workgroups" rule costs the r = 16 calls (8 slabs, 128 channels) 28 -> 34 us
-    // (profiles/small_grid_vox_devox_ab.txt).
-    while (CS > 1 && (long)p.SV * ((C + CS - 1) / CS) < 8192 && (long)B * p.S * (CS / 2) >= 256) CS /= 2;
-    p.CS = CS;
-  }
-  // (the static LDS of the reader-aware instantiation -- its 1-KiB row map -- comes out of the same budget)
-  const size_t lds_limit = (two_per_cu ? (size_t)LDS_LIMIT / 2 : (size_t)LDS_LIMIT) - PREFETCH_PAD - (occ_flags ? 1024 + 64 : 0);
-  const size_t fixed = ((size_t)p.SV + (size_t)p.n_words + 64) * 4;   // slot | ust | the cloud's slab headers
-  const size_t nocc = (size_t)(N < p.SV ? N : p.SV);
-  const size_t want = ((size_t)N + 1 + nocc) * C * 4;
-  const size_t avail = fixed < lds_limit ? lds_limit - fixed : 0;
-  const size_t arena = want < avail ? want : avail;
-  if (arena / 4 < (size_t)N + 1 + nocc) return LION_EUNSUPPORTED;
-  const size_t lds = fixed + arena + PREFETCH_PAD;
-  const int grid = ((B + 7) / 8) * 8 * p.S * p.CS;
+  const VoxPlan p = vox_plan(B, C, N, r, occ_flags ? VOX_SCATTER_READ : VOX_SCATTER);
+  if (!p.fast) return LION_EUNSUPPORTED;
   const int r3 = r * r * r;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the tile geometry of the flags: the sparse convolution's own (conv3d_tiles.h); without flags occ_td = occ_th = 0
@@ -924,7 +948,7 @@ static int voxel_scatter_impl(const float *feat, const void *plan, size_t plan_b
   return lion_with_flags(occ_flags != nullptr, [&](auto READ) {
     return vox_np_dispatch(p.NP, [&](auto NPV) {
       return lion_launch<vox_scatter_kernel<decltype(NPV)::value, decltype(READ)::value>>(
-          grid, VT, lds, st, feat, plan, B, C, N, r3, p.S, p.CS, p.SV, p.n_words, (int)(arena / 4), 64, out, occ_flags, r,
+          p.grid, VT, p.lds, st, feat, plan, B, C, N, r3, p.S, p.CS, p.SV, p.n_words, p.arena_words, CH_CAP, out, occ_flags, r,
           occ_t.td, occ_t.th);
     });
   });
@@ -942,6 +966,17 @@ int lion_voxel_scatter_read(const float *feat, const void *plan, size_t plan_byt
   if (!occ_m1) return LION_EINVAL;
   if (r != 16 && r != 32) return LION_EUNSUPPORTED;
   return voxel_scatter_impl(feat, plan, plan_bytes, B, C, N, r, out, occ_m1, stream);
+}
+
+// For tests only: what vox_plan gives the fused kernel (kind 0), the scatter kernel (1) or the reader-aware scatter (2).
+int lion_internal_voxelize_plan(int B, int C, int N, int r, int kind, int32_t *out, lionStream_t) {
+  if (!out || B <= 0 || C < (kind == VOX_FUSED ? 0 : 1) || N <= 0 || r <= 0 || kind < VOX_FUSED || kind > VOX_SCATTER_READ)
+    return LION_EINVAL;
+  if ((long)r * r * r > (1L << 30)) return LION_EUNSUPPORTED;
+  const VoxPlan p = vox_plan(B, C, N, r, static_cast<VoxKind>(kind));
+  const int32_t v[8] = {p.S, p.CS, p.SV, p.NP, p.n_words, p.arena_words, (int32_t)p.lds, p.grid};
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
+  return p.fast ? LION_OK : LION_EUNSUPPORTED;
 }
 
 int lion_avg_voxelize_backward(const float *gy, const int32_t *ind, const int32_t *cnt, int B,

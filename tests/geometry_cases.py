@@ -27,7 +27,7 @@ def seed_of(text):
 
 
 # =============================================================================================================
-# devoxelize forward: devox_launch of csrc/devoxelize.hip, line for line
+# devoxelize forward: devox_plan of csrc/devoxelize.hip, line for line (lion_internal_devoxelize_path asks the library)
 # =============================================================================================================
 
 def devox_path(B, C, N, r, aligned=True):
@@ -181,7 +181,7 @@ def devox_reads_split_piece(co_b, r):
     return bool(np.any((row % 2 == 1) & ~need[row - 1] & (z0 < 2)))
 
 
-# ---- devoxelize backward: lion_trilinear_devoxelize_backward ---------------------------------------------------
+# ---- devoxelize backward: lion_trilinear_devoxelize_backward with devox_bwd_plan -------------------------------
 
 def devox_bwd_path(r):
     r3 = r ** 3

@@ -2,6 +2,8 @@
 launcher's choice (recomputed from the formulas of the .hip files) is the one a case is filed under, and a constructed
 cloud has the property it is named for.  tests/test_geometry_paths_gpu.py runs exactly these cases on the device; none is
 skipped or filtered there."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -13,6 +15,56 @@ def ids(cases):
 
 
 # ---- devoxelize forward -------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def lib():
+    from lion_amd import _lib
+    return _lib.load()
+
+
+DEVOX_KINDS = ("ring", "slab", "gather")
+
+
+def assert_devox_path_equals_library(lib, B, C, N, r, aligned):
+    """gc.devox_path against lion_internal_devoxelize_path {kind, PX, XS, CI, ld, CT or ct, LDS bytes, grid.x}, field for
+    field; the grid's x (not among the restatement's fields) is the workgroups over the channels, or over the points"""
+    out = (ctypes.c_int32 * 8)()
+    assert lib.lion_internal_devoxelize_path(B, C, N, r, int(aligned), out, None) == 0
+    kind, PX, XS, CI, ld, ct, lds, gx = out
+    want = gc.devox_path(B, C, N, r, aligned)
+    assert DEVOX_KINDS[kind] == want["kernel"], (B, C, N, r, aligned, list(out), want)
+    if want["kernel"] == "slab":
+        assert dict(kernel="slab", PX=PX, XS=XS, CI=CI, ld=ld, CT=ct) == want, (B, C, N, r, list(out), want)
+        assert gx == gc.cdiv(C, ct) and 2 * ld * 4096 < lds <= 160 * 1024
+    elif want["kernel"] == "gather":
+        assert (PX, XS, CI, ld, ct, lds, gx) == (0, 0, 0, 0, want["ct"], 0, gc.cdiv(N, 256)), (B, C, N, r, list(out), want)
+    else:
+        assert (PX, XS, CI, ld) == (0, 0, 0, 0) and gx == gc.cdiv(C, ct) and 144 * 1024 < lds <= 160 * 1024
+
+
+@pytest.mark.parametrize("case", gc.DEVOX_FWD, ids=ids(gc.DEVOX_FWD))
+def test_devox_path_equals_the_library_on_the_case_table(lib, case):
+    p = case.p
+    assert_devox_path_equals_library(lib, p["B"], p["C"], p["N"], p["r"], p["aligned"])
+
+
+@pytest.mark.parametrize("r", sorted(set(range(2, 51, 2)) | {9, 15, 33}))
+def test_devox_path_equals_the_library_across_every_threshold(lib, r):
+    """ring (r = 32), slab (r^2 % 4 == 0, r^2 <= 4608, N <= 2048: one slab up to r = 20, LD 1 / 2 / 4 / 9, CI 16 .. 1, CT by
+    B x C) and gather (odd r, N > 2048, unaligned; ct by B x C x N)"""
+    for B in (1, 2, 8, 32, 64):
+        for C in (1, 8, 17, 64, 128):
+            for N in (1, 7, 1024, 1025, 2048, 2049, 4096, 8192, 8193):
+                for aligned in (True, False):
+                    assert_devox_path_equals_library(lib, B, C, N, r, aligned)
+
+
+def test_devox_path_query_refuses_bad_arguments(lib):
+    out = (ctypes.c_int32 * 8)()
+    for args in ((0, 8, 64, 8, 1), (1, 0, 64, 8, 1), (1, 8, 0, 8, 1), (1, 8, 64, 0, 1)):
+        assert lib.lion_internal_devoxelize_path(*args, out, None) == -1, args
+    assert lib.lion_internal_devoxelize_path(1, 8, 64, 8, 1, None, None) == -1
+
 
 def _paths(group):
     return [(c, gc.devox_path(c.p["B"], c.p["C"], c.p["N"], c.p["r"], c.p["aligned"])) for c in gc.DEVOX_FWD if c.path == group]
@@ -93,6 +145,22 @@ def test_devox_bwd_table_covers_what_it_claims():
     assert gc.devox_bwd_path(6) == {"kernel": "lds", "parts": 1, "nt": 256}
     assert gc.devox_bwd_path(26) == {"kernel": "lds", "parts": 2, "nt": 1024}
     assert {(c.p["r"], c.p["kind"]) for c in gc.DEVOX_BWD} == {(r, k) for r in (5, 34, 6, 26) for k in ("surface", "hub")}
+
+
+def test_devox_bwd_affine_refusals(lib):
+    """lion_trilinear_devoxelize_backward_affine refuses, before any launch, a slab above 128 KiB (r = 34), r3 % 8 != 0
+    (r = 6: 216 is a multiple of 8, r = 5 and the plain entry's r3 = 16388 are not) and a misaligned x or dx; null pointers
+    and empty shapes are LION_EINVAL.  (Host pointers: every call returns before it would touch them.)"""
+    buf = (ctypes.c_float * 64)()
+    base = ctypes.addressof(buf)
+    base += (-base) % 16
+    ok, off = ctypes.c_void_p(base), ctypes.c_void_p(base + 4)
+    f = lib.lion_trilinear_devoxelize_backward_affine
+    call = lambda r3, x=ok, dx=ok, gy=ok: f(gy, ok, ok, x, ok, ok, ok, 1, 2, 64, r3, dx, None)
+    assert call(34 ** 3) == -2 and call(125) == -2 and call(16388) == -2 and call(8 * 4096 + 4) == -2
+    assert call(512, x=off) == -2 and call(512, dx=off) == -2
+    assert call(512, gy=None) == -1 and call(0) == -1 and call(-8) == -1
+    assert lib.lion_trilinear_devoxelize_backward(None, ok, ok, 1, 2, 64, 512, ok, None) == -1
 
 
 @pytest.mark.parametrize("case", gc.DEVOX_BWD, ids=ids(gc.DEVOX_BWD))

@@ -125,6 +125,29 @@ def test_devox_backward_lds_kernel(bk, orc, case):
     run_devox_backward(bk, orc, case)
 
 
+def test_devox_backward_entry_off_the_cubes():
+    """lion_trilinear_devoxelize_backward handed r3 itself.  16388 = 4 * 4097 floats lie above 64 KiB, where a slab is cut
+    into two parts, but are no multiple of 8: the launcher goes back to ONE part (1024 threads, 65552 bytes of LDS) -- no
+    cube reaches that branch.  729 = 9^3 is odd: the atomic fallback.  Indices over the whole range, both ends crowded and
+    some out of range (clamped); same reference and bound as the cases above (geometry_cases.scatter_ref)."""
+    from lion_amd import _lib
+    assert gc.devox_bwd_path(9) == {"kernel": "atomic"} and 16388 * 4 > 64 * 1024 and 16388 % 4 == 0 and 16388 % 8 != 0
+    B, C, N = 1, 2, 64
+    for r3 in (16388, 729):
+        rng = np.random.default_rng(gc.seed_of(f"devox-bwd-r3-{r3}"))
+        inds = rng.integers(0, r3, (B, 8, N)).astype(np.int32)
+        inds[:, :, :6] = r3 - 1
+        inds[:, :, 6:12] = 0
+        inds[:, 0, 12:14] = (-3, r3 + 5)
+        wgts = rng.uniform(0, 1, (B, 8, N)).astype(np.float32)
+        gy = rng.standard_normal((B, C, N), dtype=np.float32)
+        ref, bound = gc.scatter_ref(gy, inds.reshape(B, -1), wgts.reshape(B, -1), r3)
+        gx = torch.full((B, C, r3), float("nan"), device="cuda")
+        _lib.call("lion_trilinear_devoxelize_backward", dev(gy), dev(inds), dev(wgts), B, C, N, r3, gx)
+        err = np.abs(host(gx) - ref)
+        assert np.all(err <= bound), f"r3 = {r3}: {np.count_nonzero(err > bound)} bins outside the bound, worst {err.max():.3g}"
+
+
 # ---- furthest point sampling ------------------------------------------------------------------------------------------
 
 def run_fps(bk, orc, case):

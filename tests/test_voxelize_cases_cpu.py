@@ -1,6 +1,8 @@
 """CPU suite: every case of tests/voxelize_cases.py reaches the plan and has the property it is named for.  The restated
-launchers are checked against the library's pure host calls (lion_voxel_plan_bytes, lion_avg_voxelize_workspace_bytes), the
+launchers are checked against the library's pure host calls (lion_internal_voxelize_plan, lion_voxel_plan_bytes,
+lion_avg_voxelize_workspace_bytes), the
 builders against the CPU oracle."""
+import ctypes
 import re
 
 import numpy as np
@@ -17,6 +19,36 @@ def lib():
 
 def ids(cases):
     return [c.id for c in cases]
+
+
+PLAN_FIELDS = ("S", "CS", "SV", "NP", "n_words", "arena_words", "lds", "grid")
+EUNSUPPORTED = -2
+
+
+def library_plan(lib, B, C, N, r, kind):
+    """lion_internal_voxelize_plan -> (return code, dict of its eight fields)"""
+    out = (ctypes.c_int32 * 8)()
+    rc = lib.lion_internal_voxelize_plan(B, C, N, r, kind, out, None)
+    return rc, dict(zip(PLAN_FIELDS, out))
+
+
+def assert_restatement_equals_library(lib, B, C, N, r):
+    """vox_plan / scatter_plan against lion_internal_voxelize_plan, field for field, for the three kinds.  `lds` and `grid`
+    are not among the scatter restatement's fields: they follow from them (ScatterLds: slot[SV] | ust[n_words] | 64 header
+    words | arena, then PREFETCH_PAD; clouds in groups of 8, S slabs x CS channel ranges each)."""
+    want = vc.vox_plan(B, C, N, r)
+    rc, got = library_plan(lib, B, C, N, r, 0)
+    assert rc == (0 if want["fast"] else EUNSUPPORTED), (B, C, N, r, rc, want["why"])
+    grid = lambda q: vc.cdiv(B, 8) * 8 * q["S"] * q["CS"]
+    assert got == dict({k: want[k] for k in PLAN_FIELDS[:7]}, grid=grid(want)), (B, C, N, r, got, want)
+    for kind, read in ((1, False), (2, True)):
+        want = vc.scatter_plan(B, C, N, r, read=read)
+        rc, got = library_plan(lib, B, C, N, r, kind)
+        assert rc == (0 if want is not None else EUNSUPPORTED), (B, C, N, r, kind, rc)
+        if want is not None:
+            lds = (want["SV"] + want["n_words"] + 64 + want["arena_words"]) * 4 + vc.PREFETCH_PAD
+            assert got == dict(want, lds=lds, grid=grid(want)), (B, C, N, r, kind, got, want)
+            assert lds + (1024 if read else 0) <= vc.LDS_LIMIT // (2 if N <= vc.VT else 1)
 
 
 def oracle_ids(orc, case):
@@ -62,6 +94,30 @@ def test_restated_plan_agrees_with_the_host_calls(lib, case):
     m = re.match(r"S(\d+)-CS(\d+)-NP(\d+)-", case.id)
     if m:
         assert (plan["S"], plan["CS"], plan["NP"]) == tuple(int(g) for g in m.groups())
+    assert_restatement_equals_library(lib, B, C, N, r)
+
+
+SWEEP_R = sorted(set(range(2, 51, 2)) | {9, 15, 33})
+
+
+@pytest.mark.parametrize("r", SWEEP_R)
+def test_restated_plans_equal_the_library_across_every_threshold(lib, r):
+    """every rule of vox_plan has a threshold among these: S and CS (B, C, r), NP and two workgroups per CU (N at 1024,
+    2048, 4096, 8192), the LDS fit (r, N), the scatter's coarsening (N <= 1024, small SV x channels), divisibility (odd r)"""
+    for B in (1, 2, 8, 32, 64):
+        for C in (1, 8, 17, 64, 128):
+            for N in (1, 7, 1024, 1025, 2048, 2049, 4096, 8192, 8193):
+                assert_restatement_equals_library(lib, B, C, N, r)
+
+
+def test_plan_query_refuses_bad_arguments(lib):
+    out = (ctypes.c_int32 * 8)()
+    for args in ((0, 8, 64, 8, 0), (1, -1, 64, 8, 0), (1, 0, 64, 8, 1), (1, 8, 0, 8, 0), (1, 8, 64, 0, 0), (1, 8, 64, 8, 3),
+                 (1, 8, 64, 8, -1)):
+        assert lib.lion_internal_voxelize_plan(*args, out, None) == -1, args
+    assert lib.lion_internal_voxelize_plan(1, 8, 64, 8, 0, None, None) == -1
+    assert lib.lion_internal_voxelize_plan(1, 0, 64, 8, 0, out, None) == 0                # the index kernel: C = 0
+    assert lib.lion_internal_voxelize_plan(1, 8, 64, 1025, 0, out, None) == EUNSUPPORTED  # r^3 > 2^30
 
 
 def test_the_case_tables_plans():
@@ -85,9 +141,9 @@ def test_the_case_tables_plans():
     assert vc.scatter_plan(32, 128, 1024, 16)["CS"] == 2
 
 
-def test_no_fast_shape_is_refused_by_the_scatter_launcher():
-    """voxel_scatter_impl's arena check (arena / 4 < N + 1 + nocc, 1088 bytes less for the reader-aware form) never refuses
-    a shape that make_plan calls fast: its fixed part is smaller than the fused kernel's by SV / 32 + 36 words and more, and
+def test_no_fast_shape_is_refused_by_the_scatter_launcher(lib):
+    """the scatter's arena check of vox_plan (arena / 4 < N + 1 + nocc, 1088 bytes less for the reader-aware form) never
+    refuses a shape that its fused form calls fast: its fixed part is smaller than the fused kernel's by SV / 32 + 36 words and more, and
     a fast shape has room for hist + tmp >= SV + N words, which exceeds N + 1 + nocc + 272"""
     for r in range(2, 52, 2):
         for N in (1, 64, 1000, 1024, 1025, 2048, 3000, 3516, 3517, 4096, 5000, 8192):
@@ -96,6 +152,8 @@ def test_no_fast_shape_is_refused_by_the_scatter_launcher():
                     if vc.vox_plan(B, C, N, r)["fast"]:
                         assert vc.scatter_plan(B, C, N, r) is not None, (B, C, N, r)
                         assert r not in (16, 32) or vc.scatter_plan(B, C, N, r, read=True) is not None, (B, C, N, r)
+                        assert library_plan(lib, B, C, N, r, 1)[0] == 0, (B, C, N, r)
+                        assert r not in (16, 32) or library_plan(lib, B, C, N, r, 2)[0] == 0, (B, C, N, r)
 
 
 ID_BUILT = [c for c in vc.ALL_FORWARD if c.p["kind"] not in ("gauss", "clump")]

@@ -1,12 +1,13 @@
-"""Case tables, cloud builders and references for the voxelisation kernels (csrc/voxelize.hip): every plan of make_plan
-and voxel_scatter_impl, the run-length edges of phase B2's double-buffered ordered sum, the wave-aggregated LDS counters, the
+"""Case tables, cloud builders and references for the voxelisation kernels (csrc/voxelize.hip): every plan of vox_plan
+(fused and scatter), the run-length edges of phase B2's double-buffered ordered sum, the wave-aggregated LDS counters, the
 chunk adoption of the NP >= 2 scatter, the three fallback kernels and the backward.  tests/test_voxelize_paths_gpu.py runs
 the cases on the device; tests/test_voxelize_cases_cpu.py runs every builder against the CPU oracle and asserts that a case
 has the plan and the property it is named for, so that a GPU test cannot pass for the wrong reason.  NumPy only; imports
 nothing from lion_amd.
 
-The launcher arithmetic is restated line for line (each function names its source lines in lion_amd/csrc/voxelize.hip); the
-host calls lion_voxel_plan_bytes / lion_avg_voxelize_workspace_bytes check the restatement in the CPU suite.
+The launcher arithmetic is restated line for line (each function names the function of lion_amd/csrc/voxelize.hip it
+restates); the host calls lion_internal_voxelize_plan / lion_voxel_plan_bytes / lion_avg_voxelize_workspace_bytes check the
+restatement in the CPU suite.
 
 u = 2^-24 is the unit roundoff of fp32."""
 from collections import namedtuple
@@ -19,11 +20,11 @@ U32 = 2.0 ** -24
 
 Case = namedtuple("Case", "id path p")   # p: dict of the case's parameters
 
-VT = 1024                     # voxelize.hip:28
-MAXP = 8                      # voxelize.hip:29
-LDS_LIMIT = 160 * 1024        # voxelize.hip:30
-PREFETCH_PAD = 2 * 16 * 4     # voxelize.hip:31
-CH_CAP = 64                   # voxelize.hip:807 (fused) and :927 (scatter)
+VT = 1024                     # voxelize.hip: VT
+MAXP = 8                      # MAXP
+LDS_LIMIT = 160 * 1024        # LDS_LIMIT
+PREFETCH_PAD = 2 * 16 * 4     # PREFETCH_PAD
+CH_CAP = 64                   # CH_CAP
 OUT_CAP_BYTES = 64 << 20      # the largest output grid of any case
 
 
@@ -45,29 +46,29 @@ def seed_of(text):
 # =============================================================================================================
 
 def vox_plan(B, C, N, r):
-    """make_plan, voxelize.hip:736-777.  `why` names the first reason a shape is not fast (None when it is)."""
+    """vox_plan(kind = VOX_FUSED) of voxelize.hip.  `why` names the first reason a shape is not fast (None when it is)."""
     r3 = r * r * r
-    two_per_cu = N <= VT                                                        # :743
-    wgs = 512 if two_per_cu else 256                                            # :744
-    lds_limit = (LDS_LIMIT // 2 if two_per_cu else LDS_LIMIT) - PREFETCH_PAD    # :747
+    two_per_cu = N <= VT
+    wgs = 512 if two_per_cu else 256
+    lds_limit = (LDS_LIMIT // 2 if two_per_cu else LDS_LIMIT) - PREFETCH_PAD
     S = 1
-    while S < 16 and B * S < wgs and r3 // (S * 2) >= 512 and r3 % (S * 2 * 4) == 0:   # :750
+    while S < 16 and B * S < wgs and r3 // (S * 2) >= 512 and r3 % (S * 2 * 4) == 0:
         S *= 2
     CS = 1
-    while B * S * CS < wgs and C // (CS * 2) >= 8:                              # :754
+    while B * S * CS < wgs and C // (CS * 2) >= 8:
         CS *= 2
-    SV = r3 // S                                                                # :756
-    n_words = align4(N)                                                         # :757
-    NP = 1 if N <= VT else 2 if N <= 2 * VT else 4 if N <= 4 * VT else 8        # :758
-    svp = ((SV + (SV >> 5) + 3) & ~3) + 4                                       # :759
-    fixed = (svp + n_words + 64 + 32) * 4                                       # :760
-    need_a = (svp + n_words) * 4                                                # :763
-    nocc = min(N, SV)                                                           # :764
-    want = max((N + 1 + nocc) * (C if C > 0 else 1) * 4, need_a)                # :765-766
-    avail = lds_limit - fixed if fixed < lds_limit else 0                       # :767
-    arena = min(want, avail)                                                    # :768
-    arena_words = arena // 4                                                    # :769
-    why = None                                                                  # :771-772, in the order written there
+    SV = r3 // S
+    n_words = align4(N)
+    NP = 1 if N <= VT else 2 if N <= 2 * VT else 4 if N <= 4 * VT else 8
+    svp = ((SV + (SV >> 5) + 3) & ~3) + 4
+    fixed = (svp + n_words + 64 + 32) * 4
+    need_a = (svp + n_words) * 4
+    nocc = min(N, SV)
+    want = max((N + 1 + nocc) * (C if C > 0 else 1) * 4, need_a)
+    avail = lds_limit - fixed if fixed < lds_limit else 0
+    arena = min(want, avail)
+    arena_words = arena // 4
+    why = None                                                                  # in the order written there
     if r3 > (1 << 17):
         why = "r3"
     elif r3 % 4 or SV % 4:
@@ -81,7 +82,7 @@ def vox_plan(B, C, N, r):
 
 
 def plan_bytes(B, N, r):
-    """lion_voxel_plan_bytes, voxelize.hip:867-872 with vox_plan_words :198-200"""
+    """lion_voxel_plan_bytes with vox_plan_words"""
     p = vox_plan(B, 0, N, r)
     return B * (2 * N + p["S"] * (4 + 2 * align4(N))) * 4 if p["fast"] else 0
 
@@ -94,68 +95,68 @@ def slabs_of_plan_bytes(nbytes, B, N):
 
 
 def scatter_plan(B, C, N, r, read=False):
-    """voxel_scatter_impl, voxelize.hip:884-919 -> dict(S, CS, SV, NP, n_words, arena_words) or None (LION_EUNSUPPORTED)"""
+    """vox_plan(kind = VOX_SCATTER / VOX_SCATTER_READ) of voxelize.hip as voxel_scatter_impl asks for it -> dict(S, CS, SV, NP, n_words, arena_words) or None (LION_EUNSUPPORTED)"""
     p0 = vox_plan(B, C, N, r)
-    if not p0["fast"]:                                                          # :887-891
+    if not p0["fast"]:
         return None
     S, CS, SV = p0["S"], p0["CS"], p0["SV"]
-    two_per_cu = N <= VT                                                        # :899 (LION_VOXS_TWO is 0)
+    two_per_cu = N <= VT
     if two_per_cu:
         CS = 1
-        while B * S * CS < 512 and C // (CS * 2) >= 8:                          # :902
+        while B * S * CS < 512 and C // (CS * 2) >= 8:
             CS *= 2
-        while CS > 1 and SV * cdiv(C, CS) < 8192 and B * S * (CS // 2) >= 256:  # :907
+        while CS > 1 and SV * cdiv(C, CS) < 8192 and B * S * (CS // 2) >= 256:
             CS //= 2
-    lds_limit = (LDS_LIMIT // 2 if two_per_cu else LDS_LIMIT) - PREFETCH_PAD - (1024 + 64 if read else 0)   # :911
-    fixed = (SV + p0["n_words"] + 64) * 4                                       # :912
-    nocc = min(N, SV)                                                           # :913
-    want = (N + 1 + nocc) * C * 4                                               # :914
-    avail = lds_limit - fixed if fixed < lds_limit else 0                       # :915
-    arena = min(want, avail)                                                    # :916
-    if arena // 4 < N + 1 + nocc:                                               # :917
+    lds_limit = (LDS_LIMIT // 2 if two_per_cu else LDS_LIMIT) - PREFETCH_PAD - (1024 + 64 if read else 0)
+    fixed = (SV + p0["n_words"] + 64) * 4
+    nocc = min(N, SV)
+    want = (N + 1 + nocc) * C * 4
+    avail = lds_limit - fixed if fixed < lds_limit else 0
+    arena = min(want, avail)
+    if arena // 4 < N + 1 + nocc:
         return None
     return dict(S=S, CS=CS, SV=SV, NP=p0["NP"], n_words=p0["n_words"], arena_words=arena // 4)
 
 
 def ch_max_of(arena_words, pts, occ, C):
-    """channels per chunk of a slab, voxelize.hip:81-82 (and :532)"""
+    """channels per chunk of a slab: ch_max of vox_means_and_store (and l_chm of vox_scatter_kernel)"""
     return min(CH_CAP, min(C, arena_words // ((pts | 1) + occ)) if pts > 0 else C)
 
 
 def chunking(plan, pts, occ, C, cs=0):
-    """The header block (voxelize.hip:525-535) and the greedy loop (:552-577) of vox_scatter_kernel for channel range `cs` of
+    """The header block and the greedy adoption loop of vox_scatter_kernel for channel range `cs` of
     one cloud.  pts / occ: per slab.  -> (chm [S], nc [S], moves [(adopter, slab, chunk)], rem [S]: chunks left with the owner)"""
     S, CS = plan["S"], plan["CS"]
-    c_per = cdiv(C, CS)                                                         # :474
+    c_per = cdiv(C, CS)
     cg_lo = cs * c_per
     cg_hi = min(C, cg_lo + c_per)
-    chm = [ch_max_of(plan["arena_words"], pts[s], occ[s], C) for s in range(S)]                      # :532
-    nc = [cdiv(cg_hi - cg_lo, chm[s]) if pts[s] > 0 else 1 for s in range(S)]                        # :533
+    chm = [ch_max_of(plan["arena_words"], pts[s], occ[s], C) for s in range(S)]
+    nc = [cdiv(cg_hi - cg_lo, chm[s]) if pts[s] > 0 else 1 for s in range(S)]
     lanes = 16                                                                  # the xor butterfly spans lanes 0..15
-    rem = [nc[s] if s < S else 0 for s in range(lanes)]                         # :552 (l_nc = 0 in the lanes past S)
+    rem = [nc[s] if s < S else 0 for s in range(lanes)]                         # (l_nc = 0 in the lanes past S)
     ld2 = [1 if s < S and pts[s] == 0 else 0x7fffff for s in range(lanes)]
     taken = [0] * lanes
     moves = []
-    if plan["NP"] >= 2 and any(pts[s] == 0 for s in range(S)):                  # :558
-        for _ in range(5 * 16):                                                 # :559
-            km = max((rem[s] << 8) | (63 - s) for s in range(lanes))            # :560-567
+    if plan["NP"] >= 2 and any(pts[s] == 0 for s in range(S)):
+        for _ in range(5 * 16):
+            km = max((rem[s] << 8) | (63 - s) for s in range(lanes))
             ka = min((ld2[s] << 8) | s for s in range(lanes))
-            smax, nmax, a_, la = 63 - (km & 0xff), km >> 8, ka & 0xff, ka >> 8  # :568
-            if nmax < 2 or nmax > 256 or la + 2 >= 2 * nmax:                    # :569
+            smax, nmax, a_, la = 63 - (km & 0xff), km >> 8, ka & 0xff, ka >> 8
+            if nmax < 2 or nmax > 256 or la + 2 >= 2 * nmax:
                 break
-            rem[smax] -= 1                                                      # :570
-            ld2[a_] += 2                                                        # :572
+            rem[smax] -= 1
+            ld2[a_] += 2
             taken[a_] += 1
-            if taken[a_] == 5:                                                  # :573
+            if taken[a_] == 5:
                 ld2[a_] = 0x7fffff
-            moves.append((a_, smax, nmax - 1))                                  # :575
+            moves.append((a_, smax, nmax - 1))
     return chm, nc, moves, rem[:S]
 
 
 def slab_headers(vox_ids, plan):
-    """per slab (points, occupied voxels) of one cloud from its voxel ids [N] (hdr of the index plan, voxelize.hip:414-417)"""
+    """per slab (points, occupied voxels) of one cloud from its voxel ids [N] (hdr of the index plan, written by vox_fused_kernel)"""
     r3 = plan["S"] * plan["SV"]
-    v = np.clip(np.asarray(vox_ids, np.int64), 0, r3 - 1)                       # :337
+    v = np.clip(np.asarray(vox_ids, np.int64), 0, r3 - 1)
     pts, occ = [], []
     for s in range(plan["S"]):
         m = v[(v >= s * plan["SV"]) & (v < (s + 1) * plan["SV"])]
@@ -165,7 +166,7 @@ def slab_headers(vox_ids, plan):
 
 
 def vox_ids(vox, r):
-    """voxel ids [B, N] from integer coordinates [B, 3, N] (voxelize.hip:327)"""
+    """voxel ids [B, N] from integer coordinates [B, 3, N] (vox_fused_kernel without P1)"""
     v = vox.astype(np.int64)
     return v[:, 0] * r * r + v[:, 1] * r + v[:, 2]
 
@@ -291,7 +292,7 @@ ADOPT = _adoption_cases()
 # =============================================================================================================
 
 def pw_of(NP):
-    return 16 if NP in (2, 4) else 8                                            # voxelize.hip:132
+    return 16 if NP in (2, 4) else 8                                            # PW of vox_means_and_store
 
 
 def run_edges(NP):
@@ -399,7 +400,7 @@ GRAD = [Case(f"grad-r{r}-b{B}", "grad", dict(r=r, B=B)) for r in (4, 16) for B i
 
 
 def grad_ref(gy, ind, cnt):
-    """vox_grad_kernel's two expressions (voxelize.hip:717-723) in NumPy float32: a clamped index, 0 where the count is 0"""
+    """vox_grad_kernel's two expressions (voxelize.hip) in NumPy float32: a clamped index, 0 where the count is 0"""
     B, C, r3 = gy.shape
     gx = np.zeros((B, C, ind.shape[1]), np.float32)
     for b in range(B):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Is the device code of two trees the same?  tools/isa_identical.py TREE_A TREE_B [file.hip ...]
+"""Is the device code of two trees the same?  tools/isa_identical.py [--rename OLD=NEW[<ARGS>] ...] TREE_A TREE_B [file.hip ...]
 
 Compiles every lion_amd/csrc/*.hip of both trees (or the named ones) with the FLAGS of csrc/build.sh without -fPIC, plus
 -S --cuda-device-only, and compares the listings -- what a host-only refactor has to show.  A file whose two listings are
@@ -8,7 +8,11 @@ a symbol) every device function is compared on its own, by the method of profile
   the lines from the function's label up to its .Lfunc_end, ';' comments stripped, .LBB<n>_<m> labels -> one token,
   mangled _Z... symbols -> one token, compared as lists; and NumVgprs, ScratchSize, Occupancy and
   .amdhsa_group_segment_fixed_size (static LDS; the dynamic part is a launch argument) compared as numbers.
-Functions are paired by their demangled names.  One line per function, then ALL IDENTICAL or the number that differ
+Functions are paired by their demangled names.  --rename OLD=NEW (repeatable; kernel names without template arguments)
+pairs TREE_A's OLD<args> with TREE_B's NEW<args>, --rename OLD=NEW<ARGS> with NEW<ARGS> whatever OLD's arguments and
+parameter list were -- a kernel folded into a template:
+  --rename 'devox_bwd_lds_kernel=devox_bwd_lds_kernel<false>' --rename 'devox_bwd_affine_kernel=devox_bwd_lds_kernel<true>'
+One line per function, then ALL IDENTICAL or the number that differ
 (exit status 1).  Needs no GPU.
 """
 import concurrent.futures
@@ -91,11 +95,36 @@ def short(name):
     return head.group(1), head.group(2) or "<>"
 
 
+def renamed(by_a, by_b, renames):
+    """by_a re-keyed: a function of A that a rename names goes under the demangled name of its partner in B (if B has it)"""
+    out = {}
+    for d, k in by_a.items():
+        kn, targs = short(d)
+        if kn in renames:
+            new, want = renames[kn]
+            hits = [e for e in by_b if short(e) == (new, (want or targs).replace(" ", "")) or short(e) == (new, want or targs)]
+            if len(hits) == 1:
+                d = hits[0]
+        out[d] = k
+    return out
+
+
 def main():
-    if len(sys.argv) < 3:
+    argv, renames = [], {}
+    it = iter(sys.argv[1:])
+    for x in it:
+        if x == "--rename" or x.startswith("--rename="):
+            old, _, new = (next(it, "") if x == "--rename" else x[len("--rename="):]).partition("=")
+            m = re.match(r"^([\w:]+)(<.*>)?$", new)
+            if not old or not m:
+                raise SystemExit("--rename OLD=NEW[<ARGS>]")
+            renames[old] = (m.group(1), m.group(2))
+        else:
+            argv.append(x)
+    if len(argv) < 2:
         raise SystemExit(__doc__)
-    a, b = sys.argv[1], sys.argv[2]
-    names = sys.argv[3:] or sorted(set(f for t in (a, b) for f in os.listdir(os.path.join(t, "lion_amd/csrc"))
+    a, b = argv[0], argv[1]
+    names = argv[2:] or sorted(set(f for t in (a, b) for f in os.listdir(os.path.join(t, "lion_amd/csrc"))
                                        if f.endswith(".hip")))
     ver = subprocess.run([HIPCC, "--version"], stdout=subprocess.PIPE, text=True).stdout.split("\n")
     print("compiler %s\n         %s" % (ver[1].strip(), ver[0].strip()))
@@ -118,6 +147,7 @@ def main():
             da, db = demangle(list(fa)), demangle(list(fb))
             by_a = {da[k]: k for k in fa}
             by_b = {db[k]: k for k in fb}
+            by_a = renamed(by_a, by_b, renames)
             if not whole and not (set(by_a) & set(by_b)):  # nothing to compare: the listing's format is not understood
                 print("%-20s listings differ and no device function was found in both  identical NO" % n)
                 bad += 1
