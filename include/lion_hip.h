@@ -388,6 +388,33 @@ int lion_chain_update_noise_cm_keyed_from(int mode, const float *x, const float 
                                           float *z_out, lionStream_t stream);
 int lion_chain_diffuse_keyed_at(const float *x0, int B, int n, const float *ms /* device f32[B][2] */, const uint32_t *keys,
                                 uint32_t stream_id, float *out, float *z_out, lionStream_t stream);
+/* Known region: the per-sample-start update with part of the state given -- RePaint's known-region
+ * conditioning (Lugmayr et al. 2022, Algorithm 1 without its resampling jumps), one byte per quad, in the kernel that ends the
+ * keyed step.  Same grid as the forms above.
+ *   known_x0         f32 laid out like x: the clean values
+ *   keep             device u8[B][n/4] (cm: [B][N]), one byte per quad (cm: per point); non-zero = kept
+ *   known_ms         device f32[rows][2], read at row i = cur[7] as (m, s): the forward process's scalars of the noise level the
+ *                    state has AFTER row i; the last row of a chain holds (1, 0)
+ *   first_row        as in the "_from" forms, or NULL: every sample starts at row 0
+ * For the quad at position j of sample b, with local = i - first_row[b]:
+ *   local < 0        the whole sample is held exactly as the "_from" forms hold it, kept quads included
+ *   keep == 0        exactly the arithmetic, the draw (step word local, stream_id) and the z_out of the "_from" forms
+ *   kept, s != 0     out = (m*x0) + (s*z'), two products and a sum, each rounded once (lion_chain_diffuse's arithmetic); z' is
+ *                    the chain generator's draw under keys[b] at counter (j, local, known_stream_id); z_out receives z'; eps and
+ *                    x are not read for this quad
+ *   kept, s == 0     out = x0 bit for bit, nothing is drawn, z_out = 0
+ * out may alias x; modes 0 and 1 as in the sibling entry points.
+ * LION_EINVAL before any launch: the rules of the keyed forms above (known_x0 counts among the 16-byte aligned pointers), a
+ * NULL known_x0, keep or known_ms, or known_stream_id == stream_id. */
+int lion_chain_update_noise_keyed_known(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                        const int32_t *first_row /* device i32[B], or NULL */, const uint32_t *keys,
+                                        uint32_t stream_id, const float *known_x0, const uint8_t *keep /* device u8[B][n/4] */,
+                                        const float *known_ms /* device f32[rows][2] */, uint32_t known_stream_id, float *out,
+                                        float *z_out, lionStream_t stream);
+int lion_chain_update_noise_cm_keyed_known(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
+                                           const int32_t *first_row, const uint32_t *keys, uint32_t stream_id,
+                                           const float *known_x0, const uint8_t *keep, const float *known_ms,
+                                           uint32_t known_stream_id, float *out, float *z_out, lionStream_t stream);
 /* Inputs of guided synthesis (csrc/perturb.hip): perturbed copies of clouds x f32[B][N][3], every cloud on its
  * own and under its own key (keys as above).  One Philox4x32-10 call per output point at counter = (point index WITHIN the
  * sample, a reserved step word, stream_id), words w0..w3; a fraction is u(w) = (w >> 8) * 2^-24, exact.  LION_VOXEL_STEP_WORD

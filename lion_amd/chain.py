@@ -51,6 +51,12 @@ KEYED_MODES = (DDIM, DDPM, SDE_DPMPP)
 # "_from" entry point of the same name instead, which takes the chain's `first_row` (int32[B]) before the keys: sample b is held
 # at the rows below first_row[b] and counts its own rows from there.  The same launch count as the keyed step.
 FROM_ROWS_MODES = (DDPM,)
+# Known region (GraphedChain(keyed=True, from_rows=True, known=True)): the per-sample-start step ends with the
+# "_known" entry point instead, which takes the chain's `known_x0` (the clean latent), `keep` (uint8, a byte per quad) and
+# `known_ms` (float32[capacity, 2], the forward process's scalars of the level the state has after each row) and this stream id
+# behind the step's own: a kept quad is re-drawn from its clean value after every row, on a Philox stream of its own -- chain
+# steps draw on stream 0, the forward draw (diffusion_ops.diffuse) on stream 1.  The same launch count as the keyed step.
+KNOWN_STREAM = 2
 # the step words no chain step can have (a step's word is its row index < the table's capacity): include/lion_hip.h
 START_STEP_WORD, DIFFUSE_STEP_WORD = 0xFFFFFFFE, 0xFFFFFFFF
 _MASK64 = 0xFFFFFFFFFFFFFFFF
@@ -276,19 +282,25 @@ class CapturedStep:
 
 class GraphedChain:
     def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
-                 record_noise=False, keyed=False, from_rows=False):
+                 record_noise=False, keyed=False, from_rows=False, known=False):
         """keyed: sample b draws its noise under its own key, seed[b], at counters that count within the sample (the "_keyed"
         update kernels) -- `seed` is then int32[num_samples, 2] and prepare() / run() take num_samples keys.
         from_rows (keyed DDPM chains only, else ValueError): the chain owns `first_row`, int32[num_samples], which prepare()
         uploads with the table; sample b is held at the rows below first_row[b] and then runs as a chain of its own that starts
-        there (the "_from" update kernel)."""
+        there (the "_from" update kernel).
+        known (keyed from_rows chains only, else ValueError): the chain also owns `known_x0`, `keep` and `known_ms`, which
+        prepare() fills; the quads marked in `keep` are replaced after every row by a forward draw of known_x0 at that row's
+        level, after the last row by known_x0 itself (the "_known" update kernel)."""
         self.model, self.mode, self.capacity, self.keyed = model, mode, int(capacity), bool(keyed)
-        self.from_rows = bool(from_rows)
+        self.from_rows, self.known = bool(from_rows), bool(known)
         dev = torch.device(device)
         size = [num_samples] + list(shape)
         per_sample = int(np.prod(shape))
         if self.from_rows and not (keyed and mode in FROM_ROWS_MODES):
             raise ValueError(f"GraphedChain: from_rows needs a keyed DDPM chain, got mode {mode}, keyed={bool(keyed)}")
+        if self.known and not (keyed and self.from_rows):
+            raise ValueError(f"GraphedChain: known needs keyed=True and from_rows=True, got keyed={bool(keyed)}, "
+                             f"from_rows={self.from_rows}")
         if keyed and mode not in KEYED_MODES:
             raise ValueError(f"GraphedChain: mode {mode} draws nothing and has no keyed form")
         if keyed and per_sample % 4 != 0:
@@ -303,6 +315,10 @@ class GraphedChain:
         self.seed = torch.zeros((num_samples, 2) if keyed else 2, dtype=torch.int32, device=dev)
         self.cur = torch.zeros(8, device=dev)
         self.first_row = torch.zeros(num_samples, dtype=torch.int32, device=dev) if self.from_rows else None   # 0: never held
+        # known region: nobody kept and level (1, 0) until prepare() fills them -- the warm-up runs the plain "_from" update
+        self.known_x0 = torch.zeros(size, device=dev) if self.known else None
+        self.keep = torch.zeros(num_samples, per_sample // 4, dtype=torch.uint8, device=dev) if self.known else None
+        self.known_ms = torch.tensor([1.0, 0.0], device=dev).repeat(self.capacity, 1) if self.known else None
         self.z = torch.zeros(size, device=dev) if record_noise and mode != ENCODE else None   # tests: the noise each step used
         self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
         self.base = torch.zeros(size, device=dev) if mode == ENCODE else None   # ENCODE: the state at the leg's low end
@@ -348,11 +364,14 @@ class GraphedChain:
                     given["size"] = [num_samples, per_sample]
             if self.from_rows:
                 given["keys"] = [self.first_row, self.seed]
+            if self.known:   # behind the step's stream id: the known region's buffers and its stream
+                k = spec.index("keys") + 2
+                spec = spec[:k] + ("known_x0", "keep", "known_ms", KNOWN_STREAM) + spec[k:]
             args = []
             for a in spec:
                 args += given[a] if a in given else [getattr(self, a) if isinstance(a, str) else a]
             _lib.call(entry + ("_cm" if self.cm_out else "") + ("_keyed" if self.keyed else "")
-                      + ("_from" if self.from_rows else ""), *args)
+                      + ("_known" if self.known else "_from" if self.from_rows else ""), *args)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
 
     def matches(self, condition_input, clip_feat):
@@ -360,7 +379,8 @@ class GraphedChain:
 
     @torch.no_grad()
     def run(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None, trajectory=None,
-            trajectory_before_last=False, noise_trajectory=None, state_hook=None, trajectory_rows=None, first_row=None):
+            trajectory_before_last=False, noise_trajectory=None, state_hook=None, trajectory_rows=None, first_row=None,
+            known=None):
         """x_init: the chain's start; table [S, 8] float32 rows {t_model, a0..a5, a6} (a6: SDE_DPMPP's noise scale, 0 in
         every other mode); seed: the chain's 64-bit key -- of a keyed chain, a sequence or tensor of one key per sample.  Returns the final latent (a fresh tensor).  `trajectory`: list that receives a copy of x after
         every step (before the last step's update if `trajectory_before_last`, as run_denoising_diffusion reports it); with
@@ -370,8 +390,11 @@ class GraphedChain:
         with launches on the current stream (no host synchronisation): inpainting / known-region replacement, or a
         benchmark forcing the states a trained model would visit (bench.py's forced clouds).
         `first_row` (a from_rows chain, where it is required): num_samples ints, the first table row each sample takes part in
-        (S or more: held throughout)."""
-        S = self.prepare(x_init, table, seed, condition_input, clip_feat, first_row)
+        (S or more: held throughout).
+        `known` (a known chain, where it is required): (x0, keep, ms) -- the clean latent, shaped like x_init; the mask, a
+        device tensor [num_samples, elements per sample / 4], non-zero = kept; ms [S, 2] float32 on the host, row i the forward
+        process's (m, s) of the level the state has after row i."""
+        S = self.prepare(x_init, table, seed, condition_input, clip_feat, first_row, known)
         if RECORD is not None and self.z is not None and noise_trajectory is None:
             noise_trajectory = []
             RECORD.append((x_init.detach().clone(), noise_trajectory))
@@ -389,10 +412,11 @@ class GraphedChain:
         return self.x.clone()
 
     @torch.no_grad()
-    def prepare(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None, first_row=None) -> int:
+    def prepare(self, x_init, table: np.ndarray, seed, condition_input=None, clip_feat=None, first_row=None, known=None) -> int:
         """everything a chain needs in device memory before its first replay (on the current stream): the start latent, the
         conditioning, the schedule table, the time-embedding rows, the step counter and the Philox key (keyed: the keys, a
-        sequence or tensor of one per sample; from_rows: `first_row`, one non-negative int per sample).  Returns S."""
+        sequence or tensor of one per sample; from_rows: `first_row`, one non-negative int per sample; known: the clean latent, the
+        quad mask and the level table, as run() describes them).  Returns S."""
         S = int(table.shape[0])
         assert 1 <= S <= self.capacity and table.shape[1] == 8
         if self.from_rows != (first_row is not None):
@@ -400,6 +424,17 @@ class GraphedChain:
         if self.from_rows:
             rows = first_rows(first_row, self.x.shape[0])
             self.first_row.copy_(torch.tensor(rows, dtype=torch.int32))
+        if self.known != (known is not None):
+            raise ValueError("GraphedChain: known goes with a known chain, and only with it")
+        if self.known:
+            x0, keep, ms = known
+            ms = np.ascontiguousarray(ms, dtype=np.float32)
+            if tuple(x0.shape) != tuple(self.x.shape) or tuple(keep.shape) != tuple(self.keep.shape) or ms.shape != (S, 2):
+                raise ValueError(f"GraphedChain: known = (x0 {tuple(x0.shape)}, keep {tuple(keep.shape)}, ms {ms.shape}) for "
+                                 f"{tuple(self.x.shape)}, {tuple(self.keep.shape)}, {(S, 2)}")
+            self.known_x0.copy_(x0)
+            self.keep.copy_(keep)
+            self.known_ms[:S].copy_(torch.from_numpy(ms))
         self.x.copy_(x_init)
         if self.cond is not None:
             self.cond.copy_(condition_input)
@@ -429,21 +464,22 @@ for _name in ("replay", "graph", "graphs", "graph_b", "geo_graphs", "pinned", "p
 
 
 class ChainCache(LRU):
-    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed, from_rows) -> GraphedChain.  A keyed
+    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed, from_rows, known) -> GraphedChain.  A keyed
     and an unkeyed capture of one (model, mode, shape) coexist, each in a slot of its own; the modes that draw nothing have the
     unkeyed capture only and serve a keyed call with it.  The per-sample-start capture (from_rows: keyed DDPM only, ValueError
-    otherwise) is a third entry beside them and takes one of the four slots."""
+    otherwise) is a third entry beside them and takes one of the four slots, and the known-region capture (known: keyed
+    from_rows only, ValueError otherwise) a fourth."""
 
     def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity, keyed=False,
-            from_rows=False):
+            from_rows=False, known=False):
         rec = RECORD is not None
-        from_rows = bool(from_rows)
+        from_rows, known = bool(from_rows), bool(known)
         keyed = bool(keyed) and (mode in KEYED_MODES or from_rows)   # from_rows on a mode without a keyed form: refused below
         return self.lookup(
-            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed, from_rows),
+            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed, from_rows, known),
             lambda hit: hit.model is model and hit.capacity >= table_capacity and hit.matches(condition_input, clip_feat),
             lambda: GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity,
-                                 record_noise=rec, keyed=keyed, from_rows=from_rows))
+                                 record_noise=rec, keyed=keyed, from_rows=from_rows, known=known))
 
 
 def draw_seed() -> int:

@@ -153,6 +153,22 @@ __global__ void begin_step_kernel(const float *__restrict__ table, int n_steps, 
 
 // MODE 0: DDIM  out = x*a0 + (a1*eps + a2*z)                     (a = {s, c, sigma})
 // MODE 1: DDPM  a5 != 0 (t == 0): out = a0*(x - a1*eps);  else out = a0*(x - a1*eps/a2) + (a3*z)*a4
+// one quad of it with a0..a5 = cur[1..6]: the arithmetic of every update_noise kernel
+template <int MODE>
+__device__ __forceinline__ void update_quad(const float xv[4], const float ev[4], const float z[4], float a0, float a1, float a2,
+                                            float a3, float a4, float a5, float o[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (MODE == 0) {
+      o[j] = ddim1(xv[j], ev[j], z[j], a0, a1, a2);
+    } else if (a5 != 0.f) {
+      o[j] = mul_rn(a0, sub_rn(xv[j], mul_rn(a1, ev[j])));
+    } else {
+      o[j] = add_rn(mul_rn(a0, sub_rn(xv[j], div_rn(mul_rn(a1, ev[j]), a2))), mul_rn(mul_rn(a3, z[j]), a4));
+    }
+  }
+}
+
 // `step` is the counter's step word: cur[7], the row's index, but in the per-sample-start form below.
 template <int MODE, bool KEYED>
 __device__ __forceinline__ void update_noise_body(const float *__restrict__ x, const float *__restrict__ eps, size_t numel,
@@ -172,16 +188,7 @@ __device__ __forceinline__ void update_noise_body(const float *__restrict__ x, c
   const bool full = i + 3 < numel;
   load_quad(x, i, numel, full, xv);
   load_eps_quad<KEYED>(eps, q, ctr, numel, full, cm_points, ev);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (MODE == 0) {
-      o[j] = ddim1(xv[j], ev[j], z[j], a0, a1, a2);
-    } else if (a5 != 0.f) {
-      o[j] = mul_rn(a0, sub_rn(xv[j], mul_rn(a1, ev[j])));
-    } else {
-      o[j] = add_rn(mul_rn(a0, sub_rn(xv[j], div_rn(mul_rn(a1, ev[j]), a2))), mul_rn(mul_rn(a3, z[j]), a4));
-    }
-  }
+  update_quad<MODE>(xv, ev, z, a0, a1, a2, a3, a4, a5, o);
   store_quad(out, i, numel, full, o);
   if (z_out) store_quad(z_out, i, numel, full, z);
 }
@@ -236,6 +243,52 @@ __global__ void update_noise_keyed_from_kernel(const float *x, const float *__re
     return;
   }
   update_noise_body<MODE, true>(x, eps, numel, sample_quads, cur, keys, (uint32_t)local, stream_id, out, z_out, cm_points);
+}
+
+// the per-sample-start form with a known region (RePaint's conditioning, Lugmayr et al. 2022, Algorithm 1 without its jumps):
+// keep u8[B][sample_quads] marks the quads whose clean value known_x0 is given.  A sample below its first row is held as above,
+// kept quads included.  Else a quad that is not kept takes the "_from" update (step word local, stream_id), and a kept one the
+// forward draw of its clean value at the level the state has after this row, (m, s) = known_ms[row]: out = m*x0 + s*z' with
+// diffuse_body's arithmetic, z' at counter (j, local, known_stream_id) -- or, where s == 0 (the last row), out = x0 bit for
+// bit, nothing drawn, z_out = 0.  A kept quad reads neither x nor eps.  first_row NULL: every sample starts at row 0.
+// The mask is per lane: a wave with both kinds runs the one draw below once and then each kind's loads and arithmetic.
+template <int MODE>
+__global__ void update_noise_keyed_known_kernel(const float *x, const float *__restrict__ eps, size_t numel,
+                                                uint32_t sample_quads, const float *__restrict__ cur,
+                                                const int32_t *__restrict__ first_row, const uint32_t *__restrict__ keys,
+                                                uint32_t stream_id, const float *__restrict__ known_x0,
+                                                const uint8_t *__restrict__ keep, const float *__restrict__ known_ms,
+                                                uint32_t known_stream_id, float *out, float *z_out, int cm_points) {
+  const int32_t row = __float_as_int(cur[7]);
+  const int32_t local = first_row ? row - first_row[blockIdx.y] : row;
+  if (local < 0) {
+    hold_quad(x, numel, sample_quads, true, out, z_out);
+    return;
+  }
+  size_t q;
+  uint64_t ctr;
+  const uint32_t *key;
+  if (!own_quad<true>(numel, sample_quads, keys, q, ctr, key)) return;
+  const size_t i = q * 4;
+  const bool kept = keep[q] != 0;
+  const float m = known_ms[2 * (size_t)row], s = known_ms[2 * (size_t)row + 1];
+  float z[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+  if (!kept || s != 0.f)
+    normal4(ctr, (uint32_t)local, kept ? known_stream_id : stream_id, (uint64_t)key[0] | ((uint64_t)key[1] << 32), z);
+  if (kept) {
+    load_quad(known_x0, i, numel, true, o);
+    if (s != 0.f) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(m, o[j]), mul_rn(s, z[j]));
+    }
+  } else {
+    float xv[4], ev[4];
+    load_quad(x, i, numel, true, xv);
+    load_eps_quad<true>(eps, q, ctr, numel, true, cm_points, ev);
+    update_quad<MODE>(xv, ev, z, cur[1], cur[2], cur[3], cur[4], cur[5], cur[6], o);
+  }
+  store_quad(out, i, numel, true, o);
+  if (z_out) store_quad(z_out, i, numel, true, z);
 }
 
 // out[b][.] = z alone: sample b's draw at counter (j, step, stream_id) under keys[b] -- the start latent of a keyed chain
@@ -294,6 +347,23 @@ static int update_noise_keyed_launch(int mode, hipStream_t st, const float *x, c
                                                                z_out, cm_points)
                    : lion_launch<update_noise_keyed_kernel<1>>(grid, 256, 0, st, x, eps, numel, sq, cur, keys, stream_id, out,
                                                                z_out, cm_points);
+}
+
+// the known-region form on the same grid; first_row may be NULL here
+static int update_noise_known_launch(int mode, hipStream_t st, const float *x, const float *eps, int B, int n, const float *cur,
+                                     const int32_t *first_row, const uint32_t *keys, uint32_t stream_id, const float *known_x0,
+                                     const uint8_t *keep, const float *known_ms, uint32_t known_stream_id, float *out,
+                                     float *z_out, int cm_points) {
+  dim3 grid;
+  uint32_t sq;
+  if (keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
+  const size_t numel = (size_t)B * n;
+  return mode == 0 ? lion_launch<update_noise_keyed_known_kernel<0>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,
+                                                                     stream_id, known_x0, keep, known_ms, known_stream_id, out,
+                                                                     z_out, cm_points)
+                   : lion_launch<update_noise_keyed_known_kernel<1>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,
+                                                                     stream_id, known_x0, keep, known_ms, known_stream_id, out,
+                                                                     z_out, cm_points);
 }
 
 static int update_noise_launch(int mode, hipStream_t st, const float *x, const float *eps, size_t numel,
@@ -699,6 +769,29 @@ int lion_chain_update_noise_cm_keyed_from(int mode, const float *x, const float 
   if (!aligned16({x, out, z_out})) return LION_EINVAL;
   return update_noise_keyed_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, first_row, keys, stream_id,
                                    out, z_out, N);
+}
+
+// ---- known region: a clean value and a mask byte per quad, beside the per-sample first rows -----------------------------------
+int lion_chain_update_noise_keyed_known(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                        const int32_t *first_row, const uint32_t *keys, uint32_t stream_id,
+                                        const float *known_x0, const uint8_t *keep, const float *known_ms,
+                                        uint32_t known_stream_id, float *out, float *z_out, lionStream_t stream) {
+  if (!x || !eps || !cur || !keys || !out || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!known_x0 || !keep || !known_ms || known_stream_id == stream_id) return LION_EINVAL;
+  if (!aligned16({x, eps, known_x0, out, z_out})) return LION_EINVAL;
+  return update_noise_known_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, first_row, keys, stream_id,
+                                   known_x0, keep, known_ms, known_stream_id, out, z_out, 0);
+}
+
+int lion_chain_update_noise_cm_keyed_known(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
+                                           const int32_t *first_row, const uint32_t *keys, uint32_t stream_id,
+                                           const float *known_x0, const uint8_t *keep, const float *known_ms,
+                                           uint32_t known_stream_id, float *out, float *z_out, lionStream_t stream) {
+  if (!x || !eps_cm || !cur || !keys || !out || N <= 0 || N > 0x1fffffff || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!known_x0 || !keep || !known_ms || known_stream_id == stream_id) return LION_EINVAL;
+  if (!aligned16({x, known_x0, out, z_out})) return LION_EINVAL;
+  return update_noise_known_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, first_row, keys, stream_id,
+                                   known_x0, keep, known_ms, known_stream_id, out, z_out, N);
 }
 
 int lion_chain_update_multistep_noise_keyed(const float *x, const float *eps, const float *hist, int B, int n, const float *cur,

@@ -214,6 +214,23 @@ class DiffusionDiscretized(object):
             table[i] = (t + 1, k_outer, k_a, k_b, scale, temp, 1.0 if is0 else 0.0, 0.0)
         return table
 
+    def known_levels(self, t_from):
+        """[t_from, 2] float32: beside row i of ddpm_table(t_from) -- the step at t = t_from-1-i, which leaves the state at the
+        noise level of index t-1 -- the two scalars (m, s) with which diffuse(x0, t-1) draws that level from a clean x0, from
+        the same expressions on the float32 host schedule; the row of t = 0 holds (1, 0): the clean value itself.  What the
+        known-region chain reads its forward draws' scalars from (chain.GraphedChain(known=True)).  Host arithmetic only."""
+        t_from = int(t_from)
+        if not 1 <= t_from <= self._diffusion_steps:
+            raise ValueError(f"known_levels: t_from = {t_from} outside [1, {self._diffusion_steps}]")
+        ms = np.zeros((t_from, 2), np.float32)
+        for i, t in enumerate(reversed(range(t_from))):
+            if t == 0:
+                ms[i] = (1.0, 0.0)
+            else:
+                ab = self._h_alpha_bars[t - 1]
+                ms[i] = (float(torch.sqrt(ab)), float(torch.sqrt(1.0 - ab)))
+        return ms
+
     # ---- DPM-Solver++(2M): schedule and coefficients (float64 on the widened float32 schedule, cast once) ----------------
     def _half_logsnr(self):
         """lambda[i] = log(alpha_i / sigma_i) = 0.5*(log(ab_i) - log1p(-ab_i)) in float64, with ab widened from float32"""
@@ -360,16 +377,19 @@ class DiffusionDiscretized(object):
             return _mixed(model, pred, mixing).float().contiguous()
 
     def _replay(self, model, num_samples, shape, mode, x, table, seed, condition_input, clip_feat, capacity=None, keys=None,
-                first_row=None, **run):
+                first_row=None, known=None, **run):
         """the graphed branch of every sampler: the captured chain of (model, mode, batch shape) from this object's cache, run
         from x over `table`; seed None: one is drawn with chain.draw_seed() once the chain is there; `run`: GraphedChain.run's
         keywords.  keys (a list of num_samples 64-bit keys) in place of seed: the keyed capture of a mode that draws.
         first_row (num_samples ints, with keys; DDPM only): the per-sample-start capture, a cache entry of its own.
+        known (GraphedChain.run's triple, with first_row): the known-region capture, another entry of its own.
         Returns the final latent."""
         keyed = keys is not None and mode in _chain.KEYED_MODES
         ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, self.device, mode,
                               self._diffusion_steps if capacity is None else capacity, keyed=keyed,
-                              from_rows=first_row is not None)
+                              from_rows=first_row is not None, known=known is not None)
+        if known is not None:
+            return ch.run(x, table, keys, condition_input, clip_feat, first_row=first_row, known=known, **run)
         if first_row is not None:
             return ch.run(x, table, keys, condition_input, clip_feat, first_row=first_row, **run)
         if keyed:
@@ -544,7 +564,8 @@ class DiffusionDiscretized(object):
     @torch.no_grad()
     def run_denoising_diffusion_from_t(self, model, num_samples, shape, time_start, x_noisy, temp=1.0, enable_autocast=False,
                                        is_image=False, prior_var=1.0, condition_input=None, given_noise=None, clip_feat=None,
-                                       graph=True, keep_trajectory=True, conv_precision="fp32", *, seed=None, seeds=None):
+                                       graph=True, keep_trajectory=True, conv_precision="fp32", *, seed=None, seeds=None,
+                                       known=None):
         """The tail of the ancestral chain from ``x_noisy`` (reference :504-563): the steps t = time_start-1 ... 0, the last of
         which returns the posterior mean; 1 <= time_start <= T, and time_start = T is the whole chain from a given start.
         Returns (x, output_list): output_list is the reference's plain list of the state after every step, whose last entry
@@ -568,9 +589,25 @@ class DiffusionDiscretized(object):
         first row.  S = 0 returns (x_noisy, []) with no launch.  This form is always keyed: the keys are `seeds`, or
         split_seed(seed, num_samples) (seed None: one is drawn).  graph=False is the debug path: the uniform eager tail on the
         whole batch once per distinct start, merged per sample; the same bits.  ValueError: given_noise, a wrong count, bool
-        entries, an entry outside 0 ... T."""
+        entries, an entry outside 0 ... T.
+        known = (x0, keep): region-preserving tail (RePaint's known-region conditioning, Lugmayr et al. 2022,
+        Algorithm 1 without its resampling jumps).  x0 is the clean latent, [num_samples] + shape; keep a bool tensor
+        [num_samples, P] over P groups of n/P consecutive elements of a sample's n (P divides n, n/P a multiple of 4: the local
+        prior's P = N latent points of 4 floats).  After the step at t the kept groups are replaced by a fresh forward draw of
+        x0 at the level the state now has, diffuse's scalars of index t-1 (known_levels), under the sample's key on
+        chain.KNOWN_STREAM; after the step at t = 0 by x0 itself, so the kept groups of the result are x0 bit for bit.  temp
+        scales the ancestral noise only.  time_start is an int or per-sample starts; both run on the known-region capture
+        (GraphedChain(known=True), a cache entry of its own; an int is a first_row of zeros), and another mask, x0 or set of
+        starts reuses it.  A sample below its first row is held, kept groups included.  Always keyed, like per-sample starts.
+        graph=False composes lion_philox_normal_keyed, lion_chain_diffuse and a where on the mask after each eager step; the
+        same bits.  ValueError before any launch: known with given_noise, an x0 of another shape, a mask that is not a bool
+        tensor [num_samples, P], or a group width that is not a multiple of 4."""
         keys = self._sample_keys("run_denoising_diffusion_from_t", seeds, num_samples, seed=seed, given_noise=given_noise)
         starts = self.per_sample_indices("run_denoising_diffusion_from_t", time_start, num_samples, 0, self._diffusion_steps)
+        if known is not None:
+            return self._tails_known(model, num_samples, shape, starts, time_start, x_noisy, temp, enable_autocast,
+                                     condition_input, given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys,
+                                     known)
         if starts is not None:
             return self._tails_from_rows(model, num_samples, shape, starts, x_noisy, temp, enable_autocast, condition_input,
                                          given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys)
@@ -635,6 +672,97 @@ class DiffusionDiscretized(object):
             if keep_trajectory:
                 output_list.extend(states)
             return x, output_list
+
+    # ---- region-preserving tails ------------------------------------------------------------------------
+    @staticmethod
+    def known_region(who, known, num_samples, shape):
+        """`known` of a sampler call as (x0, keep, elements per group): x0 [num_samples] + shape, keep a bool tensor
+        [num_samples, P] with P dividing the per-sample element count n and n/P a multiple of 4.  ValueError otherwise.  Host
+        work only: shapes and dtypes."""
+        try:
+            x0, keep = known
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{who}: known = (x0, keep), got {type(known).__name__}") from e
+        size, n = [int(num_samples)] + list(shape), int(np.prod(shape))
+        if not isinstance(x0, torch.Tensor) or list(x0.shape) != size:
+            raise ValueError(f"{who}: known x0 {tuple(getattr(x0, 'shape', ()))} for {size}")
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.dim() != 2 or keep.shape[0] != int(num_samples) \
+                or keep.shape[1] == 0 or n % keep.shape[1] != 0:
+            raise ValueError(f"{who}: known keep is a bool tensor [{num_samples}, P] with P dividing {n}, got "
+                             f"{getattr(keep, 'dtype', type(keep).__name__)} {tuple(getattr(keep, 'shape', ()))}")
+        width = n // int(keep.shape[1])
+        if width % 4 != 0:
+            raise ValueError(f"{who}: known keep has groups of {width} elements, must be a multiple of 4 (one mask byte per quad)")
+        return x0, keep, width
+
+    def _tails_known(self, model, num_samples, shape, starts, time_start, x_noisy, temp, enable_autocast, condition_input,
+                     given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys, known):
+        """run_denoising_diffusion_from_t(known=): starts is the list of per-sample starts, or None where time_start is an int"""
+        who = "run_denoising_diffusion_from_t"
+        if given_noise is not None:
+            raise ValueError(f"{who}: known draws under per-sample keys and cannot be combined with given_noise")
+        x0, keep, width = self.known_region(who, known, num_samples, shape)
+        if starts is None:
+            if isinstance(time_start, bool) or not isinstance(time_start, (int, np.integer)) \
+                    or not 0 <= time_start <= self._diffusion_steps:
+                raise ValueError(f"{who}: time_start = {time_start!r} outside [0, {self._diffusion_steps}]")
+            starts = [int(time_start)] * int(num_samples)
+        output_list = []
+        S = max(starts)
+        if S == 0:
+            return x_noisy, output_list
+        if not x_noisy.is_cuda:
+            raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
+        if list(x_noisy.shape) != [num_samples] + list(shape):
+            raise ValueError(f"{who}: x_noisy {tuple(x_noisy.shape)} for {[num_samples] + list(shape)}")
+        keys = self._call_keys(keys, seed, num_samples)
+        first_row = [S - s for s in starts]
+        table, ms = self.ddpm_table(S, temp), self.known_levels(S)
+        with _sampling(model, conv_precision):
+            x_noisy = x_noisy.to(self.device).contiguous()
+            x0, keep = x0.to(self.device).contiguous(), keep.to(self.device)
+            states = output_list if keep_trajectory else None
+            if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
+                quads = keep.repeat_interleave(width // 4, dim=1)   # one byte per quad
+                x = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, table, None, condition_input, clip_feat,
+                                 keys=keys, first_row=first_row, known=(x0, quads, ms), trajectory=states,
+                                 trajectory_before_last=True)
+            else:
+                elems = keep.repeat_interleave(width, dim=1).view(x0.shape)
+                x = self._known_steps(model, x_noisy, first_row, table, ms, enable_autocast, condition_input, clip_feat, states,
+                                      keys, x0, elems)
+            return x, output_list
+
+    def _known_steps(self, model, x, first_row, table, ms, enable_autocast, condition_input, clip_feat, states, keys, x0, elems):
+        """the eager form of the known-region chain, one row of `table` (ddpm_table) and `ms` (known_levels) at a time on the
+        whole batch: the keyed ancestral update for the samples at or past their first row, under their own row count, then for
+        their kept elements (`elems`, bool like x) the forward draw of x0 at the row's level -- lion_philox_normal_keyed on
+        chain.KNOWN_STREAM into lion_chain_diffuse -- or x0 itself where s == 0; each a `where` on the batch.  `states` as in
+        _ancestral_steps."""
+        dev, B, shape = self.device, x.shape[0], list(x.shape[1:])
+        words = _chain.key_words(keys, dev)
+        S = int(table.shape[0])
+        per_sample = lambda flags: torch.tensor(flags, device=dev).view([B] + [1] * len(shape))
+        for i in range(S):
+            t = S - 1 - i
+            eps_hat = self._eps_hat(model, x, t + 1, condition_input, clip_feat, enable_autocast, {})
+            is0, k_outer, k_a, k_b, scale = self.ddpm_coefficients(t)
+            m, s = float(ms[i, 0]), float(ms[i, 1])
+            new = x
+            for f in sorted({f for f in first_row if f <= i}):      # the samples that count this row as their row i - f
+                mine = per_sample([r == f for r in first_row])
+                z = None if is0 else self._keyed_step_noise(words, B, shape, i - f)
+                new = torch.where(mine, diffusion_ops.ddpm_update(x, eps_hat, z, is0, k_outer, k_a, k_b, scale,
+                                                                  float(table[i, 5])), new)
+                fresh = x0
+                if s != 0.0:
+                    z = diffusion_ops.philox_normal_keyed(words, B, shape, i - f, stream_id=_chain.KNOWN_STREAM, device=dev)
+                    fresh = diffusion_ops.diffuse(x0, m, s, noise=z)
+                new = torch.where(mine & elems, fresh, new)
+            if states is not None:
+                states.append(x if i == S - 1 else new)             # the last entry repeats the state before the final update
+            x = new
+        return x
 
     @torch.no_grad()
     def run_ddim(self, model, num_samples, shape, temp=1.0, enable_autocast=False, is_image=True,

@@ -6,7 +6,9 @@ Per latent the device work is one forward draw (``DiffusionDiscretized.diffuse``
 ``time_start`` replays of the prior's captured ancestral step (``run_denoising_diffusion_from_t``) -- the chain a sampling
 call of the same batch shape captured is the one replayed here.  ``time_start`` is one index per latent for the whole batch, as
 in the reference, or one per latent AND sample (per-sample start steps, DESIGN.md 4.6.9: one keyed forward draw and
-max(time_start) replays of the per-sample-start capture, each sample held until its own first row).  With ``solver_steps=S``
+max(time_start) replays of the per-sample-start capture, each sample held until its own first row).  With
+``keep=mask`` the local latent's tail is region-preserving: the marked latent points are kept, the rest is
+re-drawn conditioned on them, in the same number of replays.  With ``solver_steps=S``
 the tail is instead at most S replays of the few-step solver's captured step (``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
 
 ``voxel_guided`` is the recipe on the surface of the input's voxelisation (``perturb.voxel_surface_points``);
@@ -16,6 +18,7 @@ from __future__ import annotations
 
 import numbers
 
+import numpy as np
 import torch
 
 from . import chain as _chain
@@ -28,7 +31,7 @@ SUBKEYS = ("vae", "diffuse_global", "chain_global", "diffuse_local", "chain_loca
 
 @torch.no_grad()
 def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=None, keep_first=False, graph=True,
-                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True, seeds=None):
+                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True, seeds=None, keep=None):
     """x [B, N, 3] -> (points [B, N, 3], info).  vae: models.vae_adain.Model (in the mode the caller wants: eval() for
     inference); dae: [global prior, local prior]; diffusion: DiffusionDiscretized.
 
@@ -72,7 +75,16 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     per-step noise -- comes from its own keys at counters within the sample: it depends on neither B, nor b, nor the other
     samples' seeds, and torch's generators are not touched.  The output for a seed is promised bit-equal at equal B only
     (other batch sizes select other kernel plans).  info['seeds'] then holds 'seeds' (the list) and a list per sub-key.
-    ValueError before any launch: len(seeds) != B, or seeds with seed."""
+    ValueError before any launch: len(seeds) != B, or seeds with seed.
+    keep: a bool tensor or array [B, N] or [N] (one mask for every sample) over the INPUT points, True = keep that point's latent
+    point ("keep the legs, give me other backs").  The local latent is point-wise -- latent point i is the
+    latent_shape()[1] / N consecutive floats behind input point i -- and its tail runs region-preserving,
+    run_denoising_diffusion_from_t(known=(sampled local encoding, keep)): the kept latent points of 'local_edited' are those of
+    'local_original' bit for bit, the others are re-drawn conditioned on them.  The global latent follows time_start as without
+    keep; (0, t) leaves it alone.  keep_first, seeds, per-sample time_start and conv_precision combine with it.  The decoder
+    mixes neighbouring latent points, so the decoded kept points are NOT promised equal to the input points.  info['keep'] is
+    the mask that ran ([B, N] bool; None without keep).  ValueError before any launch: another dtype or shape, or keep with
+    solver_steps."""
     T = diffusion._diffusion_steps
     B = x.shape[0]
     pair = tuple(time_start) if isinstance(time_start, (tuple, list)) else (time_start, time_start)
@@ -92,6 +104,11 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     if solver_steps is not None and any(isinstance(t, tuple) for t in pair):
         raise ValueError("diffuse_denoise: per-sample time_start cannot be combined with solver_steps (a per-sample solver "
                          "schedule would need per-sample timesteps)")
+    if keep is not None:
+        if solver_steps is not None:
+            raise ValueError("diffuse_denoise: keep cannot be combined with solver_steps (the solver tails have no known-region "
+                             "form)")
+        keep = _keep_mask(keep, B, x.shape[1], vae.latent_shape()[1])
     visited = [[], []]
     names = SUBKEYS
     keyed = seeds is not None
@@ -128,6 +145,7 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
         if pair[i] == 0:
             return eps_ori
         which = ("global", "local")[i]
+        known = {"known": (eps_ori, keep)} if keep is not None and i == 1 else {}
         if isinstance(pair[i], tuple):   # per-sample starts: one keyed forward draw, max(start) replays of the from-rows capture
             top = max(pair[i])
             if top == 0:
@@ -138,7 +156,7 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
             eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], torch.tensor(pair[i], dtype=torch.int64),
                                                               eps_t, temp=temp, condition_input=condition_input,
                                                               clip_feat=clip_feat, graph=graph, keep_trajectory=False,
-                                                              conv_precision=conv_precision, **key("chain_" + which))
+                                                              conv_precision=conv_precision, **key("chain_" + which), **known)
             if keep_first:
                 eps[0:1] = eps_ori[0:1]
             return eps.contiguous()
@@ -154,7 +172,7 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
             eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp=temp,
                                                               condition_input=condition_input, clip_feat=clip_feat, graph=graph,
                                                               keep_trajectory=False, conv_precision=conv_precision,
-                                                              **key("chain_" + which))
+                                                              **key("chain_" + which), **known)
         if keep_first:
             eps[0:1] = eps_ori[0:1]
         return eps.contiguous()
@@ -173,8 +191,26 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     points = vae.decoder(None, beta=None, context=local_new.view(flat_shape), style=style)
     info = {"global_original": global_ori, "global_edited": global_new, "local_original": local_ori,
             "local_edited": local_new, "condition_input": condition_input, "time_start": pair, "seeds": seeds,
-            "tail_steps": (visited[0], visited[1])}
+            "tail_steps": (visited[0], visited[1]), "keep": keep}
     return points, info
+
+
+def _keep_mask(keep, B, n_points, local_shape):
+    """diffuse_denoise's `keep` as a bool tensor [B, n_points] (on the device it came from; an array: the host); ValueError on
+    another dtype or shape, or a local latent that is not a whole number of quads per point.  Host work only."""
+    if not isinstance(keep, torch.Tensor):
+        try:
+            keep = torch.from_numpy(np.asarray(keep))
+        except TypeError as e:
+            raise ValueError(f"diffuse_denoise: keep is a bool tensor or array, got {type(keep).__name__}") from e
+    if keep.dtype != torch.bool or tuple(keep.shape) not in ((B, n_points), (n_points,)):
+        raise ValueError(f"diffuse_denoise: keep is a bool mask [{B}, {n_points}] or [{n_points}], got {keep.dtype} "
+                         f"{tuple(keep.shape)}")
+    per_sample = int(np.prod(local_shape))
+    if per_sample % n_points != 0 or (per_sample // n_points) % 4 != 0:
+        raise ValueError(f"diffuse_denoise: keep needs a local latent of whole quads per point, got {per_sample} floats for "
+                         f"{n_points} points")
+    return (keep if keep.dim() == 2 else keep.unsqueeze(0).expand(B, n_points)).contiguous()
 
 
 @torch.no_grad()
