@@ -415,6 +415,30 @@ int lion_chain_update_noise_cm_keyed_known(int mode, const float *x, const float
                                            const int32_t *first_row, const uint32_t *keys, uint32_t stream_id,
                                            const float *known_x0, const uint8_t *keep, const float *known_ms,
                                            uint32_t known_stream_id, float *out, float *z_out, lionStream_t stream);
+/* Known region with resampling jumps: the "_known" pair with RePaint's jumps back up the chain (Lugmayr et
+ * al. 2022, Algorithm 1, lines 9-10), the j one-step transitions of a jump composed into one draw.  Arguments of the "_known"
+ * pair, and behind known_stream_id:
+ *   known_jump          device f32[rows][2], read at row i = cur[7] as (mf, sf): the forward move that ends the row, from the
+ *                       level the step leaves the state at to the level known_ms[i] names; (1, 0) where the row has none
+ *   resample_stream_id  the Philox stream of the jumps' draws
+ * A held sample and a kept quad are exactly those of the "_known" pair (known_ms[i] is the level BEHIND the jump).  A quad that
+ * is not kept takes the "_known" update o and then, where sf != 0,
+ *   out = (mf*o) + (sf*z''), two products and a sum, each rounded once (lion_chain_diffuse's arithmetic); z'' is the draw under
+ *   keys[b] at counter (j, local, resample_stream_id); z_out still receives the step's own z.
+ * A row with sf == 0 gives the bits of the "_known" entry point.
+ * LION_EINVAL before any launch: everything the "_known" pair refuses, a NULL known_jump, or resample_stream_id equal to
+ * stream_id or known_stream_id. */
+int lion_chain_update_noise_keyed_known_resample(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                                 const int32_t *first_row, const uint32_t *keys, uint32_t stream_id,
+                                                 const float *known_x0, const uint8_t *keep, const float *known_ms,
+                                                 uint32_t known_stream_id, const float *known_jump /* device f32[rows][2] */,
+                                                 uint32_t resample_stream_id, float *out, float *z_out, lionStream_t stream);
+int lion_chain_update_noise_cm_keyed_known_resample(int mode, const float *x, const float *eps_cm, int B, int N,
+                                                    const float *cur, const int32_t *first_row, const uint32_t *keys,
+                                                    uint32_t stream_id, const float *known_x0, const uint8_t *keep,
+                                                    const float *known_ms, uint32_t known_stream_id, const float *known_jump,
+                                                    uint32_t resample_stream_id, float *out, float *z_out,
+                                                    lionStream_t stream);
 /* Inputs of guided synthesis (csrc/perturb.hip): perturbed copies of clouds x f32[B][N][3], every cloud on its
  * own and under its own key (keys as above).  One Philox4x32-10 call per output point at counter = (point index WITHIN the
  * sample, a reserved step word, stream_id), words w0..w3; a fraction is u(w) = (w >> 8) * 2^-24, exact.  LION_VOXEL_STEP_WORD

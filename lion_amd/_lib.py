@@ -172,6 +172,10 @@ SIGNATURES = {
                                                  _vp, _vp]),
     "lion_chain_update_noise_cm_keyed_known": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32,
                                                     _vp, _vp, _vp]),
+    "lion_chain_update_noise_keyed_known_resample": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
+                                                          C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "lion_chain_update_noise_cm_keyed_known_resample": (_i, [_i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
+                                                             C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "lion_chain_diffuse_keyed_at": (_i, [_vp, _i, _i, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "lion_voxel_surface_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "lion_voxel_surface_points_keyed": (_i, [_vp, _i, _i, _i, _vp, C.c_uint32, _i, _vp, _vp, _vp, _sz, _vp]),

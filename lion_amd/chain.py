@@ -57,6 +57,11 @@ FROM_ROWS_MODES = (DDPM,)
 # behind the step's own: a kept quad is re-drawn from its clean value after every row, on a Philox stream of its own -- chain
 # steps draw on stream 0, the forward draw (diffusion_ops.diffuse) on stream 1.  The same launch count as the keyed step.
 KNOWN_STREAM = 2
+# Resampling jumps (GraphedChain(..., known=True, resample=True)): the known-region step ends with the
+# "_known_resample" entry point instead, which also takes the chain's `known_jump` (float32[capacity, 2], the forward move that
+# ends each row, (1, 0) where there is none) and this stream id behind the known region's: the quads that are not kept are moved
+# back up the chain by a draw on a Philox stream of its own.  The same launch count as the keyed step.
+RESAMPLE_STREAM = 3
 # the step words no chain step can have (a step's word is its row index < the table's capacity): include/lion_hip.h
 START_STEP_WORD, DIFFUSE_STEP_WORD = 0xFFFFFFFE, 0xFFFFFFFF
 _MASK64 = 0xFFFFFFFFFFFFFFFF
@@ -282,7 +287,7 @@ class CapturedStep:
 
 class GraphedChain:
     def __init__(self, model, num_samples, shape, condition_input, clip_feat, device, mode, capacity, warmup=2,
-                 record_noise=False, keyed=False, from_rows=False, known=False):
+                 record_noise=False, keyed=False, from_rows=False, known=False, resample=False):
         """keyed: sample b draws its noise under its own key, seed[b], at counters that count within the sample (the "_keyed"
         update kernels) -- `seed` is then int32[num_samples, 2] and prepare() / run() take num_samples keys.
         from_rows (keyed DDPM chains only, else ValueError): the chain owns `first_row`, int32[num_samples], which prepare()
@@ -290,9 +295,11 @@ class GraphedChain:
         there (the "_from" update kernel).
         known (keyed from_rows chains only, else ValueError): the chain also owns `known_x0`, `keep` and `known_ms`, which
         prepare() fills; the quads marked in `keep` are replaced after every row by a forward draw of known_x0 at that row's
-        level, after the last row by known_x0 itself (the "_known" update kernel)."""
+        level, after the last row by known_x0 itself (the "_known" update kernel).
+        resample (known chains only, else ValueError): the chain also owns `known_jump`, which prepare() fills; the quads that
+        are not kept end a row with the forward move it holds for that row (the "_known_resample" update kernel)."""
         self.model, self.mode, self.capacity, self.keyed = model, mode, int(capacity), bool(keyed)
-        self.from_rows, self.known = bool(from_rows), bool(known)
+        self.from_rows, self.known, self.resample = bool(from_rows), bool(known), bool(resample)
         dev = torch.device(device)
         size = [num_samples] + list(shape)
         per_sample = int(np.prod(shape))
@@ -301,6 +308,8 @@ class GraphedChain:
         if self.known and not (keyed and self.from_rows):
             raise ValueError(f"GraphedChain: known needs keyed=True and from_rows=True, got keyed={bool(keyed)}, "
                              f"from_rows={self.from_rows}")
+        if self.resample and not self.known:
+            raise ValueError("GraphedChain: resample needs known=True")
         if keyed and mode not in KEYED_MODES:
             raise ValueError(f"GraphedChain: mode {mode} draws nothing and has no keyed form")
         if keyed and per_sample % 4 != 0:
@@ -319,6 +328,7 @@ class GraphedChain:
         self.known_x0 = torch.zeros(size, device=dev) if self.known else None
         self.keep = torch.zeros(num_samples, per_sample // 4, dtype=torch.uint8, device=dev) if self.known else None
         self.known_ms = torch.tensor([1.0, 0.0], device=dev).repeat(self.capacity, 1) if self.known else None
+        self.known_jump = torch.tensor([1.0, 0.0], device=dev).repeat(self.capacity, 1) if self.resample else None   # no jumps
         self.z = torch.zeros(size, device=dev) if record_noise and mode != ENCODE else None   # tests: the noise each step used
         self.hist = torch.zeros(size, device=dev) if mode in (DPMPP, SDE_DPMPP) else None   # the previous step's data prediction
         self.base = torch.zeros(size, device=dev) if mode == ENCODE else None   # ENCODE: the state at the leg's low end
@@ -366,12 +376,14 @@ class GraphedChain:
                 given["keys"] = [self.first_row, self.seed]
             if self.known:   # behind the step's stream id: the known region's buffers and its stream
                 k = spec.index("keys") + 2
-                spec = spec[:k] + ("known_x0", "keep", "known_ms", KNOWN_STREAM) + spec[k:]
+                spec = spec[:k] + ("known_x0", "keep", "known_ms", KNOWN_STREAM) \
+                    + (("known_jump", RESAMPLE_STREAM) if self.resample else ()) + spec[k:]
             args = []
             for a in spec:
                 args += given[a] if a in given else [getattr(self, a) if isinstance(a, str) else a]
             _lib.call(entry + ("_cm" if self.cm_out else "") + ("_keyed" if self.keyed else "")
-                      + ("_known" if self.known else "_from" if self.from_rows else ""), *args)
+                      + ("_known_resample" if self.resample else "_known" if self.known else "_from" if self.from_rows else ""),
+                      *args)
         self.step = CapturedStep(model, step, self.x, warmup=warmup)
 
     def matches(self, condition_input, clip_feat):
@@ -393,7 +405,8 @@ class GraphedChain:
         (S or more: held throughout).
         `known` (a known chain, where it is required): (x0, keep, ms) -- the clean latent, shaped like x_init; the mask, a
         device tensor [num_samples, elements per sample / 4], non-zero = kept; ms [S, 2] float32 on the host, row i the forward
-        process's (m, s) of the level the state has after row i."""
+        process's (m, s) of the level the state has after row i.  On a resample chain it is (x0, keep, ms, jump) with jump
+        [S, 2] float32 on the host, row i the forward move (mf, sf) that ends row i, (1, 0) for none."""
         S = self.prepare(x_init, table, seed, condition_input, clip_feat, first_row, known)
         if RECORD is not None and self.z is not None and noise_trajectory is None:
             noise_trajectory = []
@@ -427,7 +440,9 @@ class GraphedChain:
         if self.known != (known is not None):
             raise ValueError("GraphedChain: known goes with a known chain, and only with it")
         if self.known:
-            x0, keep, ms = known
+            if len(known) != (4 if self.resample else 3):
+                raise ValueError("GraphedChain: known = (x0, keep, ms), and (x0, keep, ms, jump) on a resample chain")
+            x0, keep, ms = known[:3]
             ms = np.ascontiguousarray(ms, dtype=np.float32)
             if tuple(x0.shape) != tuple(self.x.shape) or tuple(keep.shape) != tuple(self.keep.shape) or ms.shape != (S, 2):
                 raise ValueError(f"GraphedChain: known = (x0 {tuple(x0.shape)}, keep {tuple(keep.shape)}, ms {ms.shape}) for "
@@ -435,6 +450,11 @@ class GraphedChain:
             self.known_x0.copy_(x0)
             self.keep.copy_(keep)
             self.known_ms[:S].copy_(torch.from_numpy(ms))
+        if self.resample:
+            jump = np.ascontiguousarray(known[3], dtype=np.float32)
+            if jump.shape != (S, 2):
+                raise ValueError(f"GraphedChain: known jump {jump.shape} for {(S, 2)}")
+            self.known_jump[:S].copy_(torch.from_numpy(jump))
         self.x.copy_(x_init)
         if self.cond is not None:
             self.cond.copy_(condition_input)
@@ -464,22 +484,24 @@ for _name in ("replay", "graph", "graphs", "graph_b", "geo_graphs", "pinned", "p
 
 
 class ChainCache(LRU):
-    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed, from_rows, known) -> GraphedChain.  A keyed
+    """the captured chains of one DiffusionDiscretized: (model, mode, batch shape, keyed, from_rows, known, resample) ->
+    GraphedChain.  A keyed
     and an unkeyed capture of one (model, mode, shape) coexist, each in a slot of its own; the modes that draw nothing have the
     unkeyed capture only and serve a keyed call with it.  The per-sample-start capture (from_rows: keyed DDPM only, ValueError
     otherwise) is a third entry beside them and takes one of the four slots, and the known-region capture (known: keyed
-    from_rows only, ValueError otherwise) a fourth."""
+    from_rows only, ValueError otherwise) a fourth.  The resampling capture (resample: known only, ValueError otherwise) is one
+    more entry: a model that runs all five evicts the least recently used of them from the four slots."""
 
     def get(self, model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity, keyed=False,
-            from_rows=False, known=False):
+            from_rows=False, known=False, resample=False):
         rec = RECORD is not None
-        from_rows, known = bool(from_rows), bool(known)
+        from_rows, known, resample = bool(from_rows), bool(known), bool(resample)
         keyed = bool(keyed) and (mode in KEYED_MODES or from_rows)   # from_rows on a mode without a keyed form: refused below
         return self.lookup(
-            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed, from_rows, known),
+            (id(model), mode, int(num_samples), tuple(shape), str(device), rec, keyed, from_rows, known, resample),
             lambda hit: hit.model is model and hit.capacity >= table_capacity and hit.matches(condition_input, clip_feat),
             lambda: GraphedChain(model, num_samples, shape, condition_input, clip_feat, device, mode, table_capacity,
-                                 record_noise=rec, keyed=keyed, from_rows=from_rows, known=known))
+                                 record_noise=rec, keyed=keyed, from_rows=from_rows, known=known, resample=resample))
 
 
 def draw_seed() -> int:

@@ -252,13 +252,19 @@ __global__ void update_noise_keyed_from_kernel(const float *x, const float *__re
 // diffuse_body's arithmetic, z' at counter (j, local, known_stream_id) -- or, where s == 0 (the last row), out = x0 bit for
 // bit, nothing drawn, z_out = 0.  A kept quad reads neither x nor eps.  first_row NULL: every sample starts at row 0.
 // The mask is per lane: a wave with both kinds runs the one draw below once and then each kind's loads and arithmetic.
-template <int MODE>
+// RESAMPLE (RePaint's resampling jumps, composed: DESIGN.md 4.6.11): row i may end with a forward move of the state,
+// (mf, sf) = known_jump[row].  Where sf != 0 a quad that is not kept goes on from its update o to mf*o + sf*z'' with the same
+// arithmetic, z'' at counter (j, local, resample_stream_id); z_out keeps the step's own z.  Kept quads are as above: known_ms
+// already holds the level behind the jump.  sf is one value per row, so the branch is uniform.  Without RESAMPLE neither
+// known_jump nor resample_stream_id is read.
+template <int MODE, bool RESAMPLE>
 __global__ void update_noise_keyed_known_kernel(const float *x, const float *__restrict__ eps, size_t numel,
                                                 uint32_t sample_quads, const float *__restrict__ cur,
                                                 const int32_t *__restrict__ first_row, const uint32_t *__restrict__ keys,
                                                 uint32_t stream_id, const float *__restrict__ known_x0,
                                                 const uint8_t *__restrict__ keep, const float *__restrict__ known_ms,
-                                                uint32_t known_stream_id, float *out, float *z_out, int cm_points) {
+                                                uint32_t known_stream_id, const float *__restrict__ known_jump,
+                                                uint32_t resample_stream_id, float *out, float *z_out, int cm_points) {
   const int32_t row = __float_as_int(cur[7]);
   const int32_t local = first_row ? row - first_row[blockIdx.y] : row;
   if (local < 0) {
@@ -286,6 +292,15 @@ __global__ void update_noise_keyed_known_kernel(const float *x, const float *__r
     load_quad(x, i, numel, true, xv);
     load_eps_quad<true>(eps, q, ctr, numel, true, cm_points, ev);
     update_quad<MODE>(xv, ev, z, cur[1], cur[2], cur[3], cur[4], cur[5], cur[6], o);
+    if constexpr (RESAMPLE) {
+      const float mf = known_jump[2 * (size_t)row], sf = known_jump[2 * (size_t)row + 1];
+      if (sf != 0.f) {
+        float zr[4];
+        normal4(ctr, (uint32_t)local, resample_stream_id, (uint64_t)key[0] | ((uint64_t)key[1] << 32), zr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = add_rn(mul_rn(mf, o[j]), mul_rn(sf, zr[j]));
+      }
+    }
   }
   store_quad(out, i, numel, true, o);
   if (z_out) store_quad(z_out, i, numel, true, z);
@@ -349,21 +364,23 @@ static int update_noise_keyed_launch(int mode, hipStream_t st, const float *x, c
                                                                z_out, cm_points);
 }
 
-// the known-region form on the same grid; first_row may be NULL here
+// the known-region form on the same grid; first_row may be NULL here.  known_jump NULL: the form without resampling jumps
 static int update_noise_known_launch(int mode, hipStream_t st, const float *x, const float *eps, int B, int n, const float *cur,
                                      const int32_t *first_row, const uint32_t *keys, uint32_t stream_id, const float *known_x0,
-                                     const uint8_t *keep, const float *known_ms, uint32_t known_stream_id, float *out,
-                                     float *z_out, int cm_points) {
+                                     const uint8_t *keep, const float *known_ms, uint32_t known_stream_id,
+                                     const float *known_jump, uint32_t resample_stream_id, float *out, float *z_out,
+                                     int cm_points) {
   dim3 grid;
   uint32_t sq;
   if (keyed_grid(B, n, &grid, &sq) != LION_OK) return LION_EINVAL;
   const size_t numel = (size_t)B * n;
-  return mode == 0 ? lion_launch<update_noise_keyed_known_kernel<0>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,
-                                                                     stream_id, known_x0, keep, known_ms, known_stream_id, out,
-                                                                     z_out, cm_points)
-                   : lion_launch<update_noise_keyed_known_kernel<1>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,
-                                                                     stream_id, known_x0, keep, known_ms, known_stream_id, out,
-                                                                     z_out, cm_points);
+#define LION_KNOWN_LAUNCH(MODE, RESAMPLE)                                                                                      \
+  lion_launch<update_noise_keyed_known_kernel<MODE, RESAMPLE>>(grid, 256, 0, st, x, eps, numel, sq, cur, first_row, keys,      \
+                                                               stream_id, known_x0, keep, known_ms, known_stream_id,           \
+                                                               known_jump, resample_stream_id, out, z_out, cm_points)
+  if (known_jump) return mode == 0 ? LION_KNOWN_LAUNCH(0, true) : LION_KNOWN_LAUNCH(1, true);
+  return mode == 0 ? LION_KNOWN_LAUNCH(0, false) : LION_KNOWN_LAUNCH(1, false);
+#undef LION_KNOWN_LAUNCH
 }
 
 static int update_noise_launch(int mode, hipStream_t st, const float *x, const float *eps, size_t numel,
@@ -780,7 +797,7 @@ int lion_chain_update_noise_keyed_known(int mode, const float *x, const float *e
   if (!known_x0 || !keep || !known_ms || known_stream_id == stream_id) return LION_EINVAL;
   if (!aligned16({x, eps, known_x0, out, z_out})) return LION_EINVAL;
   return update_noise_known_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, first_row, keys, stream_id,
-                                   known_x0, keep, known_ms, known_stream_id, out, z_out, 0);
+                                   known_x0, keep, known_ms, known_stream_id, nullptr, 0, out, z_out, 0);
 }
 
 int lion_chain_update_noise_cm_keyed_known(int mode, const float *x, const float *eps_cm, int B, int N, const float *cur,
@@ -791,7 +808,35 @@ int lion_chain_update_noise_cm_keyed_known(int mode, const float *x, const float
   if (!known_x0 || !keep || !known_ms || known_stream_id == stream_id) return LION_EINVAL;
   if (!aligned16({x, known_x0, out, z_out})) return LION_EINVAL;
   return update_noise_known_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, first_row, keys, stream_id,
-                                   known_x0, keep, known_ms, known_stream_id, out, z_out, N);
+                                   known_x0, keep, known_ms, known_stream_id, nullptr, 0, out, z_out, N);
+}
+
+// ---- known region with resampling jumps: a forward move of the free quads at the end of the rows that known_jump marks --------
+int lion_chain_update_noise_keyed_known_resample(int mode, const float *x, const float *eps, int B, int n, const float *cur,
+                                                 const int32_t *first_row, const uint32_t *keys, uint32_t stream_id,
+                                                 const float *known_x0, const uint8_t *keep, const float *known_ms,
+                                                 uint32_t known_stream_id, const float *known_jump,
+                                                 uint32_t resample_stream_id, float *out, float *z_out, lionStream_t stream) {
+  if (!x || !eps || !cur || !keys || !out || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!known_x0 || !keep || !known_ms || known_stream_id == stream_id) return LION_EINVAL;
+  if (!known_jump || resample_stream_id == stream_id || resample_stream_id == known_stream_id) return LION_EINVAL;
+  if (!aligned16({x, eps, known_x0, out, z_out})) return LION_EINVAL;
+  return update_noise_known_launch(mode, static_cast<hipStream_t>(stream), x, eps, B, n, cur, first_row, keys, stream_id,
+                                   known_x0, keep, known_ms, known_stream_id, known_jump, resample_stream_id, out, z_out, 0);
+}
+
+int lion_chain_update_noise_cm_keyed_known_resample(int mode, const float *x, const float *eps_cm, int B, int N,
+                                                    const float *cur, const int32_t *first_row, const uint32_t *keys,
+                                                    uint32_t stream_id, const float *known_x0, const uint8_t *keep,
+                                                    const float *known_ms, uint32_t known_stream_id, const float *known_jump,
+                                                    uint32_t resample_stream_id, float *out, float *z_out,
+                                                    lionStream_t stream) {
+  if (!x || !eps_cm || !cur || !keys || !out || N <= 0 || N > 0x1fffffff || (mode != 0 && mode != 1)) return LION_EINVAL;
+  if (!known_x0 || !keep || !known_ms || known_stream_id == stream_id) return LION_EINVAL;
+  if (!known_jump || resample_stream_id == stream_id || resample_stream_id == known_stream_id) return LION_EINVAL;
+  if (!aligned16({x, known_x0, out, z_out})) return LION_EINVAL;
+  return update_noise_known_launch(mode, static_cast<hipStream_t>(stream), x, eps_cm, B, N * 4, cur, first_row, keys, stream_id,
+                                   known_x0, keep, known_ms, known_stream_id, known_jump, resample_stream_id, out, z_out, N);
 }
 
 int lion_chain_update_multistep_noise_keyed(const float *x, const float *eps, const float *hist, int B, int n, const float *cur,

@@ -231,6 +231,67 @@ class DiffusionDiscretized(object):
                 ms[i] = (float(torch.sqrt(ab)), float(torch.sqrt(1.0 - ab)))
         return ms
 
+    # ---- RePaint's resampling jumps (DESIGN.md 4.6.11): a schedule that walks up as well as down ---------------------------
+    def resample_walk(self, t_from, jump_length, n_resample):
+        """[(t, up), ...]: the ancestral step at index t (ddpm_table's sense), then a forward move of `up` levels (0: none).
+        With n the number of steps still to go, n = t_from, and the anchors a = j, 2j, ... with a + j <= t_from, each with a
+        budget of n_resample - 1: take the step at t = n - 1 (n -= 1); where n is then an anchor with budget left, spend one,
+        mark that row up = j and set n += j.  RePaint's get_schedule_jump (Lugmayr et al. 2022) with the j one-step forward
+        transitions of a jump composed into one move and no jump from the clean state; an anchor is consumed only when a step
+        reaches it.  n_resample = 1 is the plain tail; the row count is t_from + (#anchors)*(n_resample - 1)*j.  ValueError:
+        a bool or non-integer argument, jump_length or n_resample below 1, t_from outside 1 ... T, more than 16*T rows.  Host
+        arithmetic only."""
+        T = self._diffusion_steps
+        for name, v in (("t_from", t_from), ("jump_length", jump_length), ("n_resample", n_resample)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"resample_walk: {name} = {v!r} is not an int")
+        t_from, j, R = int(t_from), int(jump_length), int(n_resample)
+        if j < 1 or R < 1:
+            raise ValueError(f"resample_walk: jump_length = {j} and n_resample = {R} must be at least 1")
+        if not 1 <= t_from <= T:
+            raise ValueError(f"resample_walk: t_from = {t_from} outside [1, {T}]")
+        anchors = max(t_from // j - 1, 0)                   # a = j ... with a + j <= t_from
+        rows = t_from + anchors * (R - 1) * j
+        if rows > 16 * T:
+            raise ValueError(f"resample_walk: {rows} rows for t_from = {t_from}, jump_length = {j}, n_resample = {R}: more "
+                             f"than 16*T = {16 * T}")
+        budget = {a * j: R - 1 for a in range(1, anchors + 1)}
+        walk, n = [], t_from
+        while n > 0:
+            n -= 1
+            up = 0
+            if budget.get(n, 0) > 0:
+                budget[n] -= 1
+                up = j
+            walk.append((n, up))
+            n += up
+        assert len(walk) == rows
+        return walk
+
+    def resample_tables(self, t_from, jump_length, n_resample, temp=1.0):
+        """(table [S', 8], ms [S', 2], jump [S', 2]), float32, for the S' rows (t_i, up_i) of resample_walk: table row i is
+        ddpm_table's row of t_i; jump[i] = (mf, sf) is the forward move that ends the row, (1, 0) where up_i = 0 and else
+        mf = sqrt(ab[t-1+up] / ab[t-1]), sf = sqrt(1 - ab[t-1+up] / ab[t-1]) on the float32 host schedule; ms[i] is
+        known_levels' pair of the level the state has after the row, jump included: index t-1+up, (1, 0) after the step at
+        t = 0.  With n_resample = 1 these are ddpm_table(t_from, temp), known_levels(t_from) and (1, 0) rows, bit for bit.
+        What the resampling chain reads (chain.GraphedChain(known=True, resample=True)).  Host arithmetic only."""
+        walk = self.resample_walk(t_from, jump_length, n_resample)
+        plain, levels = self.ddpm_table(t_from, temp), self.known_levels(t_from)
+        table = np.zeros((len(walk), 8), np.float32)
+        ms = np.zeros((len(walk), 2), np.float32)
+        jump = np.zeros((len(walk), 2), np.float32)
+        ab = self._h_alpha_bars
+        for i, (t, up) in enumerate(walk):
+            table[i] = plain[int(t_from) - 1 - t]
+            if up == 0:
+                ms[i], jump[i] = levels[int(t_from) - 1 - t], (1.0, 0.0)
+            else:                                           # t >= 1 here: no jump from the clean state
+                ratio = ab[t - 1 + up] / ab[t - 1]
+                jump[i] = (float(torch.sqrt(ratio)), float(torch.sqrt(1.0 - ratio)))
+                level = ab[t - 1 + up]                      # known_levels' expressions at the index behind the jump
+                ms[i] = (float(torch.sqrt(level)), float(torch.sqrt(1.0 - level)))
+        return table, ms, jump
+
     # ---- DPM-Solver++(2M): schedule and coefficients (float64 on the widened float32 schedule, cast once) ----------------
     def _half_logsnr(self):
         """lambda[i] = log(alpha_i / sigma_i) = 0.5*(log(ab_i) - log1p(-ab_i)) in float64, with ab widened from float32"""
@@ -382,12 +443,14 @@ class DiffusionDiscretized(object):
         from x over `table`; seed None: one is drawn with chain.draw_seed() once the chain is there; `run`: GraphedChain.run's
         keywords.  keys (a list of num_samples 64-bit keys) in place of seed: the keyed capture of a mode that draws.
         first_row (num_samples ints, with keys; DDPM only): the per-sample-start capture, a cache entry of its own.
-        known (GraphedChain.run's triple, with first_row): the known-region capture, another entry of its own.
+        known (GraphedChain.run's triple, with first_row): the known-region capture, another entry of its own; with a fourth
+        element, the jump table, the resampling capture, one more.
         Returns the final latent."""
         keyed = keys is not None and mode in _chain.KEYED_MODES
+        more = {"resample": True} if known is not None and len(known) == 4 else {}
         ch = self._chains.get(model, num_samples, shape, condition_input, clip_feat, self.device, mode,
                               self._diffusion_steps if capacity is None else capacity, keyed=keyed,
-                              from_rows=first_row is not None, known=known is not None)
+                              from_rows=first_row is not None, known=known is not None, **more)
         if known is not None:
             return ch.run(x, table, keys, condition_input, clip_feat, first_row=first_row, known=known, **run)
         if first_row is not None:
@@ -565,7 +628,7 @@ class DiffusionDiscretized(object):
     def run_denoising_diffusion_from_t(self, model, num_samples, shape, time_start, x_noisy, temp=1.0, enable_autocast=False,
                                        is_image=False, prior_var=1.0, condition_input=None, given_noise=None, clip_feat=None,
                                        graph=True, keep_trajectory=True, conv_precision="fp32", *, seed=None, seeds=None,
-                                       known=None):
+                                       known=None, resample=None):
         """The tail of the ancestral chain from ``x_noisy`` (reference :504-563): the steps t = time_start-1 ... 0, the last of
         which returns the posterior mean; 1 <= time_start <= T, and time_start = T is the whole chain from a given start.
         Returns (x, output_list): output_list is the reference's plain list of the state after every step, whose last entry
@@ -601,13 +664,36 @@ class DiffusionDiscretized(object):
         starts reuses it.  A sample below its first row is held, kept groups included.  Always keyed, like per-sample starts.
         graph=False composes lion_philox_normal_keyed, lion_chain_diffuse and a where on the mask after each eager step; the
         same bits.  ValueError before any launch: known with given_noise, an x0 of another shape, a mask that is not a bool
-        tensor [num_samples, P], or a group width that is not a multiple of 4."""
-        keys = self._sample_keys("run_denoising_diffusion_from_t", seeds, num_samples, seed=seed, given_noise=given_noise)
-        starts = self.per_sample_indices("run_denoising_diffusion_from_t", time_start, num_samples, 0, self._diffusion_steps)
+        tensor [num_samples, P], or a group width that is not a multiple of 4.
+        resample (with known): RePaint's resampling jumps, which make the re-drawn part agree with the kept
+        one.  An int R is n_resample at jump length 10 (RePaint's default), a pair is (jump_length, n_resample).  The call then
+        replays the rows of resample_walk(time_start, jump_length, n_resample): after the step that reaches an anchor
+        (jump_length, 2*jump_length, ... steps to go) the elements that are not kept move jump_length levels back up in ONE
+        forward draw, on chain.RESAMPLE_STREAM, while the kept ones are drawn at that higher level; each anchor is visited
+        n_resample times.  This runs on the resampling capture (GraphedChain(known=True, resample=True), one more cache entry)
+        over resample_tables; output_list holds the state after every row, jump included.  n_resample = 1 is the call without
+        resample: same capture, same launches, same bits.  graph=False adds lion_philox_normal_keyed, lion_chain_diffuse and
+        a where on the elements that are not kept to the jump rows; the same bits.  ValueError before any launch: resample
+        without known, with per-sample time_start (a sample's own walk would differ from its uniform call's) or with
+        given_noise; a bool, a non-integer or a value below 1; a walk of more than 16*T rows."""
+        who = "run_denoising_diffusion_from_t"
+        keys = self._sample_keys(who, seeds, num_samples, seed=seed, given_noise=given_noise)
+        starts = self.per_sample_indices(who, time_start, num_samples, 0, self._diffusion_steps)
+        if resample is not None:
+            resample = self.resample_pair(who, resample)
+            if known is None:
+                raise ValueError(f"{who}: resample needs known = (x0, keep): without a kept region there is nothing to agree with")
+            if starts is not None:
+                raise ValueError(f"{who}: resample cannot be combined with per-sample time_start (a sample's own walk would "
+                                 f"differ from the walk of its uniform call)")
+            if given_noise is not None:
+                raise ValueError(f"{who}: resample draws under per-sample keys and cannot be combined with given_noise")
+            if resample[1] == 1:                            # no jump is ever made: the known-region tail as it is
+                resample = None
         if known is not None:
             return self._tails_known(model, num_samples, shape, starts, time_start, x_noisy, temp, enable_autocast,
                                      condition_input, given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys,
-                                     known)
+                                     known, resample)
         if starts is not None:
             return self._tails_from_rows(model, num_samples, shape, starts, x_noisy, temp, enable_autocast, condition_input,
                                          given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys)
@@ -695,9 +781,20 @@ class DiffusionDiscretized(object):
             raise ValueError(f"{who}: known keep has groups of {width} elements, must be a multiple of 4 (one mask byte per quad)")
         return x0, keep, width
 
+    @staticmethod
+    def resample_pair(who, resample):
+        """`resample` of a sampler or editing call as (jump_length, n_resample): an int R is (10, R), RePaint's default jump
+        length.  ValueError on anything else, a bool, or a value below 1.  Host work only."""
+        pair = (10, resample) if isinstance(resample, (int, np.integer)) else resample
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2 \
+                or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in pair):
+            raise ValueError(f"{who}: resample = {resample!r}: an int n_resample >= 1 or a pair (jump_length, n_resample) of them")
+        return int(pair[0]), int(pair[1])
+
     def _tails_known(self, model, num_samples, shape, starts, time_start, x_noisy, temp, enable_autocast, condition_input,
-                     given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys, known):
-        """run_denoising_diffusion_from_t(known=): starts is the list of per-sample starts, or None where time_start is an int"""
+                     given_noise, clip_feat, graph, keep_trajectory, conv_precision, seed, keys, known, resample=None):
+        """run_denoising_diffusion_from_t(known=): starts is the list of per-sample starts, or None where time_start is an int;
+        resample is None or (jump_length, n_resample) with n_resample > 1, and then starts is None"""
         who = "run_denoising_diffusion_from_t"
         if given_noise is not None:
             raise ValueError(f"{who}: known draws under per-sample keys and cannot be combined with given_noise")
@@ -711,13 +808,19 @@ class DiffusionDiscretized(object):
         S = max(starts)
         if S == 0:
             return x_noisy, output_list
+        # the walk's three tables, here so that a walk that is too long is refused before anything else happens
+        tables = None if resample is None else self.resample_tables(S, *resample, temp=temp)
         if not x_noisy.is_cuda:
             raise RuntimeError("lion_amd: expected a CUDA(HIP) tensor; there is no CPU path")
         if list(x_noisy.shape) != [num_samples] + list(shape):
             raise ValueError(f"{who}: x_noisy {tuple(x_noisy.shape)} for {[num_samples] + list(shape)}")
         keys = self._call_keys(keys, seed, num_samples)
         first_row = [S - s for s in starts]
-        table, ms = self.ddpm_table(S, temp), self.known_levels(S)
+        if tables is None:
+            tables = self.ddpm_table(S, temp), self.known_levels(S)
+        table, ms, jump = tables[0], tables[1], tables[2:]
+        # the resampling capture holds the longest walk it has run, and at least the plain chain
+        more = {"capacity": max(self._diffusion_steps, int(table.shape[0]))} if jump else {}
         with _sampling(model, conv_precision):
             x_noisy = x_noisy.to(self.device).contiguous()
             x0, keep = x0.to(self.device).contiguous(), keep.to(self.device)
@@ -725,29 +828,33 @@ class DiffusionDiscretized(object):
             if graph and _chain.graphable(model, x_noisy, enable_autocast, {}):
                 quads = keep.repeat_interleave(width // 4, dim=1)   # one byte per quad
                 x = self._replay(model, num_samples, shape, _chain.DDPM, x_noisy, table, None, condition_input, clip_feat,
-                                 keys=keys, first_row=first_row, known=(x0, quads, ms), trajectory=states,
-                                 trajectory_before_last=True)
+                                 keys=keys, first_row=first_row, known=(x0, quads, ms) + jump, trajectory=states,
+                                 trajectory_before_last=True, **more)
             else:
                 elems = keep.repeat_interleave(width, dim=1).view(x0.shape)
                 x = self._known_steps(model, x_noisy, first_row, table, ms, enable_autocast, condition_input, clip_feat, states,
-                                      keys, x0, elems)
+                                      keys, x0, elems, *jump)
             return x, output_list
 
-    def _known_steps(self, model, x, first_row, table, ms, enable_autocast, condition_input, clip_feat, states, keys, x0, elems):
+    def _known_steps(self, model, x, first_row, table, ms, enable_autocast, condition_input, clip_feat, states, keys, x0, elems,
+                     jump=None):
         """the eager form of the known-region chain, one row of `table` (ddpm_table) and `ms` (known_levels) at a time on the
         whole batch: the keyed ancestral update for the samples at or past their first row, under their own row count, then for
         their kept elements (`elems`, bool like x) the forward draw of x0 at the row's level -- lion_philox_normal_keyed on
-        chain.KNOWN_STREAM into lion_chain_diffuse -- or x0 itself where s == 0; each a `where` on the batch.  `states` as in
-        _ancestral_steps."""
+        chain.KNOWN_STREAM into lion_chain_diffuse -- or x0 itself where s == 0; each a `where` on the batch.  `jump`
+        (resample_tables' third array): where row i has sf != 0 the elements that are not kept then go through the same pair of
+        launches on chain.RESAMPLE_STREAM with (mf, sf), from their update.  The step of row i is the one at t = table[i, 0] - 1.
+        `states` as in _ancestral_steps."""
         dev, B, shape = self.device, x.shape[0], list(x.shape[1:])
         words = _chain.key_words(keys, dev)
         S = int(table.shape[0])
         per_sample = lambda flags: torch.tensor(flags, device=dev).view([B] + [1] * len(shape))
         for i in range(S):
-            t = S - 1 - i
+            t = int(table[i, 0]) - 1                        # S - 1 - i on a plain tail
             eps_hat = self._eps_hat(model, x, t + 1, condition_input, clip_feat, enable_autocast, {})
             is0, k_outer, k_a, k_b, scale = self.ddpm_coefficients(t)
             m, s = float(ms[i, 0]), float(ms[i, 1])
+            mf, sf = (1.0, 0.0) if jump is None else (float(jump[i, 0]), float(jump[i, 1]))
             new = x
             for f in sorted({f for f in first_row if f <= i}):      # the samples that count this row as their row i - f
                 mine = per_sample([r == f for r in first_row])
@@ -759,6 +866,9 @@ class DiffusionDiscretized(object):
                     z = diffusion_ops.philox_normal_keyed(words, B, shape, i - f, stream_id=_chain.KNOWN_STREAM, device=dev)
                     fresh = diffusion_ops.diffuse(x0, m, s, noise=z)
                 new = torch.where(mine & elems, fresh, new)
+                if sf != 0.0:                               # the jump: the other elements move back up from their update
+                    z = diffusion_ops.philox_normal_keyed(words, B, shape, i - f, stream_id=_chain.RESAMPLE_STREAM, device=dev)
+                    new = torch.where(mine & ~elems, diffusion_ops.diffuse(new, mf, sf, noise=z), new)
             if states is not None:
                 states.append(x if i == S - 1 else new)             # the last entry repeats the state before the final update
             x = new

@@ -8,7 +8,8 @@ call of the same batch shape captured is the one replayed here.  ``time_start`` 
 in the reference, or one per latent AND sample (per-sample start steps, DESIGN.md 4.6.9: one keyed forward draw and
 max(time_start) replays of the per-sample-start capture, each sample held until its own first row).  With
 ``keep=mask`` the local latent's tail is region-preserving: the marked latent points are kept, the rest is
-re-drawn conditioned on them, in the same number of replays.  With ``solver_steps=S``
+re-drawn conditioned on them, in the same number of replays; ``resample=`` adds RePaint's resampling jumps to that tail (DESIGN.md
+4.6.11: more replays, and a re-drawn part that agrees with the kept one).  With ``solver_steps=S``
 the tail is instead at most S replays of the few-step solver's captured step (``run_dpm_solver(t_start=...)``, by default its stochastic form: fresh noise re-enters during the tail, as in the recipe).
 
 ``voxel_guided`` is the recipe on the surface of the input's voxelisation (``perturb.voxel_surface_points``);
@@ -31,7 +32,8 @@ SUBKEYS = ("vae", "diffuse_global", "chain_global", "diffuse_local", "chain_loca
 
 @torch.no_grad()
 def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=None, keep_first=False, graph=True,
-                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True, seeds=None, keep=None):
+                    conv_precision="fp32", seed=None, solver_steps=None, stochastic=True, seeds=None, keep=None,
+                    resample=None):
     """x [B, N, 3] -> (points [B, N, 3], info).  vae: models.vae_adain.Model (in the mode the caller wants: eval() for
     inference); dae: [global prior, local prior]; diffusion: DiffusionDiscretized.
 
@@ -84,7 +86,15 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     keep; (0, t) leaves it alone.  keep_first, seeds, per-sample time_start and conv_precision combine with it.  The decoder
     mixes neighbouring latent points, so the decoded kept points are NOT promised equal to the input points.  info['keep'] is
     the mask that ran ([B, N] bool; None without keep).  ValueError before any launch: another dtype or shape, or keep with
-    solver_steps."""
+    solver_steps.
+    resample (with keep): RePaint's resampling jumps on the region-preserving tail, an int n_resample (jump
+    length 10) or a pair (jump_length, n_resample), as run_denoising_diffusion_from_t(resample=) takes it.  In a single pass the
+    re-drawn points only ever see independent noisy copies of the kept ones and stay close to the input at small time_start;
+    walking back up and down n_resample times at every anchor lets them follow the kept points.  It applies where `known` is
+    passed, the local latent's tail.  info['resample'] is (jump_length, n_resample) (None without it) and info['tail_rows']
+    the replay count per latent: time_start for the global latent, the length of resample_walk(time_start, jump_length,
+    n_resample) for the local one.  'tail_steps' stays the plain descending list.  ValueError before any launch: resample
+    without keep, with solver_steps or with per-sample time_start."""
     T = diffusion._diffusion_steps
     B = x.shape[0]
     pair = tuple(time_start) if isinstance(time_start, (tuple, list)) else (time_start, time_start)
@@ -109,7 +119,18 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
             raise ValueError("diffuse_denoise: keep cannot be combined with solver_steps (the solver tails have no known-region "
                              "form)")
         keep = _keep_mask(keep, B, x.shape[1], vae.latent_shape()[1])
-    visited = [[], []]
+    if resample is not None:
+        resample = diffusion.resample_pair("diffuse_denoise", resample)
+        if keep is None:
+            raise ValueError("diffuse_denoise: resample needs keep: without kept points there is nothing to agree with")
+        if solver_steps is not None:
+            raise ValueError("diffuse_denoise: resample cannot be combined with solver_steps")
+        if any(isinstance(t, tuple) for t in pair):
+            raise ValueError("diffuse_denoise: resample cannot be combined with per-sample time_start (a sample's own walk "
+                             "would differ from the walk of its uniform call)")
+        if pair[1] > 0:
+            diffusion.resample_walk(pair[1], *resample)     # a walk that is too long is refused here
+    visited, rows = [[], []], [0, 0]
     names = SUBKEYS
     keyed = seeds is not None
     if keyed:
@@ -146,11 +167,14 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
             return eps_ori
         which = ("global", "local")[i]
         known = {"known": (eps_ori, keep)} if keep is not None and i == 1 else {}
+        if known and resample is not None:
+            known["resample"] = resample
         if isinstance(pair[i], tuple):   # per-sample starts: one keyed forward draw, max(start) replays of the from-rows capture
             top = max(pair[i])
             if top == 0:
                 return eps_ori
             visited[i] = list(range(top - 1, -1, -1))
+            rows[i] = top
             at = torch.tensor([t if t > 0 else -1 for t in pair[i]], dtype=torch.int64)   # start 0: neither diffused nor denoised
             eps_t = diffusion.diffuse(eps_ori, at, **key("diffuse_" + which))
             eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], torch.tensor(pair[i], dtype=torch.int64),
@@ -163,12 +187,14 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
         eps_t = diffusion.diffuse(eps_ori, pair[i], **key("diffuse_" + which))
         if solver_steps is not None:
             visited[i] = diffusion.solver_schedule(int(solver_steps), 'logsnr', pair[i])
+            rows[i] = len(visited[i])
             eps, _ = diffusion.run_dpm_solver(dae[i], B, shapes[i], steps=int(solver_steps), x_noisy=eps_t,
                                               condition_input=condition_input, clip_feat=clip_feat, keep_trajectory=False,
                                               graph=graph, conv_precision=conv_precision, stochastic=stochastic,
                                               t_start=pair[i], **key("chain_" + which))
         else:
             visited[i] = list(range(pair[i] - 1, -1, -1))
+            rows[i] = len(diffusion.resample_walk(pair[i], *resample)) if "resample" in known else pair[i]
             eps, _ = diffusion.run_denoising_diffusion_from_t(dae[i], B, shapes[i], pair[i], eps_t, temp=temp,
                                                               condition_input=condition_input, clip_feat=clip_feat, graph=graph,
                                                               keep_trajectory=False, conv_precision=conv_precision,
@@ -191,7 +217,7 @@ def diffuse_denoise(vae, dae, diffusion, x, time_start, *, temp=1.0, clip_feat=N
     points = vae.decoder(None, beta=None, context=local_new.view(flat_shape), style=style)
     info = {"global_original": global_ori, "global_edited": global_new, "local_original": local_ori,
             "local_edited": local_new, "condition_input": condition_input, "time_start": pair, "seeds": seeds,
-            "tail_steps": (visited[0], visited[1]), "keep": keep}
+            "tail_steps": (visited[0], visited[1]), "keep": keep, "resample": resample, "tail_rows": (rows[0], rows[1])}
     return points, info
 
 
@@ -217,8 +243,8 @@ def _keep_mask(keep, B, n_points, local_shape):
 def voxel_guided(vae, dae, diffusion, x, resolution, time_start, *, iou=False, **diffuse_denoise_kwargs):
     """Voxel-guided synthesis: x [B, N, 3] -> (points [B, N, 3], info).  The input is replaced by N points on the surface of
     its voxelisation at `resolution` (perturb.voxel_surface_points) and that cloud goes through diffuse_denoise(vae, dae,
-    diffusion, ., time_start, **diffuse_denoise_kwargs), which is not changed.  `seeds` (or `seed`) of the keyword arguments
-    address both: sample b's voxel points are drawn under seeds[b] at LION_VOXEL_STEP_WORD, a step word no draw of
+    diffusion, ., time_start, **diffuse_denoise_kwargs), which is not changed (`keep` and `resample` go through with the
+    rest).  `seeds` (or `seed`) of the keyword arguments address both: sample b's voxel points are drawn under seeds[b] at LION_VOXEL_STEP_WORD, a step word no draw of
     diffuse_denoise uses, so the two never share a counter.  info is diffuse_denoise's with 'input' (the voxel-surface cloud
     that was denoised) and 'faces' (int32[B], the exposed faces per cloud).
     iou=True adds the paper's measure of the experiment, the voxel IoU between the input's voxels and the voxelised output in
